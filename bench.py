@@ -1,9 +1,13 @@
 #!/usr/bin/env python
 """Learner throughput on MI355X — BASELINE.json metric.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the metric line; --dump-outputs DIR also writes
+what the last timed step returned and updated as DIR/<name>.npy.  Everything below "besides the metric" takes
+runs of its own and is measured only with --full.
 
 A "step" is one learner update (handyrl/train.py:372-392 body) on a
 device-resident synthetic replay batch in the make_batch layout: TicTacToe
@@ -12,7 +16,7 @@ losses, backward, SUM all-reduce of the gradients over RCCL (N > 1), grad
 clip 4.0 and Adam.  Every rank trains its own B=4096 x T=32 batch (weak
 scaling); value = N*B*T*K / max-over-ranks time of the K timed steps.
 
-Rank 0 prints ONE JSON line with, besides the metric:
+Rank 0 prints ONE JSON line with, besides the metric (--full):
   roofline      the step's dominant kernel, one chain block's backward (conv3x3_block_bwd2_kernel + its
                 weight-gradient fold, 3 launches, ~40% of the step): algorithmic bytes per launch / mean
                 duration from HIP events on the launch stream around the step's own launches (eager steps
@@ -617,6 +621,37 @@ def secondary_geister_rollout(device, E=2048, reps=2):
                                     'build container'}
 
 
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(path, out, net, limit=DUMP_LIMIT_BYTES):
+    """Write what the last timed step gave its caller as path/<name>.npy: the losses / dcnt LearnerStep.step
+    returned (step_<key>) and the training state it updated in place (param_<name>, buffer_<name>), float32
+    (integer buffers as float64).  Every array gets an equal share of `limit` bytes (64 MB); one larger than
+    its share is cut to the elements of its flattened form at np.random.default_rng(0)'s sorted choice of
+    indices, so the files hold at most `limit` bytes in all and every array is represented."""
+    import numpy as np
+    arrays = [('step_' + k, torch.as_tensor(v)) for k, v in sorted(out.items())]
+    arrays += [('param_' + k, v) for k, v in net.named_parameters()]
+    arrays += [('buffer_' + k, v) for k, v in net.named_buffers()]
+    os.makedirs(path, exist_ok=True)
+    share = limit // len(arrays)
+    for name, t in arrays:
+        t = t.detach()
+        a = t.to('cpu', torch.float32 if t.is_floating_point() else torch.float64).numpy().reshape(-1)
+        if a.nbytes > share:
+            a = a[dump_sample(a.size, share // a.itemsize)]
+        else:
+            a = a.reshape(t.shape if t.dim() else (1,))
+        np.save(os.path.join(path, name.replace('/', '_') + '.npy'), a)
+
+
+def dump_sample(size, count):
+    """The fixed sample of dump_outputs: `count` sorted indices into an array of `size` elements."""
+    import numpy as np
+    return np.sort(np.random.default_rng(0).choice(size, size=count, replace=False))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -627,10 +662,16 @@ def main():
     ap.add_argument('--batch', type=int, default=4096, help='trajectories per GPU (B)')
     ap.add_argument('--seq', type=int, default=32, help='forward_steps (T)')
     ap.add_argument('--graph', type=int, default=1, help='capture the step in HIP graphs (N>1: backward and update graphs around the all-reduce)')
-    ap.add_argument('--cpu-baseline', type=int, default=1)
-    ap.add_argument('--scan-iters', type=int, default=200)
-    ap.add_argument('--secondary', type=int, default=1, help='also time the B=4096 T=9 config (N=1)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one returned and updated as DIR/<name>.npy')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure the rooflines, the CPU baseline and the secondary configs (runs of their own)')
+    ap.add_argument('--cpu-baseline', type=int, default=1, help='with --full: time the CPU learner oracle (N=1)')
+    ap.add_argument('--scan-iters', type=int, default=200, help='with --full: launches in the scan timing')
+    ap.add_argument('--secondary', type=int, default=1, help='with --full: also time the secondary configs (N=1)')
     opts = ap.parse_args()
+    if opts.steps < 1:
+        ap.error('--steps must be at least 1')
 
     rank, world, local = hdist.world_from_env()
     if world != opts.gpus:
@@ -663,23 +704,51 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(opts.steps):
-        learner.step(batch)
+        out = learner.step(batch)
     barrier()
     elapsed = time.perf_counter() - t0
     if world > 1:
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
+    if opts.dump_outputs and rank == 0:
+        dump_outputs(opts.dump_outputs, out, net)
     stats, nb = learner.pop_stats()
-    # the roofline line is the step's dominant kernel, timed inside eager learner steps after the timed region,
-    # with the gradient all-reduce off (every rank runs them, so the ranks stay in step; rank 0 reports)
-    us_blk, n_blk = time_block_in_step(learner, batch, device)
-    if world > 1:
-        dist.barrier()
+    if opts.full:
+        # the roofline line is the step's dominant kernel, timed inside eager learner steps after the timed region,
+        # with the gradient all-reduce off (every rank runs them, so the ranks stay in step; rank 0 reports)
+        us_blk, n_blk = time_block_in_step(learner, batch, device)
+        if world > 1:
+            dist.barrier()
 
     if rank == 0:
         steps_total = world * B * T * opts.steps
         value = steps_total / elapsed
+        line = {
+            'metric': 'learner env-steps/sec at B=4096 T=32 (TicTacToe net, UPGO/VTRACE)',
+            'value': round(value, 1),
+            'unit': 'env-steps/s',
+            'n_gpus': world,
+            'steps': opts.steps,
+            'warmup': opts.warmup,
+            'ms_per_step': round(elapsed / opts.steps * 1e3, 4),
+            'timing_note': ('the first ~30 graph replays after the capture run 5-25% slow while the GPU clock '
+                            'settles, MFMA-bound kernels most (profiles/r06_replay_clock_ramp.txt); fewer warm-up '
+                            'steps put part of that ramp in the timed region'),
+            'higher_is_better': True,
+            'scaling': 'weak',
+            'vs_baseline': None,
+            'dtype': 'f32',
+            'data': 'synthetic (make_batch layout, SURVEY §8d D2), random-init weights',
+            'config': {'workload': 'TicTacToe SimpleConv2dModel learner step: forward + IS ratios + fused '
+                                   'HIP V-trace/UPGO scans + losses + backward + grad all-reduce + clip + Adam',
+                       'global_batch': world * B, 'per_gpu_batch': B, 'seq_len': T, 'players': 2,
+                       'parallelism': 'dp%d' % world, 'hip_graph': use_graph},
+            'full': opts.full,
+            'loss_per_dcnt': {k: v / max(stats.get('dcnt', 1.0), 1e-9) for k, v in stats.items()
+                              if k in ('p', 'v', 'ent', 'total')},
+        }
+    if rank == 0 and opts.full:
         hot = time_scan(device, B, T, opts.scan_iters)
         cold = time_scan(device, 1 << 18, T, 60, cold=True)
         scan_roof = {
@@ -738,35 +807,14 @@ def main():
         gee = secondary_geese_learner(device) if (opts.secondary and world == 1) else None
         hro = secondary_host_rollout(device) if (opts.secondary and world == 1) else None
         pro = secondary_player_rollout(device) if (opts.secondary and world == 1) else None
-        line = {
-            'metric': 'learner env-steps/sec at B=4096 T=32 (TicTacToe net, UPGO/VTRACE)',
-            'value': round(value, 1),
-            'unit': 'env-steps/s',
-            'n_gpus': world,
-            'steps': opts.steps,
-            'warmup': opts.warmup,
-            'ms_per_step': round(elapsed / opts.steps * 1e3, 4),
-            'timing_note': ('the first ~30 graph replays after the capture run 5-25% slow while the GPU clock '
-                            'settles, MFMA-bound kernels most (profiles/r06_replay_clock_ramp.txt); fewer warm-up '
-                            'steps put part of that ramp in the timed region'),
-            'higher_is_better': True,
-            'scaling': 'weak',
-            'vs_baseline': None,
-            'dtype': 'f32',
-            'data': 'synthetic (make_batch layout, SURVEY §8d D2), random-init weights',
-            'config': {'workload': 'TicTacToe SimpleConv2dModel learner step: forward + IS ratios + fused '
-                                   'HIP V-trace/UPGO scans + losses + backward + grad all-reduce + clip + Adam',
-                       'global_batch': world * B, 'per_gpu_batch': B, 'seq_len': T, 'players': 2,
-                       'parallelism': 'dp%d' % world, 'hip_graph': use_graph},
+        line.update({
             'roofline': roof,
             'scan_roofline': scan_roof,
             'net_roofline': net_roof,
             'loss_roofline': loss_roof,
             'block_roofline': block_roof,
             'cpu_baseline': cpu,
-            'loss_per_dcnt': {k: v / max(stats.get('dcnt', 1.0), 1e-9) for k, v in stats.items()
-                              if k in ('p', 'v', 'ent', 'total')},
-        }
+        })
         if cpu is not None:
             line['speedup_vs_cpu_baseline'] = round(value / cpu['value'], 1)
         if t9 is not None:
@@ -783,6 +831,7 @@ def main():
             line['host_rollout'] = hro
         if pro is not None:
             line['player_rollout'] = pro
+    if rank == 0:
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()

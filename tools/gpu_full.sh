@@ -10,5 +10,5 @@ tail -5 $out/gputests.log
 [ $rc -eq 0 ] || exit $rc
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1 || { tail -20 $out/smoke.log; exit 1; }
 tail -2 $out/smoke.log
-timeout -k 10 400 python3 bench.py > $out/bench.log 2>&1 || { tail -20 $out/bench.log; exit 1; }
+timeout -k 10 400 python3 bench.py --full > $out/bench.log 2>&1 || { tail -20 $out/bench.log; exit 1; }
 tail -1 $out/bench.log | cut -c1-300

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 tag=${1:-prof}
 out=gpurun_out/$tag
 mkdir -p $out
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o run -- python3 bench.py --cpu-baseline 0 --secondary 0 > $out/bench.log 2>&1
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o run -- python3 bench.py --full --cpu-baseline 0 --secondary 0 > $out/bench.log 2>&1
 timeout -s KILL 90 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/pmc_fetch -o run -- python3 tools/scan_pmc.py > $out/pmc_fetch.log 2>&1
 timeout -s KILL 90 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/pmc_write -o run -- python3 tools/scan_pmc.py > $out/pmc_write.log 2>&1
 # summaries on the box (the raw traces exceed gpurun's 64 MiB copy-back)

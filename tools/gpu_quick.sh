@@ -9,7 +9,7 @@ tests=${2:-tests}
 out=gpurun_out/$tag
 mkdir -p $out
 timeout -k 10 600 python -u -m pytest $tests -m gpu -x -q --timeout 120 --timeout-method thread > $out/gputests.log 2>&1
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o run -- python3 bench.py --cpu-baseline 0 --secondary 0 > $out/bench.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o run -- python3 bench.py > $out/bench.log 2>&1
 tr=$(ls $out/trace/*kernel_trace.csv | head -1)
 python3 tools/step_sequence.py $tr --marker FusedAdam > $out/step_sequence.txt
 python3 tools/prof_summary.py $tr per:FusedAdam > $out/step_kernels.md

@@ -24,7 +24,7 @@ timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $out/trace -o 
 tr=$(ls $out/trace/*kernel_trace.csv | head -1)
 python3 tools/replay_gaps.py $tr --marker adam_clip_kernel --skip 4 --count 40 > $out/replay_gaps.txt
 rm -f $tr
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o run -- python3 bench.py --cpu-baseline 0 --secondary 0 > $out/bench_under_stats.log 2>&1 || { tail -20 $out/bench_under_stats.log; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o run -- python3 bench.py --full --cpu-baseline 0 --secondary 0 > $out/bench_under_stats.log 2>&1 || { tail -20 $out/bench_under_stats.log; exit 1; }
 cp $(ls $out/stats/*kernel_stats.csv | head -1) $out/bench_kernel_stats.csv
 rm -f $out/stats/*kernel_trace.csv
 timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 > $out/bench_driver_args.log 2>&1 || { tail -20 $out/bench_driver_args.log; exit 1; }
