@@ -812,7 +812,12 @@ int hrl_output_mask_forward(const float *opol, const float *oval, const float *t
     const int64_t n = BT * A + (oval ? BT * P : 0);
     if (n > ((int64_t)1 << 40)) return HRL_EINVAL;
     const dim3 grid((unsigned)((n + kThreads - 1) / kThreads));
-    if (n + kThreads < ((int64_t)1 << 31))
+    // 32-bit indices only when the largest one fits: the thread index runs to n, but opol is read up to
+    // BT * Pq * A (P times the policy's extent when every player has a row) and the masks up to BT * P
+    int64_t top = n;
+    if (BT * Pq * A > top) top = BT * Pq * A;
+    if (BT * P > top) top = BT * P;
+    if (top + kThreads < ((int64_t)1 << 31))
         hipLaunchKernelGGL(out_mask_fwd_kernel<uint32_t>, grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream),
                            opol, oval, tmask, omask, amask, (uint32_t)BT, (int)P, (int)Pq, (int)A, pol, val);
     else

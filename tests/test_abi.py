@@ -134,3 +134,113 @@ def test_gboard_conv_refuses_packed_weights_of_another_shape():
         hnn.gboard_conv(x, torch.zeros(need - 16, dtype=torch.uint8), 64, 32)
     with pytest.raises(ValueError):
         hnn.gboard_conv(x, torch.zeros(need // 4, dtype=torch.float32), 64, 32)
+
+
+# ---- the recurrent-state, masked-rows and LSTM-gate entry points: argument validation (before any HIP call)
+
+def _fake(n, null_at=None):
+    """n distinct non-NULL, 16-byte aligned fake device addresses (never dereferenced: every call below returns
+    from the argument checks, or from the empty-batch exit)."""
+    vals = [4096 * (i + 1) for i in range(max(n, 1))]
+    if null_at is not None:
+        vals[null_at] = None
+    return (ctypes.c_void_p * len(vals))(*vals)
+
+
+def _hidden_codes(n=2, F=(8, 12), B=4, P=2, Pn=1, null_leaf=False, add_strides=None, dgathered=True, dstate=True,
+                  only=None):
+    """The return code of every hrl_hidden_* entry point (or those named in `only`) for one argument set."""
+    lib = _native.load()
+    m = max(n, 1)
+    Fv = (ctypes.c_int64 * m)(*[F[i % len(F)] for i in range(m)])
+    null_at = m - 1 if null_leaf else None
+    a, b, c, d = _fake(m, null_at), _fake(m), _fake(m, null_at), _fake(m)
+    add = _fake(m)
+    st = (ctypes.c_int64 * m)(*(add_strides or [Fv[i] + 4 for i in range(m)]))
+    mask = ctypes.c_void_p(64)
+    calls = {
+        'gather': lambda s: lib.hrl_hidden_gather(a, mask, B, P, n, Fv, s, c, None),
+        'gather_backward': lambda s: lib.hrl_hidden_gather_backward(a, mask, B, P, n, Fv, s, c, None),
+        'gather_backward_add': lambda s: lib.hrl_hidden_gather_backward_add(a, mask, B, P, n, Fv, s, add, st, c,
+                                                                            None),
+        'update': lambda s: lib.hrl_hidden_update(a, b, Pn, mask, B, P, n, Fv, c, None),
+        'update_backward': lambda s: lib.hrl_hidden_update_backward(a, mask, B, P, Pn, n, Fv, c, d, None),
+        'update_backward_add': lambda s: lib.hrl_hidden_update_backward_add(a, mask, B, P, Pn, n, Fv, add, st, c, d,
+                                                                            None),
+        'update_gather': lambda s: lib.hrl_hidden_update_gather(a, b, Pn, mask, mask, B, P, n, Fv, s, c, d, None),
+        'update_gather_backward': lambda s: lib.hrl_hidden_update_gather_backward(
+            a if dgathered else _fake(m, 0), mask, mask, B, P, Pn, n, Fv, s, add if dstate else None, st, add, st,
+            c, d, None),
+    }
+    return {(k, s): f(s) for k, f in calls.items() if only is None or k in only for s in (0, 1)}
+
+
+def test_hidden_entry_points_validate_arguments():
+    """hrl_hidden_*: HRL_EINVAL for 0 or 17 leaves, Pn not in {1, P}, F < 1, a NULL leaf pointer, an addend row
+    stride below F and a leaf with neither a gathered-input nor a state gradient; HRL_OK for an empty batch."""
+    EINVAL = _native.HRL_EINVAL
+    assert set(_hidden_codes(B=0).values()) == {_native.HRL_OK}
+    assert set(_hidden_codes(B=0, n=16, Pn=2).values()) == {_native.HRL_OK}
+    for kw in ({'n': 0}, {'n': 17}, {'F': (8, 0)}, {'F': (-4, 8)}, {'null_leaf': True}):
+        assert set(_hidden_codes(**kw).values()) == {EINVAL}, kw
+    with_pn = ('update', 'update_backward', 'update_backward_add', 'update_gather', 'update_gather_backward')
+    for Pn in (0, 2, 4):
+        assert set(_hidden_codes(P=3, Pn=Pn, only=with_pn).values()) == {EINVAL}, Pn
+    with_addend = ('gather_backward_add', 'update_backward_add', 'update_gather_backward')
+    assert set(_hidden_codes(add_strides=[8, 11], only=with_addend).values()) == {EINVAL}
+    assert set(_hidden_codes(add_strides=[7, 12], only=with_addend).values()) == {EINVAL}
+    fused = ('update_gather_backward',)
+    assert set(_hidden_codes(dgathered=False, dstate=False, only=fused).values()) == {EINVAL}
+    # a NULL gathered-input gradient is fine when that leaf's state gradient is given
+    assert set(_hidden_codes(B=0, dgathered=False, only=fused).values()) == {_native.HRL_OK}
+
+
+def test_masked_rows_copy_validates_arguments():
+    """hrl_masked_rows_copy: HRL_EINVAL for a row stride below F (either side) and for 17 leaves; E = 0 is OK."""
+    lib = _native.load()
+    mask = ctypes.c_void_p(64)
+
+    def code(n=2, dst_stride=(40, 40), src_stride=(36, 72), E=5):
+        m = max(n, 1)
+        F = (ctypes.c_int64 * m)(*[36] * m)
+        ds = (ctypes.c_int64 * m)(*[dst_stride[i % 2] for i in range(m)])
+        ss = (ctypes.c_int64 * m)(*[src_stride[i % 2] for i in range(m)])
+        return lib.hrl_masked_rows_copy(n, _fake(m), ds, _fake(m), ss, F, mask, E, None)
+
+    assert code(E=0) == _native.HRL_OK and code(n=16, E=0) == _native.HRL_OK
+    assert code(dst_stride=(40, 35)) == _native.HRL_EINVAL
+    assert code(src_stride=(35, 72)) == _native.HRL_EINVAL
+    assert code(n=17) == _native.HRL_EINVAL and code(n=17, E=0) == _native.HRL_EINVAL
+    assert code(n=0) == _native.HRL_EINVAL
+
+
+def test_lstm_gates_entry_points_validate_arguments():
+    """hrl_lstm_gates_*: HRL_EINVAL for a bias without zx, zx_stride < 4 H HW, dh_parts < 1 and L = 5; HRL_OK for
+    N = 0."""
+    lib = _native.load()
+    x = ctypes.c_void_p(4096)
+    H, HW = 4, 9
+    row = 4 * H * HW
+    EINVAL, OK = _native.HRL_EINVAL, _native.HRL_OK
+
+    def forward(N=2, zx=x, zx_stride=row, bias=None):
+        return lib.hrl_lstm_gates_forward(zx, zx_stride, x, x, N, H, HW, bias, 1, x, x, None, None)
+
+    def grouped(N=2, L=3, zx_strides=(row, row + 4, 2 * row), zh_extra=8):
+        m = max(L, 1)
+        st = (ctypes.c_int64 * m)(*[zx_strides[i % 3] for i in range(m)])
+        return lib.hrl_lstm_gates_forward_grouped(L, x, L * row + zh_extra, _fake(m), st, _fake(m), N, H, HW,
+                                                  _fake(m), _fake(m), None, None)
+
+    def backward_ex(N=2, parts=4):
+        return lib.hrl_lstm_gates_backward_ex(x, x, x, x, 4 * H * HW, parts, H * HW, x, N, H, HW, x, x, None, 1,
+                                              None)
+
+    assert forward(zx=None, zx_stride=0, bias=x) == EINVAL
+    assert forward(zx_stride=row - 1) == EINVAL
+    assert grouped(zx_strides=(row, row - 1, row)) == EINVAL
+    assert grouped(zh_extra=-1) == EINVAL
+    assert grouped(L=5) == EINVAL and grouped(L=0) == EINVAL
+    assert backward_ex(parts=0) == EINVAL and backward_ex(parts=-1) == EINVAL
+    assert forward(N=0) == OK and grouped(N=0) == OK and grouped(N=0, L=4) == OK and backward_ex(N=0) == OK
+    assert lib.hrl_lstm_gates_backward(x, x, x, x, x, 0, H, HW, x, x, None) == OK
