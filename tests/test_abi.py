@@ -244,3 +244,87 @@ def test_lstm_gates_entry_points_validate_arguments():
     assert backward_ex(parts=0) == EINVAL and backward_ex(parts=-1) == EINVAL
     assert forward(N=0) == OK and grouped(N=0) == OK and grouped(N=0, L=4) == OK and backward_ex(N=0) == OK
     assert lib.hrl_lstm_gates_backward(x, x, x, x, x, 0, H, HW, x, x, None) == OK
+
+
+# ---- the fused loss entry points: argument validation (before any HIP call)
+
+def _loss_forward_code(B=4, T=8, P=2, Pp=1, A=9, null=(), vt=3, pt=2, symmetrize=1, ws_short=0):
+    """hrl_loss_forward on fake device addresses; `null` names the pointer arguments passed as NULL."""
+    lib = _native.load()
+    names = ('tpol', 'bpol', 'action', 'emask', 'tmask', 'omask', 'progress', 'value', 'outcome', 'ret_out', 'ret',
+             'reward', 'workspace', 'losses')
+    assert set(null) <= set(names)
+    a = {n: None if n in null else ctypes.c_void_p(4096 * (i + 1)) for i, n in enumerate(names)}
+    size = lib.hrl_loss_workspace_bytes(B, T, P, Pp)
+    size = (size if size > 0 else 1 << 20) - ws_short
+    return lib.hrl_loss_forward(a['tpol'], a['bpol'], a['action'], B, T, P, Pp, A, a['emask'], a['tmask'], a['omask'],
+                                a['progress'], a['value'], a['outcome'], a['ret_out'], a['ret'], a['reward'], vt, pt,
+                                symmetrize, 0.7, 0.8, 0.1, 0.1, a['workspace'], size, a['losses'], None)
+
+
+def _loss_backward_code(B=4, T=8, P=2, Pp=1, A=9, null=(), ws_short=0):
+    lib = _native.load()
+    names = ('tpol', 'action', 'emask', 'tmask', 'omask', 'progress', 'value', 'ret_out', 'workspace', 'dlosses',
+             'g_tpol', 'g_value', 'g_ret')
+    assert set(null) <= set(names)
+    a = {n: None if n in null else ctypes.c_void_p(4096 * (i + 1)) for i, n in enumerate(names)}
+    size = lib.hrl_loss_workspace_bytes(B, T, P, Pp)
+    size = (size if size > 0 else 1 << 20) - ws_short
+    return lib.hrl_loss_backward(a['tpol'], a['action'], B, T, P, Pp, A, a['emask'], a['tmask'], a['omask'],
+                                 a['progress'], a['value'], a['ret_out'], 0.1, 0.1, a['workspace'], size,
+                                 a['dlosses'], a['g_tpol'], a['g_value'], a['g_ret'], None)
+
+
+BAD_LOSS_DIMS = ({'B': 0}, {'B': -1}, {'T': 0}, {'P': 0, 'Pp': 0}, {'P': 0}, {'P': 65, 'Pp': 65}, {'P': 65},
+                 {'P': 4, 'Pp': 2}, {'P': 4, 'Pp': 0}, {'P': 2, 'Pp': 3})
+
+
+def test_loss_workspace_bytes_validates_dimensions():
+    """hrl_loss_workspace_bytes: -1 for B < 1, T < 1, P in {0, 65} and Pp not in {1, P}; otherwise room for the
+    3 policy-shaped, 5 value-shaped and 1 step-shaped float arrays the backward reads."""
+    lib = _native.load()
+    for kw in BAD_LOSS_DIMS:
+        d = dict({'B': 4, 'T': 8, 'P': 2, 'Pp': 1}, **kw)
+        assert lib.hrl_loss_workspace_bytes(d['B'], d['T'], d['P'], d['Pp']) == -1, kw
+    for B, T, P, Pp in ((1, 1, 1, 1), (4, 8, 2, 1), (3, 33, 64, 64), (3, 100, 5, 1), (16389, 33, 8, 8),
+                        (4097, 3, 2, 2)):
+        BT = B * T
+        assert lib.hrl_loss_workspace_bytes(B, T, P, Pp) >= 4 * (3 * BT * Pp + 5 * BT * P + BT), (B, T, P, Pp)
+
+
+def test_loss_forward_validates_arguments():
+    """hrl_loss_forward: HRL_EINVAL for bad dimensions, A < 1, each required pointer NULL, value without outcome,
+    ret_out without ret or reward, symmetrize with P != 2, an algorithm outside MC..VTRACE and a workspace one
+    byte short.  No case gets as far as a launch."""
+    EINVAL = _native.HRL_EINVAL
+    for kw in BAD_LOSS_DIMS:
+        assert _loss_forward_code(symmetrize=0, **kw) == EINVAL, kw
+    for A in (0, -3):
+        assert _loss_forward_code(A=A) == EINVAL, A
+    for name in ('tpol', 'bpol', 'action', 'emask', 'tmask', 'omask', 'progress', 'losses', 'workspace'):
+        assert _loss_forward_code(null=(name,)) == EINVAL, name
+    assert _loss_forward_code(null=('outcome',)) == EINVAL
+    assert _loss_forward_code(null=('ret',)) == EINVAL
+    assert _loss_forward_code(null=('reward',)) == EINVAL
+    for P, Pp in ((1, 1), (3, 1), (3, 3), (64, 1)):
+        assert _loss_forward_code(P=P, Pp=Pp, symmetrize=1) == EINVAL, (P, Pp)
+    for vt, pt in ((-1, 0), (4, 0), (0, -1), (0, 4), (7, 7)):
+        assert _loss_forward_code(vt=vt, pt=pt) == EINVAL, (vt, pt)
+    assert _loss_forward_code(ws_short=1) == EINVAL
+    assert _loss_forward_code(P=3, Pp=3, symmetrize=0, null=('value', 'outcome', 'ret_out', 'ret', 'reward'),
+                              ws_short=1) == EINVAL
+
+
+def test_loss_backward_validates_arguments():
+    """hrl_loss_backward: HRL_EINVAL for bad dimensions, g_value without value, g_ret without ret_out, NULL dlosses
+    or g_tpol (or any other required pointer) and a short workspace."""
+    EINVAL = _native.HRL_EINVAL
+    for kw in BAD_LOSS_DIMS:
+        assert _loss_backward_code(**kw) == EINVAL, kw
+    assert _loss_backward_code(A=0) == EINVAL
+    assert _loss_backward_code(null=('value',)) == EINVAL
+    assert _loss_backward_code(null=('ret_out',)) == EINVAL
+    for name in ('dlosses', 'g_tpol', 'tpol', 'action', 'emask', 'tmask', 'omask', 'progress', 'workspace'):
+        assert _loss_backward_code(null=(name,)) == EINVAL, name
+    assert _loss_backward_code(ws_short=1) == EINVAL
+    assert _loss_backward_code(null=('value', 'g_value', 'ret_out', 'g_ret'), ws_short=1) == EINVAL
