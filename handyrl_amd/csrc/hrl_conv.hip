@@ -681,118 +681,7 @@ struct BlockBwdArgs {
     double *part;                                                // epilogue 2 sums [block][32][2]
     float *wpart;                                                // weight-gradient partials [block][tap][ci][co]
     int64_t M;
-    unsigned *tickets;                                           // block form 2: per-CU arrival tickets
-    int stagger;                                                 // block form 2: s_sleep(32)s of the later arrival
-    // a BatchNorm finalize folded into the prologue (fold_part nullptr: none; bnfold below): mode 0 = the input BN's
-    // forward statistics -> its alpha / beta (the conv's prologue), mode 1 = BN_i's backward sums -> k / mean(dy)
-    const double *fold_part;                                     // partial rows [fold_nblocks][32][2]
-    int fold_nblocks, fold_mode;
-    double fold_count, fold_eps;
-    float fold_momentum;
-    const float *fold_w, *fold_b;                                // mode 0: the BN's weight / bias
-    float *fold_rm, *fold_rv;                                    // mode 0: running statistics (workgroup 0)
-    float *fold_o0, *fold_o1, *fold_o2, *fold_o3;                // mode 0: mean invstd alpha beta; 1: dw db k gm
 };
-
-// ------------------------------------------------------------------ BatchNorm finalize in a consumer's prologue
-// hrl_bn_finalize_stats / _backward (bn_finalize_kernel, one group) as the first step of the kernel that consumes
-// its coefficients, instead of a launch of its own: every 512-thread workgroup folds the fold_nblocks partial rows
-// of all 32 channels in bn_finalize_kernel's exact order -- thread i of its 256 sums rows i, i + 256 (0.0 first),
-// then the fixed tree (i, i + 128), (i, i + 64), (i, i + 32) ... (i, i + 1) -- and computes the channel's
-// coefficients with its float operations; workgroup 0 writes the outputs the separate launch wrote (the running
-// statistics advance once).  Bit-identical to the two launches (tests/test_bn_gpu.py).  Here lane (c, k) of wave j
-// holds leaves j + 8 m (m < 32; one contiguous 512-byte row per wave load): the levels 128 .. 8 are its register
-// tree, 4, 2, 1 run over the eight waves' nodes through LDS.
-namespace bnfold {
-
-constexpr int kThreadsFold = 512;
-
-__device__ __forceinline__ void fold(const BlockBwdArgs &a, unsigned char *lds, float &c0, float &c1) {
-    double *sums = reinterpret_cast<double *>(lds);                 // [32][2]
-    double *part8 = reinterpret_cast<double *>(lds + 64 * 8 + 64 * 4);   // [8][64]: the tree's level-8 nodes
-    float *coef = reinterpret_cast<float *>(lds + 64 * 8);          // [2][32]
-    const int tid = threadIdx.x;
-    // lane (c, k) = tid & 63 reads one double of every row its wave j = tid >> 6 owns: rows j + 8 m, 512 contiguous
-    // bytes per wave instruction
-    const int ck = tid & 63, j = tid >> 6;
-    const int nb = a.fold_nblocks;
-    const double *pc = a.fold_part + ck;
-    double v[32];
-#pragma unroll
-    for (int m = 0; m < 32; ++m) {
-        const int i = j + 8 * m;
-        const double lo = i < nb ? pc[(int64_t)i * kC * 2] : 0.0;
-        const double hi = i + 256 < nb ? pc[(int64_t)(i + 256) * kC * 2] : 0.0;
-        v[m] = (0.0 + lo) + hi;      // bn_finalize_kernel's s = 0.0; s += part[i]; s += part[i + 256] (+0.0 exact)
-    }
-#pragma unroll
-    for (int w = 16; w >= 1; w >>= 1)
-#pragma unroll
-        for (int m = 0; m < w; ++m) v[m] += v[m + w];
-    part8[j * 64 + ck] = v[0];
-    __syncthreads();
-    if (tid < 64) {   // the levels 4, 2, 1 over the eight waves' nodes
-        double e[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) e[q] = part8[q * 64 + ck];
-#pragma unroll
-        for (int w = 4; w >= 1; w >>= 1)
-#pragma unroll
-            for (int q = 0; q < w; ++q) e[q] += e[q + w];
-        sums[ck] = e[0];
-    }
-    __syncthreads();
-    if (tid < kC) {
-        const int ch = tid;
-        const double S0 = sums[ch * 2], S1 = sums[ch * 2 + 1];
-        const double M = a.fold_count;
-        const bool out = blockIdx.x == 0;
-        if (a.fold_mode == 0) {   // bn_finalize_kernel mode 0's float operations
-            const float w = a.fold_w ? a.fold_w[ch] : 1.0f;
-            const double mean = S0 / M;
-            double var = S1 / M - mean * mean;
-            if (var < 0.0) var = 0.0;
-            const float meanf = (float)mean;
-            const float invstd = (float)(1.0 / sqrt(var + a.fold_eps));
-            const float alpha = invstd * w;
-            const float beta = (a.fold_b ? a.fold_b[ch] : 0.0f) - meanf * alpha;
-            coef[ch] = alpha;
-            coef[kC + ch] = beta;
-            if (out) {
-                const float momentum = a.fold_momentum;
-                a.fold_o0[ch] = meanf;
-                a.fold_o1[ch] = invstd;
-                a.fold_o2[ch] = alpha;
-                a.fold_o3[ch] = beta;
-                if (a.fold_rm) a.fold_rm[ch] = momentum * meanf + (1.0f - momentum) * a.fold_rm[ch];
-                if (a.fold_rv) {
-                    const float unbiased = (float)(M > 1.0 ? var * M / (M - 1.0) : var);
-                    a.fold_rv[ch] = momentum * unbiased + (1.0f - momentum) * a.fold_rv[ch];
-                }
-            }
-        } else {                  // mode 1: the BN's saved invstd is bn_invstd
-            const float invstd = a.bn_invstd[ch];
-            const float sum_dy = (float)S0, dot = (float)S1;
-            const float kc = dot * invstd * invstd / (float)M;
-            const float gm = sum_dy / (float)M;
-            coef[ch] = kc;
-            coef[kC + ch] = gm;
-            if (out) {
-                if (a.fold_o0) a.fold_o0[ch] = dot * invstd;
-                if (a.fold_o1) a.fold_o1[ch] = sum_dy;
-                a.fold_o2[ch] = kc;
-                a.fold_o3[ch] = gm;
-            }
-        }
-    }
-    __syncthreads();
-    const int ch = threadIdx.x & 31;
-    c0 = coef[ch];
-    c1 = coef[kC + ch];
-    __syncthreads();   // every lane has its coefficients before the caller's staging reuses these bytes
-}
-
-}  // namespace bnfold
 
 typedef unsigned int u32x3 __attribute__((ext_vector_type(3)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
@@ -1096,14 +985,6 @@ __global__ __launch_bounds__(kThreads) void conv3x3_block_bwd_kernel(BlockBwdArg
 // association across tiles than the per-wave kernel.
 namespace bb2 {
 
-// diagnostic variants (tools/bb2_variants.sh builds them; the product is 0): bit 1 = no stage VALU (raw bits
-// packed into the images), bit 2 = no MFMA phase, bit 4 = no epilogue / gin store, bit 8 = every wave computes
-// first, bit 16 = no gin store (epilogue kept), bit 32 = raised wave priority (s_setprio 2) through the MFMA phase
-#ifndef BB2_VARIANT
-#define BB2_VARIANT 0
-#endif
-constexpr int kVariant = BB2_VARIANT;
-
 constexpr int kWaves = 8;
 constexpr int kThreads = 64 * kWaves;
 constexpr int kPartBytes = kCells * kC * kTile * 2;        // one bf16 part image (9 KB)
@@ -1111,7 +992,7 @@ constexpr int kImgBytes = 3 * kPartBytes;                  // h, m, l (27 KB)
 constexpr int kDy0 = 0;                                    // dY images, buffers 0/1
 constexpr int kX0 = 2 * kImgBytes;                         // x' images, buffers 0/1
 // the epilogue's raw x (fp32, [row][channel][cell], rows kXrStride floats apart), buffers 0/1: staged with the
-// images instead of re-read from HBM (the re-read cost more than the MFMAs: tools/bb2_variants.sh)
+// images instead of re-read from HBM (the re-read cost more than the MFMAs)
 constexpr int kXrStride = kRow + 4;                        // 292: the 4 row groups of a read 16 banks apart
 constexpr int kXrBytes = kTile * kXrStride * 4;            // 18,688 B
 constexpr int kXr0 = 4 * kImgBytes;
@@ -1209,9 +1090,7 @@ __device__ __forceinline__ void run(const BlockBwdArgs &a, unsigned char *smem, 
     // BN_i's backward apply for channel ch (bn_bwd_apply_kernel's per-channel values), the prologue's BN_{i-1}
     float mu = 0.f, kk = 0.f, gmn = 0.f, is = 1.f, ww = 1.f, al = 1.f, be = 0.f;
     if constexpr (!kFwd) {
-        // BN_i's backward finalize (bnfold) first, while the registers are free (beside tile 0's loads it spilled)
-        if (a.fold_part) bnfold::fold(a, smem, kk, gmn);
-        else { kk = a.bn_k[ch]; gmn = a.bn_gm[ch]; }
+        kk = a.bn_k[ch]; gmn = a.bn_gm[ch];
         mu = a.bn_mean[ch]; is = a.bn_invstd[ch];
         ww = a.bn_w ? a.bn_w[ch] : 1.0f;
         al = is * ww;
@@ -1326,14 +1205,8 @@ __device__ __forceinline__ void run(const BlockBwdArgs &a, unsigned char *smem, 
                 dv[r] = d;
                 xv2[r] = xv;
             }
-            if constexpr (kVariant & 1) {
-                dp[0][i] = dp[1][i] = dp[2][i] = __builtin_amdgcn_perm(__float_as_uint(G[1][i]), __float_as_uint(G[0][i]), 0x07060302u);
-                xp[0][i] = xp[1][i] = __builtin_amdgcn_perm(__float_as_uint(X[1][i]), __float_as_uint(X[0][i]), 0x07060302u);
-                xp[2][i] = __builtin_amdgcn_perm(__float_as_uint(Y[1][i]), __float_as_uint(Y[0][i]), 0x07060302u);
-            } else {
-                hrl_split::split_pair(dv[0], dv[1], dp[0][i], dp[1][i], dp[2][i]);
-                if constexpr (!kFwd) hrl_split::split_pair(xv2[0], xv2[1], xp[0][i], xp[1][i], xp[2][i]);
-            }
+            hrl_split::split_pair(dv[0], dv[1], dp[0][i], dp[1][i], dp[2][i]);
+            if constexpr (!kFwd) hrl_split::split_pair(xv2[0], xv2[1], xp[0][i], xp[1][i], xp[2][i]);
         }
         const int half = rho0 >> 3, sub = 2 * (rho0 & 7);
 #pragma unroll
@@ -1356,12 +1229,7 @@ __device__ __forceinline__ void run(const BlockBwdArgs &a, unsigned char *smem, 
     f32x4 acc[kNq];
     auto compute = [&](int it) __attribute__((always_inline)) {
         const unsigned char *dyi = smem + kDy0 + (it & 1) * kImgBytes;
-        if constexpr (kVariant & 2) {
-            if constexpr (kIg) {
-#pragma unroll
-                for (int s = 0; s < kNq; ++s) acc[s] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            }
-        } else if constexpr (!kIg && kFwd) {
+        if constexpr (!kIg && kFwd) {
             // the forward has no weight gradient: these waves only stage
         } else if constexpr (!kIg) {
             // weight gradient: dW[tap] += x'_p^T (32 ci x 16 rows) . dY_q (16 rows x 32 co), p ascending
@@ -1436,7 +1304,7 @@ __device__ __forceinline__ void run(const BlockBwdArgs &a, unsigned char *smem, 
         }
     };
     auto epilogue = [&](int it) __attribute__((always_inline)) {   // accumulators -> gin, straight from registers
-        if constexpr (kIg && !(kVariant & 4)) {
+        if constexpr (kIg) {
             int rows;
             const __amdgpu_buffer_rsrc_t ro = rsrc_of(a.gin, it, rows);
             const int co = kCt * 16 + (lane & 15);
@@ -1483,27 +1351,25 @@ __device__ __forceinline__ void run(const BlockBwdArgs &a, unsigned char *smem, 
                 s2 += (double)t2;
             }
             // per row the wave's output cells are one run of kNq floats (rows past the batch: dropped)
-            if constexpr (!(kVariant & 16)) {
 #pragma unroll
-                for (int rr = 0; rr < 4; ++rr) {
-                    const int row = (lane >> 4) * 4 + rr;
-                    const int off = (row * kRow + co * kCells + R::kQ[0]) * 4;
-                    float v[kNq];
+            for (int rr = 0; rr < 4; ++rr) {
+                const int row = (lane >> 4) * 4 + rr;
+                const int off = (row * kRow + co * kCells + R::kQ[0]) * 4;
+                float v[kNq];
 #pragma unroll
-                    for (int s = 0; s < R::kNq; ++s) {
-                        v[s] = acc[s][rr];
-                        if constexpr (EPI == 3)
-                            if (!(rv[s][rr] > 0.f)) v[s] = 0.f;
-                    }
-                    u32x4 w;
-                    w.x = __float_as_uint(v[0]);
-                    w.y = __float_as_uint(v[1]);
-                    w.z = __float_as_uint(v[2]);
-                    w.w = __float_as_uint(v[3]);
-                    __builtin_amdgcn_raw_buffer_store_b128(w, ro, off, 0, 0);
-                    if constexpr (R::kNq > 4)
-                        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[4 % kNq]), ro, off + 16, 0, 0);
+                for (int s = 0; s < R::kNq; ++s) {
+                    v[s] = acc[s][rr];
+                    if constexpr (EPI == 3)
+                        if (!(rv[s][rr] > 0.f)) v[s] = 0.f;
                 }
+                u32x4 w;
+                w.x = __float_as_uint(v[0]);
+                w.y = __float_as_uint(v[1]);
+                w.z = __float_as_uint(v[2]);
+                w.w = __float_as_uint(v[3]);
+                __builtin_amdgcn_raw_buffer_store_b128(w, ro, off, 0, 0);
+                if constexpr (R::kNq > 4)
+                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[4 % kNq]), ro, off + 16, 0, 0);
             }
         }
     };
@@ -1519,10 +1385,8 @@ __device__ __forceinline__ void run(const BlockBwdArgs &a, unsigned char *smem, 
         // stage / issue run unconditionally (past the last tile they stage and load zeros that nothing reads):
         // a branch around them makes the compiler's wait for the loaded registers vmcnt(0) at the loop head,
         // which then also waits for the previous iteration's gin stores
-        if constexpr (R::kCFirst || (kVariant & 8)) {
-            if constexpr (kVariant & 32) __builtin_amdgcn_s_setprio(2);
+        if constexpr (R::kCFirst) {
             compute(it);
-            if constexpr (kVariant & 32) __builtin_amdgcn_s_setprio(0);
             epilogue(it);
             BB2_STAMP(it, 1);
             stage(it + 1);
@@ -1532,9 +1396,7 @@ __device__ __forceinline__ void run(const BlockBwdArgs &a, unsigned char *smem, 
             stage(it + 1);
             issue(it + 2);
             BB2_STAMP(it, 1);
-            if constexpr (kVariant & 32) __builtin_amdgcn_s_setprio(2);
             compute(it);
-            if constexpr (kVariant & 32) __builtin_amdgcn_s_setprio(0);
             epilogue(it);
             BB2_STAMP(it, 2);
         }
@@ -1575,398 +1437,6 @@ __device__ __forceinline__ void run(const BlockBwdArgs &a, unsigned char *smem, 
 
 }  // namespace bb2
 
-// ------------------------------------------------------------------ one chain block's backward, two workgroups per CU
-// conv3x3_block_bwd4_kernel<PRO, EPI, DG> (block form 2): bb2's arithmetic with the CU shared by TWO independent
-// 4-wave workgroups instead of one 8-wave workgroup.  bb2 double-buffered its images in 148 KB of LDS, so one
-// workgroup filled the CU and all 8 waves met at every tile's barrier: a wave whose loads came late held the other
-// seven (18-28 % of every tile at the barrier, MFMA busy 0.39 of the SIMD cycles: profiles/r05_bb2_stamps.txt).
-// Here a workgroup's images are single-buffered (dY and x' part images 2 x 27 KB + the epilogue's raw x 18.3 KB =
-// 72.3 KB), so two workgroups reside on every CU, one wave of each on every SIMD, and each runs
-//     MFMAs of tile k + epilogue | barrier | stage tile k+1 (registers -> images) | issue the loads of tile k+2 | barrier
-// -- while one workgroup waits at a barrier or stages, the other's MFMAs run on the same SIMDs: the tile skew is
-// absorbed by the other workgroup instead of costing all eight waves.  Per workgroup:
-//  * waves 0, 1: the input gradient of column tile ct = wave for ALL nine output cells (49 (p, q) pairs, 294
-//    v_mfma_f32_16x16x32_bf16), the three split parts of their weights in registers; a row's nine cells leave in
-//    one 36-byte run per lane (two dwordx4 + one dword);
-//  * waves 2, 3: the weight gradient of taps {0, 2, 4, 6, 8} (25 pairs) and {1, 3, 5, 7} (24 pairs), 32x32x16;
-//  * the waves stage the tile as bb2's eight (row pair, channel) diagonals: one each for the input-gradient waves
-//    (30 registers of loads in flight per lane beside their 144 of weights and accumulators), three each for the
-//    weight-gradient waves (90).
-// Same operands, same images and the same per-accumulator MFMA order as bb2: the input gradient is bit-identical;
-// the weight gradient sums 16 instead of 32 tiles per partial row (512 rows per launch: a different association
-// across tiles); the epilogue-2 sums are per workgroup (hrl_conv3x3_block_sum_blocks rows).
-namespace bb4 {
-
-// diagnostic variants (tools/bb4_variants.sh; the product is 0): bit 1 = loads of the first tile only, bit 2 = no
-// MFMA phase, bit 4 = no epilogue / gin store
-#ifndef BB4_VARIANT
-#define BB4_VARIANT 0
-#endif
-constexpr int kVariant = BB4_VARIANT;
-
-constexpr int kWaves = 4;
-constexpr int kThreads = 64 * kWaves;
-constexpr int kPartBytes = bb2::kPartBytes;
-constexpr int kImgBytes = bb2::kImgBytes;
-constexpr int kDy0 = 0;
-constexpr int kX0 = kImgBytes;
-constexpr int kXrStride = bb2::kXrStride;                  // 292
-constexpr int kXrBytes = bb2::kXrBytes;
-constexpr int kXr0 = 2 * kImgBytes;
-constexpr int kLdsBytes = kXr0 + kXrBytes;                 // 73,984 B
-static_assert(2 * kLdsBytes <= 160 * 1024, "two workgroups per CU");
-constexpr int kPerCu = 2;                                  // resident workgroups per CU
-constexpr int kGrid = 256 * kPerCu;
-
-// the weight-gradient waves' taps: corners + centre (4 x 4 + 9 = 25 pairs) and edges (4 x 6 = 24)
-template <int W> struct Taps;
-template <> struct Taps<2> { static constexpr int kN = 5; static constexpr int kT[5] = {0, 2, 4, 6, 8}; };
-template <> struct Taps<3> { static constexpr int kN = 4; static constexpr int kT[4] = {1, 3, 5, 7}; };
-template <> struct Taps<0> { static constexpr int kN = 1; static constexpr int kT[1] = {0}; };
-template <> struct Taps<1> { static constexpr int kN = 1; static constexpr int kT[1] = {0}; };
-
-// the (row pair, channel) diagonals a wave stages (bb2's diagonal of wave D: rows 2 ((D + ch/4) & 7) + {0, 1}), 30
-// registers of loads each: one for each input-gradient wave (108 registers of weights, 20 of accumulators, the
-// epilogue), three for each weight-gradient wave (80 / 64 accumulators) -- no wave spills (a spill reload is a
-// vector-memory operation: its wait would also wait for the next tile's loads)
-template <int W> struct Diags;
-template <> struct Diags<0> { static constexpr int kN = 1; static constexpr int kD[1] = {0}; };
-template <> struct Diags<1> { static constexpr int kN = 1; static constexpr int kD[1] = {1}; };
-template <> struct Diags<2> { static constexpr int kN = 3; static constexpr int kD[3] = {2, 4, 6}; };
-template <> struct Diags<3> { static constexpr int kN = 3; static constexpr int kD[3] = {3, 5, 7}; };
-
-// the lane id from an instruction the compiler may not hoist: the staging addresses derived from it are recomputed
-// where they are used (a few VALU) instead of held across the loop in registers the input-gradient waves lack
-__device__ __forceinline__ int fresh_lane() {
-    int l;
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-    return l;
-}
-
-template <bool PRO, int EPI, bool DG, int W>
-__device__ __forceinline__ void run(const BlockBwdArgs &a, unsigned char *smem, int lane, int delay) {
-    constexpr bool kIg = W < 2;
-    constexpr int kCt = W & 1;
-    constexpr int kNt = Taps<W>::kN;
-    const int ch = lane & 31, hh = lane >> 5;
-    // BN_i's backward apply for channel ch (bn_bwd_apply_kernel's per-channel values), the prologue's BN_{i-1}
-    const float mu = a.bn_mean[ch], kk = a.bn_k[ch], gmn = a.bn_gm[ch], is = a.bn_invstd[ch];
-    const float ww = a.bn_w ? a.bn_w[ch] : 1.0f;
-    const float al = is * ww;
-    const float be = (a.bn_b ? a.bn_b[ch] : 0.0f) - mu * al;
-    float pa = 1.f, pb = 0.f;
-    if constexpr (PRO) {
-        pa = a.in_alpha[ch];
-        pb = a.in_beta[ch];
-    }
-    // the input gradient's weights, all three parts of all nine taps in registers (bb2's fragment layout)
-    uint4 wh[kTaps], wm[kTaps], wl[kTaps];
-    if constexpr (kIg && DG) {
-        const int ci0 = 8 * (lane >> 4), j = lane & 15;
-#pragma unroll
-        for (int t = 0; t < kTaps; ++t) {
-            uint32_t hv[4], mv[4], lv[4];
-#pragma unroll
-            for (int d = 0; d < 4; ++d) {
-                const int tc = t * 2 + kCt;
-                const float w0 = a.wpk[(tc * kC + ci0 + 2 * d) * 16 + j];
-                const float w1 = a.wpk[(tc * kC + ci0 + 2 * d + 1) * 16 + j];
-                uint32_t h0, m0, l0, h1, m1, l1;
-                hrl_split::split3(w0, h0, m0, l0);
-                hrl_split::split3(w1, h1, m1, l1);
-                hv[d] = h0 | (h1 << 16);
-                mv[d] = m0 | (m1 << 16);
-                lv[d] = l0 | (l1 << 16);
-            }
-            wh[t] = make_uint4(hv[0], hv[1], hv[2], hv[3]);
-            wm[t] = make_uint4(mv[0], mv[1], mv[2], mv[3]);
-            wl[t] = make_uint4(lv[0], lv[1], lv[2], lv[3]);
-        }
-    }
-    float em = 0.f, ea = 1.f, eb = 0.f;     // epilogue 2: BN_{i-1} of this lane's output channel
-    if constexpr (EPI == 2 && kIg && DG) {
-        em = a.ep_mean[kCt * 16 + (lane & 15)];
-        ea = a.ep_alpha[kCt * 16 + (lane & 15)];
-        eb = a.ep_beta[kCt * 16 + (lane & 15)];
-    }
-    double s1 = 0.0, s2 = 0.0;
-    f32x16 wacc[kNt];
-#pragma unroll
-    for (int t = 0; t < kNt; ++t)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) wacc[t][i] = 0.f;
-
-    const int64_t ntiles = (a.M + kTile - 1) / kTile;
-    const int64_t t0 = blockIdx.x;
-    const int64_t step = gridDim.x;
-    const int n_iter = t0 < ntiles ? (int)((ntiles - 1 - t0) / step + 1) : 0;
-    // this lane stages rows rho_of(j), rho_of(j) + 1 (bb2's diagonals Diags<W>::kD) and cells c0 .. c0+4 of channel
-    // ch (lanes hh = 1 take cells 4..8)
-    constexpr int kNd = Diags<W>::kN;
-    auto rho_of = [](int j, int c) __attribute__((always_inline)) { return 2 * ((Diags<W>::kD[j] + (c >> 2)) & 7); };
-    float G[kNd][2][5], Y[kNd][2][5], X[kNd][2][5];
-    auto rsrc_of = [&](const float *base, int it, int &rows) __attribute__((always_inline)) {
-        const int64_t t = t0 + (int64_t)it * step;
-        const bool ok = it < n_iter;
-        rows = ok ? (int)min<int64_t>(kTile, a.M - t * kTile) : 0;
-        return wave_rsrc(base + (ok ? t * kTile * kRow : 0), (uint32_t)rows * kRow * 4);
-    };
-    auto issue = [&](int it) __attribute__((always_inline)) {   // loads of iteration it's tile (zeros past the end)
-        if constexpr (kVariant & 1) {
-            if (it > 0) return;
-        }
-        int rows;
-        const __amdgpu_buffer_rsrc_t rg = rsrc_of(a.g, it, rows), ry = rsrc_of(a.y, it, rows),
-                                     rx = rsrc_of(a.x, it, rows);
-        const int ln = fresh_lane(), cl = ln & 31, c0 = (ln >> 5) ? 4 : 0;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-#pragma unroll
-            for (int j = 0; j < kNd; ++j) {
-#pragma unroll
-                for (int r = 0; r < 2; ++r) {
-                    const int off = ((rho_of(j, cl) + r) * kRow + cl * kCells + c0) * 4;
-                    const __amdgpu_buffer_rsrc_t rs = k == 0 ? rg : (k == 1 ? ry : rx);
-                    float(&d)[5] = k == 0 ? G[j][r] : (k == 1 ? Y[j][r] : X[j][r]);
-                    const u32x3 v = __builtin_amdgcn_raw_buffer_load_b96(rs, off, 0, 0);
-                    const u32x2 u = __builtin_amdgcn_raw_buffer_load_b64(rs, off + 12, 0, 0);
-                    d[0] = __uint_as_float(v.x);
-                    d[1] = __uint_as_float(v.y);
-                    d[2] = __uint_as_float(v.z);
-                    d[3] = __uint_as_float(u.x);
-                    d[4] = __uint_as_float(u.y);
-                }
-            }
-        }
-    };
-    unsigned char *dyi = smem + kDy0;
-    unsigned char *xi = smem + kX0;
-    float *xr = reinterpret_cast<float *>(smem + kXr0);
-    auto stage = [&](int it) __attribute__((always_inline)) {   // registers -> the images
-        const int64_t t = t0 + (int64_t)it * step;
-        const int rows = (int)max<int64_t>(0, min<int64_t>(kTile, a.M - t * kTile));
-        const int ln = fresh_lane(), cl = ln & 31, c0 = (ln >> 5) ? 4 : 0;
-#pragma unroll
-        for (int j = 0; j < kNd; ++j) {
-            const int rj = rho_of(j, cl);
-            uint32_t dp[3][5], xp[3][5];
-#pragma unroll
-            for (int i = 0; i < 5; ++i) {
-                float dv[2], xv2[2];
-#pragma unroll
-                for (int r = 0; r < 2; ++r) {
-                    // dY = BN_i backward apply (bn_bwd_apply_kernel's float operations); rows past the batch are 0
-                    const bool valid = rj + r < rows;
-                    const float yv = Y[j][r][i];
-                    float gv = G[j][r][i];
-                    if (!(yv * al + be > 0.f)) gv = 0.f;
-                    const float tt = (yv - mu) * kk;
-                    float d = (((gv - gmn) - tt) * is) * ww;
-                    dv[r] = valid ? d : 0.f;
-                    float xv = X[j][r][i];
-                    if constexpr (PRO) {   // bn_apply_kernel's float operations
-                        const float u = xv * pa + pb;
-                        xv = u < 0.f ? 0.f : u;
-                    }
-                    xv2[r] = xv;
-                }
-                hrl_split::split_pair(dv[0], dv[1], dp[0][i], dp[1][i], dp[2][i]);
-                hrl_split::split_pair(xv2[0], xv2[1], xp[0][i], xp[1][i], xp[2][i]);
-            }
-            const int half = rj >> 3, sub = 2 * (rj & 7);
-#pragma unroll
-            for (int i = 0; i < 5; ++i) {
-                const int o = bb2::img_off(c0 + i, cl, half) + sub;
-#pragma unroll
-                for (int part = 0; part < 3; ++part) {
-                    *reinterpret_cast<uint32_t *>(dyi + part * kPartBytes + o) = dp[part][i];
-                    *reinterpret_cast<uint32_t *>(xi + part * kPartBytes + o) = xp[part][i];
-                }
-            }
-            if constexpr (DG && (EPI == 2 || EPI == 3)) {   // the epilogue's raw x (rows past the batch: 0)
-#pragma unroll
-                for (int r = 0; r < 2; ++r)
-#pragma unroll
-                    for (int i = 0; i < 5; ++i) xr[(rj + r) * kXrStride + cl * kCells + c0 + i] = X[j][r][i];
-            }
-        }
-    };
-    auto wgrad = [&]() __attribute__((always_inline)) {
-        // weight gradient: dW[tap] += x'_p^T (32 ci x 16 rows) . dY_q (16 rows x 32 co), p ascending
-        const int kg = lane >> 5;
-#pragma unroll
-        for (int p = 0; p < kCells; ++p) {
-            // one input cell's operands at a time: hoisting the next cells' LDS reads spilled (see Diags)
-            __builtin_amdgcn_sched_barrier(0);
-            const int o = bb2::img_off(p, ch, kg);
-            const uint4 Ah = *reinterpret_cast<const uint4 *>(xi + o);
-            const uint4 Am = *reinterpret_cast<const uint4 *>(xi + kPartBytes + o);
-            const uint4 Al = *reinterpret_cast<const uint4 *>(xi + 2 * kPartBytes + o);
-#pragma unroll
-            for (int s = 0; s < kNt; ++s) {
-                const int dy = Taps<W>::kT[s] / 3, dx = Taps<W>::kT[s] % 3;
-                const int qy = p / 3 - dy + 1, qx = p % 3 - dx + 1;
-                if (qy < 0 || qy > 2 || qx < 0 || qx > 2) continue;
-                const int ob = bb2::img_off(qy * 3 + qx, ch, kg);
-                const uint4 Bh = *reinterpret_cast<const uint4 *>(dyi + ob);
-                const uint4 Bm = *reinterpret_cast<const uint4 *>(dyi + kPartBytes + ob);
-                const uint4 Bl = *reinterpret_cast<const uint4 *>(dyi + 2 * kPartBytes + ob);
-                f32x16 c = wacc[s];
-                c = mfma32(Al, Bh, c);   // smallest terms first
-                c = mfma32(Am, Bm, c);
-                c = mfma32(Ah, Bl, c);
-                c = mfma32(Am, Bh, c);
-                c = mfma32(Ah, Bm, c);
-                c = mfma32(Ah, Bh, c);
-                wacc[s] = c;
-            }
-        }
-    };
-    // input gradient blocks (q, kCt) of output cells Q0 .. Q0+NQ-1: acc[s] += sum_p dY_p (16 rows x 32 co) .
-    // W'[tap(p, Q0+s)][kCt], p ascending, then their epilogue; the input-gradient waves run two such passes (cells
-    // 0-4 and 5-8), so their accumulators take 20 registers instead of 36 (the spill reloads a 36-accumulator form
-    // needed were vector-memory operations: each one's wait also waited for the next tile's loads)
-    float t1 = 0.f, t2 = 0.f;
-    auto ig_pass = [&](int it, auto q0c, auto nqc) __attribute__((always_inline)) {
-        constexpr int Q0 = decltype(q0c)::value, NQ = decltype(nqc)::value;
-        f32x4 acc[NQ];
-#pragma unroll
-        for (int s = 0; s < NQ; ++s) acc[s] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if constexpr (!(kVariant & 2)) {
-            const int g = lane >> 4, i = lane & 15, qq = i >> 2, pp = i & 3;
-            const int tr_sub = 8 * (pp & 1);
-#pragma unroll
-            for (int p = 0; p < kCells; ++p) {
-                uint32_t A[3][4];
-#pragma unroll
-                for (int part = 0; part < 3; ++part) {
-#pragma unroll
-                    for (int hlf = 0; hlf < 2; ++hlf) {
-                        const int o = part * kPartBytes + bb2::img_off(p, 8 * g + 4 * hlf + qq, pp >> 1) + tr_sub;
-                        const bb2::v4s r = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                            (bb2::lds_v4s *)((__attribute__((address_space(3))) unsigned char *)(dyi + o)));
-                        const uint2 u = __builtin_bit_cast(uint2, r);
-                        A[part][2 * hlf] = u.x;
-                        A[part][2 * hlf + 1] = u.y;
-                    }
-                }
-                const uint4 Ah = make_uint4(A[0][0], A[0][1], A[0][2], A[0][3]);
-                const uint4 Am = make_uint4(A[1][0], A[1][1], A[1][2], A[1][3]);
-                const uint4 Al = make_uint4(A[2][0], A[2][1], A[2][2], A[2][3]);
-#pragma unroll
-                for (int s = 0; s < NQ; ++s) {
-                    const int tap = tap_of(p, Q0 + s);
-                    if (tap < 0) continue;
-                    f32x4 c = acc[s];
-                    c = mfma_bf16(Al, wh[tap], c);   // smallest terms first
-                    c = mfma_bf16(Am, wm[tap], c);
-                    c = mfma_bf16(Ah, wl[tap], c);
-                    c = mfma_bf16(Am, wh[tap], c);
-                    c = mfma_bf16(Ah, wm[tap], c);
-                    c = mfma_bf16(Ah, wh[tap], c);
-                    acc[s] = c;
-                }
-            }
-        }
-        if constexpr (kVariant & 4) return;
-        __builtin_amdgcn_sched_barrier(0);
-        // epilogue: accumulators -> gin straight from registers, per row one run of the pass's NQ cells
-        int rows;
-        const __amdgpu_buffer_rsrc_t ro = rsrc_of(a.gin, it, rows);
-        const int co = kCt * 16 + (lane & 15);
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-            const int row = (lane >> 4) * 4 + rr;     // C/D: row = (lane>>4)*4 + reg, col = lane & 15
-            float v[NQ];
-#pragma unroll
-            for (int s = 0; s < NQ; ++s) {
-                v[s] = acc[s][rr];
-                if constexpr (EPI == 2 || EPI == 3) {
-                    const float x0 = xr[row * kXrStride + co * kCells + Q0 + s];
-                    if constexpr (EPI == 2) {   // bn_bwd_reduce_kernel's mask and sums
-                        const float gm = (x0 * ea + eb > 0.f && row < rows) ? v[s] : 0.f;
-                        t1 += gm;
-                        t2 += gm * (x0 - em);
-                    } else {
-                        if (!(x0 > 0.f)) v[s] = 0.f;
-                    }
-                }
-            }
-            const int off = (row * kRow + co * kCells + Q0) * 4;
-            u32x4 w0;
-            w0.x = __float_as_uint(v[0]);
-            w0.y = __float_as_uint(v[1]);
-            w0.z = __float_as_uint(v[2]);
-            w0.w = __float_as_uint(v[3]);
-            __builtin_amdgcn_raw_buffer_store_b128(w0, ro, off, 0, 0);
-            if constexpr (NQ > 4) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[4 % NQ]), ro, off + 16, 0, 0);
-        }
-    };
-    using I0 = std::integral_constant<int, 0>;
-    using I4 = std::integral_constant<int, 4>;
-    using I5 = std::integral_constant<int, 5>;
-
-    // stage(it + 1) follows the tile-it gin stores in every iteration, the first included (its loads were issued
-    // before them, in the prologue or the previous iteration), so the compiler's wait for the staged registers counts
-    // the stores as younger and never waits for them; stage / issue also run past the last tile (zeros nothing
-    // reads): a branch around them would make that wait a vmcnt(0)
-    if (n_iter > 0) {
-        issue(0);
-        stage(0);
-        issue(1);
-    }
-    for (int k = 0; k < delay; ++k) __builtin_amdgcn_s_sleep(32);
-    bb2::bar_lds();                                  // tile 0 staged
-    for (int it = 0; it < n_iter; ++it) {
-        if constexpr (!kIg) {
-            if constexpr (!(kVariant & 2)) wgrad();
-        } else if constexpr (DG) {
-            t1 = 0.f;
-            t2 = 0.f;
-            ig_pass(it, I0{}, I5{});                 // output cells 0-4
-            ig_pass(it, I5{}, I4{});                 // output cells 5-8
-            if constexpr (EPI == 2) {
-                s1 += (double)t1;
-                s2 += (double)t2;
-            }
-        }
-        bb2::bar_lds();                              // tile it's images read: the next stage may overwrite them
-        stage(it + 1);
-        issue(it + 2);
-        bb2::bar_lds();                              // tile it+1 staged
-    }
-    // weight-gradient partials partial[block][tap][ci][co] (C/D layout of 32x32x16: col = co = lane & 31,
-    // row = ci = (i&3) + 8(i>>2) + 4h); each tap has one owner wave
-    if constexpr (!kIg) {
-        constexpr int kW = kTaps * kC * kC;
-        float *outp = a.wpart + (int64_t)blockIdx.x * kW;
-        const int h = lane >> 5;
-#pragma unroll
-        for (int s = 0; s < kNt; ++s)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int ci = (i & 3) + 8 * (i >> 2) + 4 * h;
-                outp[(Taps<W>::kT[s] * kC + ci) * kC + ch] = wacc[s][i];
-            }
-    }
-    if constexpr (DG && EPI == 2) {   // the sums: waves 0-1 [wave][lane] -> channel wave*16 + (lane&15)
-        double *dred = reinterpret_cast<double *>(smem);     // the loop's last barrier freed the images
-        if (kIg) {
-            dred[(W * 64 + lane) * 2 + 0] = s1;
-            dred[(W * 64 + lane) * 2 + 1] = s2;
-        }
-        __syncthreads();
-        if (W == 0) {
-            const int c = lane >> 1, k = lane & 1, ct = c >> 4, l16 = c & 15;
-            double tot = 0.0;
-            for (int lg = 0; lg < 4; ++lg) tot += dred[(ct * 64 + lg * 16 + l16) * 2 + k];
-            a.part[((int64_t)blockIdx.x * kC + c) * 2 + k] = tot;
-        }
-    }
-}
-
-}  // namespace bb4
-
 // ------------------------------------------------------------------ the chain's forward conv, LDS-DMA ring
 // conv3x3_fwd_dma_kernel<PRO>: y = conv(x') with x' = relu(x*in_alpha + in_beta) (PRO) or x, and the output's BN
 // statistics (sum y, sum y^2 per channel): every output block is the same split MFMA sequence as bb2's forward (EPI 1)
@@ -1985,13 +1455,6 @@ __device__ __forceinline__ void run(const BlockBwdArgs &a, unsigned char *smem, 
 // Rows past the batch: their LDS-DMA is dropped by the descriptor's range check, so the ring holds stale rows
 // there; every output row depends on its own input row only, its store is dropped and its statistics masked.
 namespace fw3 {
-
-// diagnostic variants (FW3_VARIANT; the product is 0): bit 1 = the y stores by lane 0 only (same instruction count,
-// so the counted vmcnt waits stay right; ~no write traffic), bit 2 = no MFMAs
-#ifndef FW3_VARIANT
-#define FW3_VARIANT 0
-#endif
-constexpr int kVariant = FW3_VARIANT;
 
 constexpr int kSlots = 5;                                   // raw-x ring depth
 constexpr int kRawBytes = kTile * kRow * 4;                 // one tile of x (18,432 B, rows contiguous)
@@ -2105,10 +1568,8 @@ __device__ __forceinline__ void run(const BlockBwdArgs &a, unsigned char *smem, 
     }
     float pa = 1.f, pb = 0.f;
     if constexpr (PRO) {
-        if (!a.fold_part) {
-            pa = a.in_alpha[ch];
-            pb = a.in_beta[ch];
-        }
+        pa = a.in_alpha[ch];
+        pb = a.in_beta[ch];
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the weight and prologue loads, before any DMA is counted
     const uint32_t smem_base = (uint32_t)(uintptr_t)smem;
@@ -2162,11 +1623,6 @@ __device__ __forceinline__ void run(const BlockBwdArgs &a, unsigned char *smem, 
     // prologue: tiles 0 .. kSlots-1 in flight; tile 0 staged
 #pragma unroll
     for (int j = 0; j < kSlots; ++j) dma(j, j);
-    if constexpr (PRO) {
-        // the input BN's finalize (bnfold) while the ring fills; its loads' wait also covers the DMAs issued
-        // before them (the counted waits below then pass at once)
-        if (a.fold_part) bnfold::fold(a, smem, pa, pb);
-    }
     vm_wait<(kSlots - 1) * NP>();                            // tile 0 landed
     bb2::bar_lds();
     stage(0, 0);
@@ -2187,7 +1643,7 @@ __device__ __forceinline__ void run(const BlockBwdArgs &a, unsigned char *smem, 
         for (int s = 0; s < kNq; ++s) acc[s] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int p = 0; p < kCells; ++p) {
-            if (!g_uses_p<G>(p) || (kVariant & 2)) continue;
+            if (!g_uses_p<G>(p)) continue;
             uint32_t A[3][4];
 #pragma unroll
             for (int part = 0; part < 3; ++part) {
@@ -2242,9 +1698,6 @@ __device__ __forceinline__ void run(const BlockBwdArgs &a, unsigned char *smem, 
         for (int rr = 0; rr < 4; ++rr) {
             const int row = (lane >> 4) * 4 + rr;
             const int off = (row * kRow + co * kCells + C::kQ[0]) * 4;
-            if constexpr (kVariant & 1) {
-                if (lane != 0) continue;
-            }
             if constexpr (kNq == 3) {
                 u32x3 v;
                 v.x = __float_as_uint(acc[0][rr]);
@@ -2281,251 +1734,6 @@ __device__ __forceinline__ void run(const BlockBwdArgs &a, unsigned char *smem, 
 
 }  // namespace fw3
 
-// ------------------------------------------------------------------ the chain's forward conv, y staged in the ring
-// conv3x3_fwd_ls_kernel<PRO> (fwd form 3): fw3's ring, staging and split MFMA sequence (bit-identical y and sums),
-// with y leaving through LDS.  fw3 stores y straight from the accumulators: 8- and 12-byte runs 36 bytes apart per
-// lane, which cost more than the ring's reads (a ping-pong form measured them: profiles/r06_fw4_pingpong.txt).  A
-// tile of y is 18,432 contiguous bytes of HBM and exactly one ring slot, and tile it's slot is free once its x' is
-// staged, so:
-//  * iteration it: the MFMAs of tile it, then y(it) into ring slot it % kSlots as [row][288] fp32 (the HBM image);
-//  * iteration it + 1, after the barrier: wave W reads back its LDS-DMA pieces p = W, W + 8, W + 16 of that slot,
-//    stores them as 1 KiB contiguous buffer stores, then issues tile it + kSlots's LDS-DMA into the same pieces
-//    (only this wave reads or writes them, so no barrier between);
-//  * tile X's LDS-DMA is issued in iteration X - 4 (fw3: X - 5): one ring slot holds the drained tile.
-namespace fw5 {
-
-// diagnostic variants (FW5_VARIANT; the product is 0): bit 1 = the y stores by lane 0 only (same instruction
-// count), bit 2 = y written to LDS with the row groups 16 banks apart (wrong y: the bank-conflict-free write cost)
-#ifndef FW5_VARIANT
-#define FW5_VARIANT 0
-#endif
-constexpr int kVariant = FW5_VARIANT;
-
-constexpr int kSlots = fw3::kSlots;
-constexpr int kRawBytes = fw3::kRawBytes;
-constexpr int kImg0 = fw3::kImg0;
-constexpr int kRaw0 = fw3::kRaw0;
-constexpr int kLdsBytes = fw3::kLdsBytes;
-static_assert(kSlots == 5 && kRawBytes == kTile * kRow * 4, "one ring slot = one tile of y");
-
-template <bool PRO, int W>
-__device__ __forceinline__ void run(const BlockBwdArgs &a, unsigned char *smem, int lane) {
-    constexpr int kCt = W & 1, G = W >> 1;
-    using C = fw3::Cells<G>;
-    constexpr int kNq = C::kN;
-    constexpr int NP = fw3::pieces_of<W>();
-    const int64_t ntiles = (a.M + kTile - 1) / kTile;
-    const int64_t t0 = blockIdx.x;
-    const int64_t step = gridDim.x;
-    const int n_iter = t0 < ntiles ? (int)((ntiles - 1 - t0) / step + 1) : 0;
-    const int ch = lane & 31, hh = lane >> 5;
-    uint4 wh[kTaps], wm[kTaps], wl[kTaps];
-    {
-        const int ci0 = 8 * (lane >> 4), j = lane & 15;
-#pragma unroll
-        for (int t = 0; t < kTaps; ++t) {
-            if (!fw3::g_uses_tap<G>(t)) continue;
-            uint32_t hv[4], mv[4], lv[4];
-#pragma unroll
-            for (int d = 0; d < 4; ++d) {
-                const int tc = t * 2 + kCt;
-                const float w0 = a.wpk[(tc * kC + ci0 + 2 * d) * 16 + j];
-                const float w1 = a.wpk[(tc * kC + ci0 + 2 * d + 1) * 16 + j];
-                uint32_t h0, m0, l0, h1, m1, l1;
-                hrl_split::split3(w0, h0, m0, l0);
-                hrl_split::split3(w1, h1, m1, l1);
-                hv[d] = h0 | (h1 << 16);
-                mv[d] = m0 | (m1 << 16);
-                lv[d] = l0 | (l1 << 16);
-            }
-            wh[t] = make_uint4(hv[0], hv[1], hv[2], hv[3]);
-            wm[t] = make_uint4(mv[0], mv[1], mv[2], mv[3]);
-            wl[t] = make_uint4(lv[0], lv[1], lv[2], lv[3]);
-        }
-    }
-    float pa = 1.f, pb = 0.f;
-    if constexpr (PRO) {
-        pa = a.in_alpha[ch];
-        pb = a.in_beta[ch];
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the weight and prologue loads, before any DMA is counted
-    const uint32_t smem_base = (uint32_t)(uintptr_t)smem;
-    auto rows_of = [&](int it) __attribute__((always_inline)) {
-        const int64_t t = t0 + (int64_t)it * step;
-        return it < n_iter ? (int)min<int64_t>(kTile, a.M - t * kTile) : 0;
-    };
-    auto dma = [&](int it) __attribute__((always_inline)) {   // tile it -> ring slot it % kSlots (this wave's pieces)
-        const int64_t t = t0 + (int64_t)it * step;
-        const int rows = rows_of(it);
-        const u32x4 desc = fw3::wave_desc(a.x + (rows > 0 ? t * kTile * kRow : 0), (uint32_t)rows * kRow * 4);
-        const uint32_t raw = smem_base + kRaw0 + (uint32_t)(it % kSlots) * kRawBytes;
-#pragma unroll
-        for (int j = 0; j < NP; ++j) {
-            const int p = W + 8 * j;
-            fw3::dma16(desc, p * 1024 + lane * 16, raw + p * 1024);
-        }
-    };
-    const int c0 = hh ? 4 : 0;
-    const int rho0 = 2 * ((W + (ch >> 2)) & 7);              // bb2 staging wave W's row pair (its diagonal)
-    auto stage = [&](int it) __attribute__((always_inline)) {
-        const float *raw = reinterpret_cast<const float *>(smem + kRaw0 + (it % kSlots) * kRawBytes);
-        unsigned char *xi = smem + kImg0 + (it & 1) * bb2::kImgBytes;
-        uint32_t xp[3][5];
-        float xv[2][5];
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            const float *src = raw + (rho0 + r) * kRow + ch * kCells + c0;
-#pragma unroll
-            for (int i = 0; i < 5; ++i) {
-                float v = src[i];
-                if constexpr (PRO) {   // bn_apply_kernel's float operations
-                    const float u = v * pa + pb;
-                    v = u < 0.f ? 0.f : u;
-                }
-                xv[r][i] = v;
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 5; ++i) hrl_split::split_pair(xv[0][i], xv[1][i], xp[0][i], xp[1][i], xp[2][i]);
-        const int half = rho0 >> 3, sub = 2 * (rho0 & 7);
-#pragma unroll
-        for (int i = 0; i < 5; ++i) {
-            const int o = bb2::img_off(c0 + i, ch, half) + sub;
-#pragma unroll
-            for (int part = 0; part < 3; ++part)
-                *reinterpret_cast<uint32_t *>(xi + part * bb2::kPartBytes + o) = xp[part][i];
-        }
-    };
-    // tile it's y: this wave's pieces of its ring slot -> HBM (1 KiB contiguous per store), then tile it + kSlots's
-    // LDS-DMA into the same pieces (the stores have consumed the reads)
-    auto drain = [&](int it, bool refill) __attribute__((always_inline)) {
-        const int64_t t = t0 + (int64_t)it * step;
-        const int rows = rows_of(it);
-        const __amdgpu_buffer_rsrc_t od = wave_rsrc(a.gin + (rows > 0 ? t * kTile * kRow : 0), (uint32_t)rows * kRow * 4);
-        const unsigned char *raw = smem + kRaw0 + (it % kSlots) * kRawBytes;
-        u32x4 v[NP];
-#pragma unroll
-        for (int j = 0; j < NP; ++j) v[j] = *reinterpret_cast<const u32x4 *>(raw + (W + 8 * j) * 1024 + lane * 16);
-#pragma unroll
-        for (int j = 0; j < NP; ++j) {
-            if constexpr (kVariant & 1) {
-                if (lane != 0) continue;
-            }
-            __builtin_amdgcn_raw_buffer_store_b128(v[j], od, (W + 8 * j) * 1024 + lane * 16, 0, 0);
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the pieces are read before the DMA rewrites them
-        if (refill) dma(it + kSlots);
-    };
-    const int co = kCt * 16 + (lane & 15);
-    const int g = lane >> 4, i16 = lane & 15, qq = i16 >> 2, pp = i16 & 3;
-    const int tr_sub = 8 * (pp & 1);
-    double s1 = 0.0, s2 = 0.0;
-    // prologue: tiles 0 .. kSlots-2 in flight; tile 0 staged
-#pragma unroll
-    for (int j = 0; j < kSlots - 1; ++j) dma(j);
-    fw3::vm_wait<(kSlots - 2) * NP>();                       // tile 0 landed
-    bb2::bar_lds();
-    stage(0);
-    fw3::vm_wait<(kSlots - 3) * NP>();                       // tile 1 landed
-    bb2::bar_lds();
-    for (int it = 0; it < n_iter; ++it) {
-        BB2_STAMP(it, 0);
-        if (it == 0) dma(kSlots - 1);                        // ring slot kSlots-1 is still empty
-        else drain(it - 1, true);                            // y(it-1) out, tile it-1+kSlots in
-        stage(it + 1);                                       // runs past the last tile too (stale rows, unread)
-        BB2_STAMP(it, 1);
-        const unsigned char *img = smem + kImg0 + (it & 1) * bb2::kImgBytes;
-        f32x4 acc[kNq];
-#pragma unroll
-        for (int s = 0; s < kNq; ++s) acc[s] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int p = 0; p < kCells; ++p) {
-            if (!fw3::g_uses_p<G>(p)) continue;
-            uint32_t A[3][4];
-#pragma unroll
-            for (int part = 0; part < 3; ++part) {
-#pragma unroll
-                for (int hlf = 0; hlf < 2; ++hlf) {
-                    const int o = part * bb2::kPartBytes + bb2::img_off(p, 8 * g + 4 * hlf + qq, pp >> 1) + tr_sub;
-                    const bb2::v4s r = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                        (bb2::lds_v4s *)((__attribute__((address_space(3))) unsigned char *)(img + o)));
-                    const uint2 u = __builtin_bit_cast(uint2, r);
-                    A[part][2 * hlf] = u.x;
-                    A[part][2 * hlf + 1] = u.y;
-                }
-            }
-            const uint4 Ah = make_uint4(A[0][0], A[0][1], A[0][2], A[0][3]);
-            const uint4 Am = make_uint4(A[1][0], A[1][1], A[1][2], A[1][3]);
-            const uint4 Al = make_uint4(A[2][0], A[2][1], A[2][2], A[2][3]);
-#pragma unroll
-            for (int s = 0; s < kNq; ++s) {
-                const int tap = tap_of(p, C::kQ[s]);
-                if (tap < 0) continue;
-                f32x4 c = acc[s];
-                c = mfma_bf16(Al, wh[tap], c);   // smallest terms first (bb2's order)
-                c = mfma_bf16(Am, wm[tap], c);
-                c = mfma_bf16(Ah, wl[tap], c);
-                c = mfma_bf16(Am, wh[tap], c);
-                c = mfma_bf16(Ah, wm[tap], c);
-                c = mfma_bf16(Ah, wh[tap], c);
-                acc[s] = c;
-            }
-        }
-        BB2_STAMP(it, 2);
-        // the output's BN statistics (fp32 per tile, fp64 across tiles), then y into tile it's ring slot
-        const int rows = rows_of(it);
-        float t1 = 0.f, t2 = 0.f;
-#pragma unroll
-        for (int s = 0; s < kNq; ++s) {
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-                const int row = g * 4 + rr;
-                const float u = row < rows ? acc[s][rr] : 0.f;
-                t1 += u;
-                t2 += u * u;
-            }
-        }
-        s1 += (double)t1;
-        s2 += (double)t2;
-        {
-            float *yo = reinterpret_cast<float *>(smem + kRaw0 + (it % kSlots) * kRawBytes);
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr)
-#pragma unroll
-                for (int s = 0; s < kNq; ++s) {
-                    int o = (g * 4 + rr) * kRow + co * kCells + C::kQ[s];
-                    if constexpr (kVariant & 2) o = (o + 16 * g) % (kTile * kRow);
-                    yo[o] = acc[s][rr];
-                }
-        }
-        // tile it+2 landed: younger are this wave's later LDS-DMA pieces and y stores (tile X's DMA is issued in
-        // iteration X-4, after that iteration's stores; the prologue issued tiles 0..3, iteration 0 tile 4)
-        if (it == 0) fw3::vm_wait<2 * NP>();
-        else if (it == 1) fw3::vm_wait<3 * NP>();
-        else fw3::vm_wait<4 * NP>();
-        BB2_STAMP(it, 3);
-        bb2::bar_lds();                                      // y(it) and tile it+1's image staged
-    }
-    if (n_iter > 0) drain(n_iter - 1, false);
-    fw3::vm_wait<0>();
-    // the sums: [wave][lane] -> channel (wave & 1) * 16 + (lane & 15), waves and lane groups in a fixed order
-    __syncthreads();
-    double *dred = reinterpret_cast<double *>(smem);
-    dred[(W * 64 + lane) * 2 + 0] = s1;
-    dred[(W * 64 + lane) * 2 + 1] = s2;
-    __syncthreads();
-    if (W == 0) {
-        const int c = lane >> 1, k = lane & 1, ct = c >> 4, l16 = c & 15;
-        double tot = 0.0;
-        for (int w = ct; w < 8; w += 2)
-            for (int lg = 0; lg < 4; ++lg) tot += dred[(w * 64 + lg * 16 + l16) * 2 + k];
-        a.part[((int64_t)blockIdx.x * kC + c) * 2 + k] = tot;
-    }
-}
-
-}  // namespace fw5
-
-
 template <bool PRO>
 __global__ __launch_bounds__(bb2::kThreads) void conv3x3_fwd_dma_kernel(BlockBwdArgs a) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[fw3::kLdsBytes];
@@ -2540,23 +1748,6 @@ __global__ __launch_bounds__(bb2::kThreads) void conv3x3_fwd_dma_kernel(BlockBwd
     case 5: fw3::run<PRO, 5>(a, smem, lane); break;
     case 6: fw3::run<PRO, 6>(a, smem, lane); break;
     default: fw3::run<PRO, 7>(a, smem, lane); break;
-    }
-}
-
-template <bool PRO>
-__global__ __launch_bounds__(bb2::kThreads) void conv3x3_fwd_ls_kernel(BlockBwdArgs a) {
-    __shared__ __attribute__((aligned(16))) unsigned char smem[fw5::kLdsBytes];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    switch (wave) {
-    case 0: fw5::run<PRO, 0>(a, smem, lane); break;
-    case 1: fw5::run<PRO, 1>(a, smem, lane); break;
-    case 2: fw5::run<PRO, 2>(a, smem, lane); break;
-    case 3: fw5::run<PRO, 3>(a, smem, lane); break;
-    case 4: fw5::run<PRO, 4>(a, smem, lane); break;
-    case 5: fw5::run<PRO, 5>(a, smem, lane); break;
-    case 6: fw5::run<PRO, 6>(a, smem, lane); break;
-    default: fw5::run<PRO, 7>(a, smem, lane); break;
     }
 }
 
@@ -2575,41 +1766,6 @@ __global__ __launch_bounds__(bb2::kThreads) void conv3x3_block_bwd2_kernel(Block
     case 6: bb2::run<PRO, EPI, 6>(a, smem, lane); break;
     default: bb2::run<PRO, EPI, 7>(a, smem, lane); break;
     }
-}
-
-// two 4-wave workgroups per CU: at most 256 registers per lane (two waves per SIMD), 72.3 KB of LDS each
-template <bool PRO, int EPI, bool DG>
-__global__ __launch_bounds__(bb4::kThreads, 2) void conv3x3_block_bwd4_kernel(BlockBwdArgs a) {
-    __shared__ __attribute__((aligned(16))) unsigned char smem[bb4::kLdsBytes];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // the two workgroups of a CU run the same program with a barrier per phase and fall into lockstep (both
-    // staging, then both issuing MFMAs; MI355X_MICROARCH.md "Two waves per SIMD" item 9): the later arrival on its
-    // CU (a per-CU ticket: HW_ID's CU/SH/SE fields and XCC_ID) starts `stagger` s_sleep(32)s behind
-    int delay = 0;
-    if (a.stagger > 0) {
-        if (threadIdx.x == 0) {      // one lane: a vector atomic
-            unsigned hw, xcc;
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-            const unsigned key = ((xcc & 7u) << 8) | ((hw >> 8) & 0xffu);
-            *reinterpret_cast<volatile unsigned *>(smem) = atomicAdd(a.tickets + key, 1u) & 1u;
-        }
-        __syncthreads();
-        delay = *reinterpret_cast<volatile unsigned *>(smem) ? a.stagger : 0;
-        delay = __builtin_amdgcn_readfirstlane(delay);
-        __syncthreads();
-    }
-#ifdef BB4_ONLY_W
-    bb4::run<PRO, EPI, DG, BB4_ONLY_W>(a, smem, lane, delay);
-#else
-    switch (wave) {
-    case 0: bb4::run<PRO, EPI, DG, 0>(a, smem, lane, delay); break;
-    case 1: bb4::run<PRO, EPI, DG, 1>(a, smem, lane, delay); break;
-    case 2: bb4::run<PRO, EPI, DG, 2>(a, smem, lane, delay); break;
-    default: bb4::run<PRO, EPI, DG, 3>(a, smem, lane, delay); break;
-    }
-#endif
 }
 
 // fold per-workgroup partials into dW[co][ci][3][3]: a workgroup owns 64 consecutive
@@ -2670,19 +1826,12 @@ __global__ void conv3x3_pack_n_kernel(WeightList wl, int n, float *__restrict__ 
 
 // Forward / input-gradient arithmetic: exact-split bf16 MFMA (1, default) or fp32 MFMA (0).
 int g_split = 1;
-// Chain block backward: 1 = the 8-wave tile-shared conv3x3_block_bwd2_kernel (default); 2 = two 4-wave workgroups
-// per CU, conv3x3_block_bwd4_kernel (round 6: bit-identical, slower -- DESIGN §4.3); 0 = the per-wave
-// conv3x3_block_bwd_kernel (the tests' reference form).  Forms 0 and 1 run the per-wave kernel when there is no
-// input gradient.
+// Chain block backward: 1 = the 8-wave tile-shared conv3x3_block_bwd2_kernel (default); 0 = the per-wave
+// conv3x3_block_bwd_kernel (the tests' reference form).  Both run the per-wave kernel when there is no input
+// gradient.
 int g_block_form = 1;
-// block form 2: the later-arriving workgroup of each CU starts this many s_sleep(32) behind (0: no stagger);
-// HRL_BB4_STAGGER overrides (tools)
-int g_bb4_stagger = [] {
-    const char *e = getenv("HRL_BB4_STAGGER");
-    return e ? atoi(e) : 0;
-}();
-// The chain's forward conv (epilogue 1, packed weights, no bias): 3 = the ring form with y staged through LDS (fw5),
-// 2 = the LDS-DMA ring form (fw3, default), 1 = the tile-shared form (bb2, EPI 1), 0 = conv3x3_kernel<PRO, 1>.
+// The chain's forward conv (epilogue 1, packed weights, no bias): 2 = the LDS-DMA ring form (fw3, default),
+// 1 = the tile-shared form (bb2, EPI 1), 0 = conv3x3_kernel<PRO, 1>.
 int g_fwd_form = 2;
 
 // One 4-wave workgroup per CU (LDS: 109 KB forward, 145 KB weight gradient);
@@ -2702,15 +1851,6 @@ int grid_for(int64_t M) {
     return (int)(blocks < kGrid ? blocks : kGrid);
 }
 
-// block form 2: one 16-row tile per workgroup and iteration, two workgroups per CU
-int grid4_for(int64_t M) {
-    const int64_t tiles = (M + kTile - 1) / kTile;
-    return (int)(tiles < bb4::kGrid ? tiles : bb4::kGrid);
-}
-
-// workgroups (= weight-gradient partial rows and epilogue-2 sum rows) of hrl_conv3x3_block_backward
-int block_grid_for(int64_t M) { return g_block_form == 2 ? grid4_for(M) : grid_for(M); }
-
 }  // namespace
 
 extern "C" {
@@ -2719,27 +1859,24 @@ extern "C" {
 int hrl_debug_set_stamps_conv(void *buf) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_hrl_stamps), &buf, sizeof(buf)); }
 #endif
 
-constexpr int64_t kTicketBytes = 2048 * 4;   // block form 2's per-CU tickets (any contents: only parity is used)
-
 int64_t hrl_conv3x3_workspace_bytes(int64_t M) {
     if (M < 1) return -1;
-    const int64_t rows = grid4_for(M) > grid_for(M) ? grid4_for(M) : grid_for(M);   // every block form's partials
-    return rows * kTaps * kC * kC * 4 + (int64_t)kTaps * 2 * kC * 16 * 4 * 2 + kTicketBytes;
+    return (int64_t)grid_for(M) * kTaps * kC * kC * 4 + (int64_t)kTaps * 2 * kC * 16 * 4 * 2;
 }
 
 int64_t hrl_conv3x3_stats_blocks(int64_t M) { return M < 1 ? -1 : grid_for(M); }
 
-int64_t hrl_conv3x3_block_sum_blocks(int64_t M) { return M < 1 ? -1 : block_grid_for(M); }
+int64_t hrl_conv3x3_block_sum_blocks(int64_t M) { return M < 1 ? -1 : grid_for(M); }
 
 int hrl_conv3x3_set_block_form(int form) {
     const int prev = g_block_form;
-    g_block_form = form < 0 ? 0 : (form > 2 ? 2 : form);
+    g_block_form = form < 0 ? 0 : (form > 1 ? 1 : form);
     return prev;
 }
 
 int hrl_conv3x3_set_fwd_form(int form) {
     const int prev = g_fwd_form;
-    g_fwd_form = form < 0 ? 0 : (form > 3 ? 3 : form);
+    g_fwd_form = form < 0 ? 0 : (form > 2 ? 2 : form);
     return prev;
 }
 
@@ -2775,10 +1912,7 @@ int hrl_conv3x3_forward_ex(const float *x, int64_t M, const float *in_alpha, con
         BlockBwdArgs a{};
         a.x = x; a.in_alpha = in_alpha; a.in_beta = in_beta; a.wpk = wpk; a.gin = y; a.part = part; a.M = M;
         const dim3 grid(grid_for(M)), block(bb2::kThreads);
-        if (g_fwd_form == 3) {
-            if (in_alpha) hipLaunchKernelGGL((conv3x3_fwd_ls_kernel<true>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((conv3x3_fwd_ls_kernel<false>), grid, block, 0, s, a);
-        } else if (g_fwd_form == 2) {
+        if (g_fwd_form == 2) {
             if (in_alpha) hipLaunchKernelGGL((conv3x3_fwd_dma_kernel<true>), grid, block, 0, s, a);
             else hipLaunchKernelGGL((conv3x3_fwd_dma_kernel<false>), grid, block, 0, s, a);
         } else if (in_alpha) {
@@ -2871,30 +2005,16 @@ int hrl_conv3x3_block_backward(const float *g, const float *y, int64_t M, const 
     if (gin && (!packed_flip || epilogue < 0 || epilogue == 1 || epilogue > 3)) return HRL_EINVAL;
     if (gin && epilogue == 2 && (!ep_mean || !ep_alpha || !ep_beta || !part)) return HRL_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int grid = block_grid_for(M);
+    const int grid = grid_for(M);
     float *wpart = static_cast<float *>(workspace) + kTaps * 2 * kC * 16 * 2;
     BlockBwdArgs a{g, y, bn_weight, bn_bias, save_mean, save_invstd, kcoef, gmean, x, in_alpha, in_beta, packed_flip,
                    ep_mean, ep_alpha, ep_beta, gin, part, wpart, M};
-    a.tickets = reinterpret_cast<unsigned *>(static_cast<char *>(workspace) + workspace_bytes - kTicketBytes);
-    a.stagger = g_bb4_stagger;
     const bool pro = in_alpha != nullptr;
 #define HRL_BLOCK_LAUNCH(PRO, EPI, DG) \
     hipLaunchKernelGGL((conv3x3_block_bwd_kernel<PRO, EPI, DG>), dim3(grid), dim3(kThreads), 0, s, a)
 #define HRL_BLOCK2_LAUNCH(PRO, EPI) \
     hipLaunchKernelGGL((conv3x3_block_bwd2_kernel<PRO, EPI>), dim3(grid), dim3(bb2::kThreads), 0, s, a)
-#define HRL_BLOCK4_LAUNCH(PRO, EPI, DG) \
-    hipLaunchKernelGGL((conv3x3_block_bwd4_kernel<PRO, EPI, DG>), dim3(grid), dim3(bb4::kThreads), 0, s, a)
-    if (g_block_form == 2) {
-        if (!gin) {
-            if (pro) HRL_BLOCK4_LAUNCH(true, 0, false); else HRL_BLOCK4_LAUNCH(false, 0, false);
-        } else if (epilogue == 2) {
-            if (pro) HRL_BLOCK4_LAUNCH(true, 2, true); else HRL_BLOCK4_LAUNCH(false, 2, true);
-        } else if (epilogue == 3) {
-            if (pro) HRL_BLOCK4_LAUNCH(true, 3, true); else HRL_BLOCK4_LAUNCH(false, 3, true);
-        } else {
-            if (pro) HRL_BLOCK4_LAUNCH(true, 0, true); else HRL_BLOCK4_LAUNCH(false, 0, true);
-        }
-    } else if (!gin) {
+    if (!gin) {
         if (pro) HRL_BLOCK_LAUNCH(true, 0, false); else HRL_BLOCK_LAUNCH(false, 0, false);
     } else if (g_block_form == 0) {   // the per-wave form (kept for comparison)
         if (epilogue == 2) {
@@ -2913,87 +2033,8 @@ int hrl_conv3x3_block_backward(const float *g, const float *y, int64_t M, const 
     }
 #undef HRL_BLOCK_LAUNCH
 #undef HRL_BLOCK2_LAUNCH
-#undef HRL_BLOCK4_LAUNCH
     int rc = status();
     if (rc || !dweight) return rc;   // no dweight: the partials stay for a later fold (hrl_grad_fold_norm)
-    hipLaunchKernelGGL(conv3x3_wgrad_reduce_kernel, dim3(kTaps * kC * kC / 64), dim3(256), 0, s, wpart, grid,
-                       dweight);
-    return status();
-}
-
-int hrl_conv3x3_forward_bnfold(const float *x, int64_t M, const double *prev_part, int64_t prev_nblocks,
-                               const float *gamma, const float *beta, float *running_mean, float *running_var,
-                               double momentum, double eps, float *save_mean, float *save_invstd, float *alpha,
-                               float *beta_out, const float *packed, float *y, double *part, void *workspace,
-                               int64_t workspace_bytes, void *stream) {
-    if (M < 1 || !x || !prev_part || prev_nblocks < 1 || !save_mean || !save_invstd || !alpha || !beta_out ||
-        !packed || !y || !part || !workspace)
-        return HRL_EINVAL;
-    if (!aligned16(x) || !aligned16(y) || workspace_bytes < hrl_conv3x3_workspace_bytes(M)) return HRL_EINVAL;
-    if (prev_part == part) return HRL_EINVAL;   // the prologue reads every row the epilogue rewrites
-    if (g_fwd_form != 2 || !g_split || prev_nblocks > 512 || M * kRow * 4 > 0xffffffffLL) {
-        // the other forms: the two launches
-        const int rc = hrl_bn_finalize_stats(prev_part, prev_nblocks, kC, M * kCells, gamma, beta, running_mean,
-                                             running_var, momentum, eps, save_mean, save_invstd, alpha, beta_out,
-                                             stream);
-        if (rc) return rc;
-        return hrl_conv3x3_forward_ex(x, M, alpha, beta_out, packed, nullptr, 2, y, 1, nullptr, nullptr, nullptr,
-                                      nullptr, part, workspace, workspace_bytes, stream);
-    }
-    BlockBwdArgs a{};
-    a.x = x; a.wpk = packed; a.gin = y; a.part = part; a.M = M;
-    a.fold_part = prev_part; a.fold_nblocks = (int)prev_nblocks; a.fold_mode = 0;
-    a.fold_count = (double)(M * kCells); a.fold_eps = eps; a.fold_momentum = (float)momentum;
-    a.fold_w = gamma; a.fold_b = beta; a.fold_rm = running_mean; a.fold_rv = running_var;
-    a.fold_o0 = save_mean; a.fold_o1 = save_invstd; a.fold_o2 = alpha; a.fold_o3 = beta_out;
-    hipLaunchKernelGGL((conv3x3_fwd_dma_kernel<true>), dim3(grid_for(M)), dim3(bb2::kThreads), 0,
-                       static_cast<hipStream_t>(stream), a);
-    return status();
-}
-
-int hrl_conv3x3_block_backward_bnfold(const float *g, const float *y, int64_t M, const float *bn_weight,
-                                      const float *bn_bias, const float *save_mean, const float *save_invstd,
-                                      const double *sums, int64_t sums_nblocks, float *dgamma, float *dbeta,
-                                      float *kcoef, float *gmean, const float *x, const float *in_alpha,
-                                      const float *in_beta, const float *packed_flip, float *dweight, float *gin,
-                                      int epilogue, const float *ep_mean, const float *ep_alpha, const float *ep_beta,
-                                      double *part, void *workspace, int64_t workspace_bytes, void *stream) {
-    if (!sums || sums_nblocks < 1 || !save_invstd || !kcoef || !gmean) return HRL_EINVAL;
-    if (part && sums == part) return HRL_EINVAL;   // the prologue reads every row the epilogue rewrites
-    const bool fused = g_block_form == 1 && gin && sums_nblocks <= 512;
-    if (!fused) {   // the other forms: the two launches
-        const int rc = hrl_bn_finalize_backward(sums, sums_nblocks, kC, M * kCells, bn_weight, save_invstd, dgamma,
-                                                dbeta, kcoef, gmean, stream);
-        if (rc) return rc;
-        return hrl_conv3x3_block_backward(g, y, M, bn_weight, bn_bias, save_mean, save_invstd, kcoef, gmean, x,
-                                          in_alpha, in_beta, packed_flip, dweight, gin, epilogue, ep_mean, ep_alpha,
-                                          ep_beta, part, workspace, workspace_bytes, stream);
-    }
-    if (M < 1 || !g || !y || !save_mean || !x || !workspace) return HRL_EINVAL;
-    if ((in_alpha == nullptr) != (in_beta == nullptr)) return HRL_EINVAL;
-    if (workspace_bytes < hrl_conv3x3_workspace_bytes(M) || M * kRow * 4 > 0xffffffffLL) return HRL_EINVAL;
-    if (!packed_flip || epilogue < 0 || epilogue == 1 || epilogue > 3) return HRL_EINVAL;
-    if (epilogue == 2 && (!ep_mean || !ep_alpha || !ep_beta || !part)) return HRL_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int grid = block_grid_for(M);
-    float *wpart = static_cast<float *>(workspace) + kTaps * 2 * kC * 16 * 2;
-    BlockBwdArgs a{g, y, bn_weight, bn_bias, save_mean, save_invstd, kcoef, gmean, x, in_alpha, in_beta, packed_flip,
-                   ep_mean, ep_alpha, ep_beta, gin, part, wpart, M};
-    a.fold_part = sums; a.fold_nblocks = (int)sums_nblocks; a.fold_mode = 1; a.fold_count = (double)(M * kCells);
-    a.fold_o0 = dgamma; a.fold_o1 = dbeta; a.fold_o2 = kcoef; a.fold_o3 = gmean;
-    const bool pro = in_alpha != nullptr;
-#define HRL_BLOCK2_LAUNCH(PRO, EPI) \
-    hipLaunchKernelGGL((conv3x3_block_bwd2_kernel<PRO, EPI>), dim3(grid), dim3(bb2::kThreads), 0, s, a)
-    if (epilogue == 2) {
-        if (pro) HRL_BLOCK2_LAUNCH(true, 2); else HRL_BLOCK2_LAUNCH(false, 2);
-    } else if (epilogue == 3) {
-        if (pro) HRL_BLOCK2_LAUNCH(true, 3); else HRL_BLOCK2_LAUNCH(false, 3);
-    } else {
-        if (pro) HRL_BLOCK2_LAUNCH(true, 0); else HRL_BLOCK2_LAUNCH(false, 0);
-    }
-#undef HRL_BLOCK2_LAUNCH
-    int rc = status();
-    if (rc || !dweight) return rc;
     hipLaunchKernelGGL(conv3x3_wgrad_reduce_kernel, dim3(kTaps * kC * kC / 64), dim3(256), 0, s, wpart, grid,
                        dweight);
     return status();
@@ -3002,7 +2043,7 @@ int hrl_conv3x3_block_backward_bnfold(const float *g, const float *y, int64_t M,
 int64_t hrl_conv3x3_wgrad_partials(int64_t M, int64_t *offset_bytes) {
     if (M < 1) return -1;
     if (offset_bytes) *offset_bytes = (int64_t)kTaps * 2 * kC * 16 * 2 * 4;
-    return block_grid_for(M);
+    return grid_for(M);
 }
 
 int hrl_conv3x3_wgrad(const float *x, const float *dy, int64_t M, int64_t C_in, int64_t C_out, float *dweight,

@@ -175,19 +175,18 @@ int64_t hrl_conv3x3_stats_blocks(int64_t M);
  * rounding per product), 0 the fp32 v_mfma_f32_16x16x4_f32.  Process-wide; returns the previous setting. */
 int hrl_conv3x3_set_split(int on);
 /* Kernel form of hrl_conv3x3_block_backward: 1 (the default) the 8-wave tile-shared, pipelined kernel (the next
- * tile staged in a second LDS buffer while the MFMAs run); 2 two independent 4-wave workgroups per CU, each
- * sharing a 16-row tile among its waves (single-buffered LDS images, ABI 25); 0 the per-wave kernel.
- * Forms 0 and 1 run the per-wave kernel without an input gradient.  The input gradient and the epilogue are the
- * same in all; the weight gradient sums the tiles in a different association per form.  Process-wide; returns
- * the previous setting. */
+ * tile staged in a second LDS buffer while the MFMAs run); 0 the per-wave kernel.  Values outside 0..1 are clamped.
+ * Both run the per-wave kernel without an input gradient.  The input gradient and the epilogue are the same in
+ * both; the weight gradient sums the tiles in a different association per form.  Process-wide; returns the
+ * previous setting. */
 int hrl_conv3x3_set_block_form(int form);
-/* Rows of epilogue-2 sums (32 x 2 doubles each) hrl_conv3x3_block_backward writes into `part` under the current
- * block form (ABI 25; form 2 writes more rows than hrl_conv3x3_stats_blocks). */
+/* Rows of epilogue-2 sums (32 x 2 doubles each) hrl_conv3x3_block_backward writes into `part`.  Since ABI 27 every
+ * block form writes one row per workgroup of the same grid, so this equals hrl_conv3x3_stats_blocks(M). */
 int64_t hrl_conv3x3_block_sum_blocks(int64_t M);
 /* The chain's forward conv with BN statistics (hrl_conv3x3_forward_ex, epilogue 1, packed weights, no bias):
- * 2 (default) = the LDS-DMA ring form (every wave computes, x' staged from a raw ring), 3 = the same with y staged
- * through the ring slot into 1 KiB contiguous stores (round 6, bit-identical), 1 = the block backward's tile-shared
- * form, 0 = the per-wave conv3x3_kernel (tools/fwd_form_bench.py).  Returns the previous. */
+ * 2 (default) = the LDS-DMA ring form (every wave computes, x' staged from a raw ring), 1 = the block backward's
+ * tile-shared form, 0 = the per-wave conv3x3_kernel (tools/fwd_form_bench.py).  Values outside 0..2 are clamped.
+ * Returns the previous. */
 int hrl_conv3x3_set_fwd_form(int form);
 /* Both packed layouts of n <= 8 weights (32, 32, 3, 3) in one launch: packed[(l*2 + f) * 9216], f = 0 forward,
  * 1 input gradient (host array of device pointers).  hrl_conv3x3_forward_ex with flip | 2 takes `weight`
@@ -223,36 +222,6 @@ int hrl_conv3x3_block_backward(const float *g, const float *y, int64_t M, const 
                                const float *in_beta, const float *packed_flip, float *dweight, float *gin,
                                int epilogue, const float *ep_mean, const float *ep_alpha, const float *ep_beta,
                                double *part, void *workspace, int64_t workspace_bytes, void *stream);
-
-/*
- * The BatchNorm finalize folded into the kernel that consumes it (ABI 26): the chain's kernels no longer wait on
- * a finalize launch of their own between them.
- *
- * hrl_conv3x3_forward_bnfold = hrl_bn_finalize_stats(prev_part, prev_nblocks, 32, M*9, gamma, beta, running_mean,
- *   running_var, momentum, eps, save_mean, save_invstd, alpha, beta_out) followed by hrl_conv3x3_forward_ex(x, M,
- *   alpha, beta_out, packed, NULL, 2, y, 1, ..., part): the previous conv's BN statistics -> its coefficients ->
- *   this conv's BN + ReLU prologue, epilogue 1 (this conv's statistics into part).  Under fwd form 2 (default) one
- *   launch: every workgroup folds the partial rows in bn_finalize_kernel's order (bit-identical coefficients),
- *   workgroup 0 writes the four outputs and advances the running statistics; other forms run the two launches.
- *   prev_part != part (the prologue reads every row the epilogue rewrites); prev_nblocks <= 512 for the fused form.
- * hrl_conv3x3_block_backward_bnfold = hrl_bn_finalize_backward(sums, sums_nblocks, 32, M*9, bn_weight,
- *   save_invstd, dgamma, dbeta, kcoef, gmean) followed by hrl_conv3x3_block_backward(... kcoef, gmean ...): one
- *   launch under block form 1 (default) with an input gradient, the two otherwise.  sums != part.
- * Both replace the finalize between two of the TicTacToe body's convs (tictactoe.py:57-65; BatchNorm2d's
- * statistics / backward reduction, train.py:383).
- */
-int hrl_conv3x3_forward_bnfold(const float *x, int64_t M, const double *prev_part, int64_t prev_nblocks,
-                               const float *gamma, const float *beta, float *running_mean, float *running_var,
-                               double momentum, double eps, float *save_mean, float *save_invstd, float *alpha,
-                               float *beta_out, const float *packed, float *y, double *part, void *workspace,
-                               int64_t workspace_bytes, void *stream);
-int hrl_conv3x3_block_backward_bnfold(const float *g, const float *y, int64_t M, const float *bn_weight,
-                                      const float *bn_bias, const float *save_mean, const float *save_invstd,
-                                      const double *sums, int64_t sums_nblocks, float *dgamma, float *dbeta,
-                                      float *kcoef, float *gmean, const float *x, const float *in_alpha,
-                                      const float *in_beta, const float *packed_flip, float *dweight, float *gin,
-                                      int epilogue, const float *ep_mean, const float *ep_alpha, const float *ep_beta,
-                                      double *part, void *workspace, int64_t workspace_bytes, void *stream);
 
 /*
  * Fused ConvLSTM cell gates (GeisterNet DRC, handyrl/envs/geister.py:48-63;

@@ -1,5 +1,5 @@
-"""Time one chain block's backward: the fused hrl_conv3x3_block_backward (the default two-workgroup form 2, the
-tile-shared form 1 and the per-wave form 0) vs the three launches it replaces.
+"""Time one chain block's backward: the fused hrl_conv3x3_block_backward (the default tile-shared form 1 and the
+per-wave form 0) vs the three launches it replaces.
 
     python tools/block_bench.py [--M 131072] [--iters 20]
 HRL_LIB_PATH selects another build of libhrl.so (diagnostic variants).  HIP events on the launch stream.
@@ -21,7 +21,7 @@ def main():
     ap.add_argument('--M', type=int, default=131072)
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--epi', type=int, default=2, help='epilogue of the fused launch: 0, 2 (BN sums) or 3 (mask)')
-    ap.add_argument('--forms', default='', help='only these block forms (comma list), e.g. 2,1')
+    ap.add_argument('--forms', default='', help='only these block forms (comma list), e.g. 1,0')
     opts = ap.parse_args()
     dev = torch.device('cuda', 0)
     lib = _native.load()
@@ -37,8 +37,7 @@ def main():
     _native.check(lib.hrl_conv3x3_pack_n(_native.ptr_array([w]), 1, P(packed), stream), 'pack')
     ws_bytes = lib.hrl_conv3x3_workspace_bytes(M)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    part = torch.empty(max(lib.hrl_conv3x3_stats_blocks(M), lib.hrl_conv3x3_block_sum_blocks(M)) * 64,
-                       dtype=torch.float64, device=dev)
+    part = torch.empty(lib.hrl_conv3x3_block_sum_blocks(M) * 64, dtype=torch.float64, device=dev)
     dw, gin, dy = torch.empty(32, 32, 3, 3, device=dev), torch.empty_like(g), torch.empty_like(g)
 
     def fused():
@@ -65,7 +64,7 @@ def main():
             fused()
             lib.hrl_conv3x3_set_block_form(prev)
         return run
-    cases = [('fused_two_wg_us', form(2), 2), ('fused_tile_shared_us', form(1), 1), ('fused_per_wave_us', form(0), 0),
+    cases = [('fused_tile_shared_us', form(1), 1), ('fused_per_wave_us', form(0), 0),
              ('three_launches_us', three, None)]
     if only is None:
         cases = [('fused_us', fused, None)] + cases
