@@ -103,6 +103,10 @@ SIGNATURES = {
                                                   _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, ctypes.c_int, _f32p,
                                                   _f32p, _f32p, ctypes.c_void_p, ctypes.c_void_p, _i64,
                                                   ctypes.c_void_p]),
+    'hrl_conv3x3_block_backward_dz': (ctypes.c_int, [_f32p, _f32p, _f32p, _f32p, _i64, _f32p, _f32p, _f32p, _f32p,
+                                                     _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p,
+                                                     ctypes.c_int, _f32p, _f32p, _f32p, ctypes.c_void_p,
+                                                     ctypes.c_void_p, _i64, ctypes.c_void_p]),
     'hrl_conv3x3_wgrad_ex': (ctypes.c_int, [_f32p, _f32p, _f32p, _f32p, _i64, _f32p, ctypes.c_void_p, _i64,
                                             ctypes.c_void_p]),
     'hrl_hidden_gather': (ctypes.c_int, [ctypes.c_void_p, _f32p, _i64, _i64, ctypes.c_int, ctypes.c_void_p,
@@ -162,6 +166,9 @@ SIGNATURES = {
     'hrl_heads_backward': (ctypes.c_int, [_f32p, _i64, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p,
                                           ctypes.c_void_p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p,
                                           _f32p, _f32p, _f32p, _f32p, ctypes.c_void_p, _i64, ctypes.c_void_p]),
+    'hrl_heads_backward_dz': (ctypes.c_int, [_f32p, _i64, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p,
+                                             ctypes.c_void_p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p,
+                                             _f32p, _f32p, _f32p, _f32p, ctypes.c_void_p, _i64, ctypes.c_void_p]),
     'hrl_bn_apply_residual': (ctypes.c_int, [_f32p, _f32p, _i64, _i64, _i64, _f32p, _f32p, _f32p, ctypes.c_void_p]),
     'hrl_bn_backward_masked': (ctypes.c_int, [_f32p, _f32p, _f32p, _i64, _i64, _i64, _f32p, _f32p, _f32p, _f32p,
                                               _f32p, _f32p, ctypes.c_void_p, _i64, ctypes.c_void_p]),
@@ -234,7 +241,7 @@ SIGNATURES = {
                                                       ctypes.c_void_p]),
 }
 
-ABI_VERSION = 27
+ABI_VERSION = 28
 
 _lib = None
 

@@ -681,6 +681,9 @@ struct BlockBwdArgs {
     double *part;                                                // epilogue 2 sums [block][32][2]
     float *wpart;                                                // weight-gradient partials [block][tap][ci][co]
     int64_t M;
+    // conv3x3_block_bwd2_kernel<PRO, 2, true> only: g is the heads' dz (M, 28) and dL/d out = W1^T dz is rebuilt
+    // from the 1x1 head convs' weights (policy [2][32], value [32])
+    const float *w1p = nullptr, *w1v = nullptr;
 };
 
 typedef unsigned int u32x3 __attribute__((ext_vector_type(3)));
@@ -998,6 +1001,16 @@ constexpr int kXrBytes = kTile * kXrStride * 4;            // 18,688 B
 constexpr int kXr0 = 4 * kImgBytes;
 constexpr int kLdsBytes = kXr0 + 2 * kXrBytes;             // 147,968 B
 static_assert(kLdsBytes <= 160 * 1024, "LDS");
+// the dz form (run<PRO, 2, W, true>): the heads' dz rows of a tile (16 x 28 floats, contiguous in HBM), 2 slots.
+// With the row stride of 28 floats the eight row pairs a wave stages fall on distinct banks and the lanes of a row
+// pair broadcast: the stage's dword reads are conflict-free.  (A [m][12] row layout read as b128 + b32 measured the
+// same, tools/block_bench.py --dz: 172.0 vs 172.9 us.)
+constexpr int kDzStride = 28;
+constexpr int kDzBytes = kTile * kDzStride * 4;            // 1,792 B
+constexpr int kDz0 = kLdsBytes;
+constexpr int kLdsBytesDz = kDz0 + 2 * kDzBytes;           // 151,552 B
+static_assert(kLdsBytesDz <= 160 * 1024, "LDS");
+static_assert(kDzBytes / 4 <= 7 * 64, "a dword per lane of waves 0..6");
 
 typedef short v4s __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) v4s lds_v4s;
@@ -1075,8 +1088,12 @@ template <int W> __device__ constexpr bool uses_tap(int t) {
 #define BB2_STAMP(it, k) do { } while (0)
 #endif
 
-template <bool PRO, int EPI, int W>
+// DZ (the chain's last block behind the fused heads): a.g is the heads' dz (M, 28) instead of dL/d out (M, 288).
+// The tile's dz rows pass through a small LDS slot (loaded one tile ahead of y and x, a dword per lane of waves
+// 0..6) and stage() rebuilds g[ch][q] = sum_m W1[m][ch] dz[m][q] with heads_bwd2_kernel's float operations.
+template <bool PRO, int EPI, int W, bool DZ = false>
 __device__ __forceinline__ void run(const BlockBwdArgs &a, unsigned char *smem, int lane) {
+    static_assert(!DZ || EPI == 2, "the dz form is the last chain block's");
     using R = Role<W>;
     constexpr bool kIg = R::kIg;
     constexpr int kNq = R::kNq > 0 ? R::kNq : 1;
@@ -1100,6 +1117,12 @@ __device__ __forceinline__ void run(const BlockBwdArgs &a, unsigned char *smem, 
     if constexpr (PRO) {
         pa = a.in_alpha[ch];
         pb = a.in_beta[ch];
+    }
+    float w1[3] = {0.f, 0.f, 0.f};   // DZ: W1[m][ch] (m = 0, 1 the policy head's, 2 the value head's)
+    if constexpr (DZ) {
+        w1[0] = a.w1p[ch];
+        w1[1] = a.w1p[kC + ch];
+        w1[2] = a.w1v[ch];
     }
     // the input gradient's weights: all three parts of its taps in registers ([tap][ct][part][lane] layout of
     // conv3x3_block_bwd_kernel's LDS fragments: lane l holds W'[tap][ci = 8(l>>4) + e][co = 16ct + (l&15)])
@@ -1164,7 +1187,7 @@ __device__ __forceinline__ void run(const BlockBwdArgs &a, unsigned char *smem, 
         for (int r = 0; r < 2; ++r) {
             const int off = ldoff + r * kRow * 4;
 #pragma unroll
-            for (int k = kFwd ? 2 : 0; k < 3; ++k) {
+            for (int k = kFwd ? 2 : (DZ ? 1 : 0); k < 3; ++k) {
                 const __amdgpu_buffer_rsrc_t rs = k == 0 ? rg : (k == 1 ? ry : rx);
                 float(&d)[5] = k == 0 ? G[r] : (k == 1 ? Y[r] : X[r]);
                 const u32x3 v = __builtin_amdgcn_raw_buffer_load_b96(rs, off, 0, 0);
@@ -1177,11 +1200,31 @@ __device__ __forceinline__ void run(const BlockBwdArgs &a, unsigned char *smem, 
             }
         }
     };
+    // DZ: dword W * 64 + lane of iteration it's dz rows (zeros past the tile's rows and past the last tile) ...
+    auto load_dz = [&](int it) __attribute__((always_inline)) {
+        float v = 0.f;
+        if constexpr (DZ && W < 7) {
+            const int64_t t = t0 + (int64_t)it * step;
+            const bool ok = it < n_iter;
+            const int rows = ok ? (int)min<int64_t>(kTile, a.M - t * kTile) : 0;
+            const __amdgpu_buffer_rsrc_t rz =
+                wave_rsrc(a.g + (ok ? t * kTile * kDzStride : 0), (uint32_t)rows * kDzStride * 4);
+            v = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rz, (W * 64 + lane) * 4, 0, 0));
+        }
+        return v;
+    };
+    // ... and into slot it & 1, one barrier before stage(it) reads it
+    auto put_dz = [&](int it, float v) __attribute__((always_inline)) {
+        if constexpr (DZ && W < 7)
+            reinterpret_cast<float *>(smem + kDz0 + (it & 1) * kDzBytes)[W * 64 + lane] = v;
+    };
+    float DZv = 0.f;
     auto stage = [&](int it) __attribute__((always_inline)) {   // registers -> the images of buffer it & 1
         const int64_t t = t0 + (int64_t)it * step;
         const int rows = (int)max<int64_t>(0, min<int64_t>(kTile, a.M - t * kTile));
         unsigned char *dyi = smem + kDy0 + (it & 1) * kImgBytes;
         unsigned char *xi = smem + kX0 + (it & 1) * kImgBytes;
+        const float *dzl = reinterpret_cast<const float *>(smem + kDz0 + (it & 1) * kDzBytes);   // DZ only
         uint32_t dp[3][5], xp[3][5];
 #pragma unroll
         for (int i = 0; i < 5; ++i) {
@@ -1191,7 +1234,15 @@ __device__ __forceinline__ void run(const BlockBwdArgs &a, unsigned char *smem, 
                 // dY = BN_i backward apply (bn_bwd_apply_kernel's float operations); rows past the batch are 0
                 const bool valid = rho0 + r < rows;
                 const float yv = Y[r][i];
-                float gv = G[r][i];
+                float gv;
+                if constexpr (DZ) {   // heads_bwd2_kernel's dh: t = 0; t += W1[m][ch] * dz[m][q], m ascending
+                    const float *dzr = dzl + (rho0 + r) * kDzStride + c0 + i;
+                    gv = 0.f;
+#pragma unroll
+                    for (int m = 0; m < 3; ++m) gv += w1[m] * dzr[m * kCells];
+                } else {
+                    gv = G[r][i];
+                }
                 if (!(yv * al + be > 0.f)) gv = 0.f;
                 const float tt = (yv - mu) * kk;
                 float d = (((gv - gmn) - tt) * is) * ww;
@@ -1374,7 +1425,23 @@ __device__ __forceinline__ void run(const BlockBwdArgs &a, unsigned char *smem, 
         }
     };
 
-    if (n_iter > 0) {
+    if constexpr (DZ) {
+        // tiles 0 and 1's dz into their slots behind one extra barrier, tile 2's into the prefetch register; in
+        // the loop, iteration it puts tile it+2's dz (slot it & 1, last read by stage(it) in iteration it-1)
+        // and loads tile it+3's
+        if (n_iter > 0) {
+            const float d0 = load_dz(0), d1 = load_dz(1);
+            issue(0);
+            put_dz(0, d0);
+            put_dz(1, d1);
+            DZv = load_dz(2);
+        }
+        bar_lds();                                  // tiles 0 and 1's dz in LDS
+        if (n_iter > 0) {
+            stage(0);
+            issue(1);
+        }
+    } else if (n_iter > 0) {
         issue(0);
         stage(0);
         issue(1);
@@ -1390,10 +1457,18 @@ __device__ __forceinline__ void run(const BlockBwdArgs &a, unsigned char *smem, 
             epilogue(it);
             BB2_STAMP(it, 1);
             stage(it + 1);
+            if constexpr (DZ) {
+                put_dz(it + 2, DZv);
+                DZv = load_dz(it + 3);
+            }
             issue(it + 2);
             BB2_STAMP(it, 2);
         } else {
             stage(it + 1);
+            if constexpr (DZ) {
+                put_dz(it + 2, DZv);
+                DZv = load_dz(it + 3);
+            }
             issue(it + 2);
             BB2_STAMP(it, 1);
             compute(it);
@@ -1751,20 +1826,20 @@ __global__ __launch_bounds__(bb2::kThreads) void conv3x3_fwd_dma_kernel(BlockBwd
     }
 }
 
-template <bool PRO, int EPI>
+template <bool PRO, int EPI, bool DZ = false>
 __global__ __launch_bounds__(bb2::kThreads) void conv3x3_block_bwd2_kernel(BlockBwdArgs a) {
-    __shared__ __attribute__((aligned(16))) unsigned char smem[bb2::kLdsBytes];
+    __shared__ __attribute__((aligned(16))) unsigned char smem[DZ ? bb2::kLdsBytesDz : bb2::kLdsBytes];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     switch (wave) {
-    case 0: bb2::run<PRO, EPI, 0>(a, smem, lane); break;
-    case 1: bb2::run<PRO, EPI, 1>(a, smem, lane); break;
-    case 2: bb2::run<PRO, EPI, 2>(a, smem, lane); break;
-    case 3: bb2::run<PRO, EPI, 3>(a, smem, lane); break;
-    case 4: bb2::run<PRO, EPI, 4>(a, smem, lane); break;
-    case 5: bb2::run<PRO, EPI, 5>(a, smem, lane); break;
-    case 6: bb2::run<PRO, EPI, 6>(a, smem, lane); break;
-    default: bb2::run<PRO, EPI, 7>(a, smem, lane); break;
+    case 0: bb2::run<PRO, EPI, 0, DZ>(a, smem, lane); break;
+    case 1: bb2::run<PRO, EPI, 1, DZ>(a, smem, lane); break;
+    case 2: bb2::run<PRO, EPI, 2, DZ>(a, smem, lane); break;
+    case 3: bb2::run<PRO, EPI, 3, DZ>(a, smem, lane); break;
+    case 4: bb2::run<PRO, EPI, 4, DZ>(a, smem, lane); break;
+    case 5: bb2::run<PRO, EPI, 5, DZ>(a, smem, lane); break;
+    case 6: bb2::run<PRO, EPI, 6, DZ>(a, smem, lane); break;
+    default: bb2::run<PRO, EPI, 7, DZ>(a, smem, lane); break;
     }
 }
 
@@ -2033,6 +2108,38 @@ int hrl_conv3x3_block_backward(const float *g, const float *y, int64_t M, const 
     }
 #undef HRL_BLOCK_LAUNCH
 #undef HRL_BLOCK2_LAUNCH
+    int rc = status();
+    if (rc || !dweight) return rc;   // no dweight: the partials stay for a later fold (hrl_grad_fold_norm)
+    hipLaunchKernelGGL(conv3x3_wgrad_reduce_kernel, dim3(kTaps * kC * kC / 64), dim3(256), 0, s, wpart, grid,
+                       dweight);
+    return status();
+}
+
+// hrl_conv3x3_block_backward for the chain's last block behind the fused heads: dL/d out is not read but rebuilt
+// from the heads' dz (M, 28; hrl_heads_backward_dz) and the 1x1 head conv weights w1p [2][32], w1v [32].  The
+// tile-shared form with epilogue 2 only; bit-identical to hrl_conv3x3_block_backward fed the materialised dh.
+int hrl_conv3x3_block_backward_dz(const float *dz, const float *w1p, const float *w1v, const float *y, int64_t M,
+                                  const float *bn_weight, const float *bn_bias, const float *save_mean,
+                                  const float *save_invstd, const float *kcoef, const float *gmean, const float *x,
+                                  const float *in_alpha, const float *in_beta, const float *packed_flip,
+                                  float *dweight, float *gin, int epilogue, const float *ep_mean,
+                                  const float *ep_alpha, const float *ep_beta, double *part, void *workspace,
+                                  int64_t workspace_bytes, void *stream) {
+    if (M < 1 || !dz || !w1p || !w1v || !y || !save_mean || !save_invstd || !kcoef || !gmean || !x || !workspace)
+        return HRL_EINVAL;
+    if ((in_alpha == nullptr) != (in_beta == nullptr)) return HRL_EINVAL;
+    if (workspace_bytes < hrl_conv3x3_workspace_bytes(M) || M * kRow * 4 > 0xffffffffLL) return HRL_EINVAL;
+    if (g_block_form != 1 || epilogue != 2 || !gin || !packed_flip) return HRL_EINVAL;
+    if (!ep_mean || !ep_alpha || !ep_beta || !part) return HRL_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int grid = grid_for(M);
+    float *wpart = static_cast<float *>(workspace) + kTaps * 2 * kC * 16 * 2;
+    BlockBwdArgs a{dz, y, bn_weight, bn_bias, save_mean, save_invstd, kcoef, gmean, x, in_alpha, in_beta, packed_flip,
+                   ep_mean, ep_alpha, ep_beta, gin, part, wpart, M, w1p, w1v};
+    if (in_alpha)
+        hipLaunchKernelGGL((conv3x3_block_bwd2_kernel<true, 2, true>), dim3(grid), dim3(bb2::kThreads), 0, s, a);
+    else
+        hipLaunchKernelGGL((conv3x3_block_bwd2_kernel<false, 2, true>), dim3(grid), dim3(bb2::kThreads), 0, s, a);
     int rc = status();
     if (rc || !dweight) return rc;   // no dweight: the partials stay for a later fold (hrl_grad_fold_norm)
     hipLaunchKernelGGL(conv3x3_wgrad_reduce_kernel, dim3(kTaps * kC * kC / 64), dim3(256), 0, s, wpart, grid,

@@ -479,7 +479,9 @@ __device__ __forceinline__ void load_group(__amdgpu_buffer_rsrc_t rh, int64_t ro
     for (int k = 0; k < kGV; ++k) st[k] = __builtin_amdgcn_raw_buffer_load_b128(rh, ob + (k * 64 + lane) * 16, 0, 0);
 }
 
-template <bool BN>
+// DZ: the rows' dz (kDZS floats each, the pad 0) leave in dh's place -- dh = W1^T dz is rebuilt by its one consumer
+// (conv3x3_block_bwd2_kernel<PRO, 2, true>); t below is still formed, in the same order, for the BN sums.
+template <bool BN, bool DZ = false>
 __global__ __launch_bounds__(256, 2) void heads_bwd2_kernel(const float *__restrict__ h, int64_t N, Weights w, BnIn bn,
                                                          const float *__restrict__ a_p, const float *__restrict__ a_v,
                                                          const float *__restrict__ dp, const float *__restrict__ dv,
@@ -525,7 +527,7 @@ __global__ __launch_bounds__(256, 2) void heads_bwd2_kernel(const float *__restr
         fo_a[s] = pol ? kSmAP + i % kZP : kSmAV + (i - kOP * kZP < kHW ? i - kOP * kZP : 0);
     }
     const __amdgpu_buffer_rsrc_t rh = heads_rsrc(h, (uint32_t)(N * kRow * 4));
-    const __amdgpu_buffer_rsrc_t rd = heads_rsrc(dh, (uint32_t)(N * kRow * 4));
+    const __amdgpu_buffer_rsrc_t rd = heads_rsrc(dh, (uint32_t)(N * (DZ ? kDZS : kRow) * 4));
     const int64_t nblocks = (N + kBR - 1) / kBR;
     const int64_t wstep = (int64_t)gridDim.x * kWaves2;
     float *sxw = sx[wave];
@@ -594,6 +596,16 @@ __global__ __launch_bounds__(256, 2) void heads_bwd2_kernel(const float *__restr
             }
         }
         lds_fence();
+        if constexpr (DZ) {   // the block's dz: one contiguous run of 32 x 28 floats (rows past N: dropped)
+            const uint32_t ob = (uint32_t)(base * kDZS * 4);
+#pragma unroll
+            for (int k = 0; k < (kBR * kDZS / 4 + 63) / 64; ++k) {
+                const int i = k * 64 + lane;
+                if (i < kBR * kDZS / 4)
+                    __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const hu32x4 *>(dzs + 4 * i), rd,
+                                                           ob + i * 16, 0, 0);
+            }
+        }
         // fc weight gradients over the block's rows, in order
 #pragma unroll 4
         for (int row = 0; row < kBR; ++row) {
@@ -657,17 +669,20 @@ __global__ __launch_bounds__(256, 2) void heads_bwd2_kernel(const float *__restr
                             t2 += gm * (x[q] - mu);
                         }
                     }
-                    xr[q] = t;
+                    if constexpr (!DZ) xr[q] = t;
                 }
                 t1d += (double)t1;
                 t2d += (double)t2;
             }
-            lds_fence();
-            const uint32_t ob = (uint32_t)((base + kGR * g) * kRow * 4);
+            if constexpr (!DZ) {
+                lds_fence();
+                const uint32_t ob = (uint32_t)((base + kGR * g) * kRow * 4);
 #pragma unroll
-            for (int k = 0; k < kGV; ++k)   // rows past N: dropped (the descriptor's range)
-                __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const hu32x4 *>(sxw + 4 * (k * 64 + lane)),
-                                                       rd, ob + (k * 64 + lane) * 16, 0, 0);
+                for (int k = 0; k < kGV; ++k)   // rows past N: dropped (the descriptor's range)
+                    __builtin_amdgcn_raw_buffer_store_b128(
+                        *reinterpret_cast<const hu32x4 *>(sxw + 4 * (k * 64 + lane)), rd, ob + (k * 64 + lane) * 16, 0,
+                        0);
+            }
             lds_fence();   // the tile's reads are done before the next group overwrites it
         }
         lds_fence();   // the block's LDS rows are read before the next block overwrites them
@@ -842,11 +857,17 @@ int hrl_heads_forward(const float *h, int64_t N, const float *w1p, const float *
     return status();
 }
 
-int hrl_heads_backward(const float *h, int64_t N, const float *w1p, const float *w1v, const float *wp,
-                       const float *wv, const float *bn_alpha, const float *bn_beta, const float *bn_mean,
-                       double *bn_part, const float *a_p, const float *a_v, const float *dp, const float *dv,
-                       const float *v_tanh, float *dh, float *dw1p, float *db1p, float *dw1v, float *db1v, float *dwp, float *dwv,
-                       void *workspace, int64_t workspace_bytes, void *stream) {
+}  // extern "C"
+
+namespace {
+
+// hrl_heads_backward (emit_dz false: dh = (N, 288)) and hrl_heads_backward_dz (true: dh = dz, (N, 28), form 2 only)
+int heads_backward(const float *h, int64_t N, const float *w1p, const float *w1v, const float *wp, const float *wv,
+                   const float *bn_alpha, const float *bn_beta, const float *bn_mean, double *bn_part,
+                   const float *a_p, const float *a_v, const float *dp, const float *dv, const float *v_tanh, float *dh,
+                   float *dw1p, float *db1p, float *dw1v, float *db1v, float *dwp, float *dwv, void *workspace,
+                   int64_t workspace_bytes, void *stream, bool emit_dz) {
+    if (emit_dz && g_heads_bwd_form != 2) return HRL_EINVAL;
     if (N < 1 || !h || !w1p || !w1v || !wp || !wv || !a_p || !a_v || !dp || !dv || !dh || !workspace)
         return HRL_EINVAL;
     const bool defer = !dw1p && !db1p && !dw1v && !db1v && !dwp && !dwv;   // partials left for a later fold
@@ -861,12 +882,15 @@ int hrl_heads_backward(const float *h, int64_t N, const float *w1p, const float 
     if (g_heads_bwd_form == 2) {
         if ((N + kBR) * kRow * 4 >= (int64_t)1 << 32) return HRL_EINVAL;   // 32-bit buffer offsets (+ a block)
         const int grid = grid_bwd(N);
-        if (bn_alpha)
-            hipLaunchKernelGGL(heads_bwd2_kernel<true>, dim3(grid), dim3(256), 0, s, h, N, w, bn, a_p, a_v, dp, dv,
-                               v_tanh, dh, part);
-        else
-            hipLaunchKernelGGL(heads_bwd2_kernel<false>, dim3(grid), dim3(256), 0, s, h, N, w, bn, a_p, a_v, dp, dv,
-                               v_tanh, dh, part);
+#define HRL_HEADS_BWD2(BN, DZ)                                                                                       \
+    hipLaunchKernelGGL((heads_bwd2_kernel<BN, DZ>), dim3(grid), dim3(256), 0, s, h, N, w, bn, a_p, a_v, dp, dv, v_tanh, \
+                       dh, part)
+        if (emit_dz) {
+            if (bn_alpha) HRL_HEADS_BWD2(true, true); else HRL_HEADS_BWD2(false, true);
+        } else {
+            if (bn_alpha) HRL_HEADS_BWD2(true, false); else HRL_HEADS_BWD2(false, false);
+        }
+#undef HRL_HEADS_BWD2
         const int rc = status();
         if (rc || defer) return rc;
         hipLaunchKernelGGL(heads_reduce_kernel, dim3(kGN), dim3(256), 0, s, part, grid, dw1p, dw1v, db1p, db1v, dwp,
@@ -886,6 +910,28 @@ int hrl_heads_backward(const float *h, int64_t N, const float *w1p, const float 
     hipLaunchKernelGGL(heads_reduce_kernel, dim3(kGN), dim3(256), 0, s, part, grid, dw1p, dw1v, db1p, db1v, dwp,
                        dwv);
     return status();
+}
+
+}  // namespace
+
+extern "C" {
+
+int hrl_heads_backward(const float *h, int64_t N, const float *w1p, const float *w1v, const float *wp,
+                       const float *wv, const float *bn_alpha, const float *bn_beta, const float *bn_mean,
+                       double *bn_part, const float *a_p, const float *a_v, const float *dp, const float *dv,
+                       const float *v_tanh, float *dh, float *dw1p, float *db1p, float *dw1v, float *db1v, float *dwp, float *dwv,
+                       void *workspace, int64_t workspace_bytes, void *stream) {
+    return heads_backward(h, N, w1p, w1v, wp, wv, bn_alpha, bn_beta, bn_mean, bn_part, a_p, a_v, dp, dv, v_tanh, dh,
+                          dw1p, db1p, dw1v, db1v, dwp, dwv, workspace, workspace_bytes, stream, false);
+}
+
+int hrl_heads_backward_dz(const float *h, int64_t N, const float *w1p, const float *w1v, const float *wp,
+                          const float *wv, const float *bn_alpha, const float *bn_beta, const float *bn_mean,
+                          double *bn_part, const float *a_p, const float *a_v, const float *dp, const float *dv,
+                          const float *v_tanh, float *dz, float *dw1p, float *db1p, float *dw1v, float *db1v,
+                          float *dwp, float *dwv, void *workspace, int64_t workspace_bytes, void *stream) {
+    return heads_backward(h, N, w1p, w1v, wp, wv, bn_alpha, bn_beta, bn_mean, bn_part, a_p, a_v, dp, dv, v_tanh, dz,
+                          dw1p, db1p, dw1v, db1v, dwp, dwv, workspace, workspace_bytes, stream, true);
 }
 
 }  // extern "C"

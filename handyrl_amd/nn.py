@@ -2021,9 +2021,29 @@ def _chain_forward(h0, meta, relu_in, params, apply_out=True):
     return out, ys, coefs, unit, packed
 
 
-def _chain_backward(h0, ys, coefs, unit, params, relu_in, g, need_input_grad, packed, part_in=None, nblk_in=0):
+# The fused heads hand the chain's last block their dz (N, 28) and 1x1 conv weights instead of dh (N, 288): the
+# heads backward stops writing dh and the block backward rebuilds it per element (hrl_heads_backward_dz,
+# hrl_conv3x3_block_backward_dz; bit-identical).  False: the materialised-dh path (the tests' reference).
+HEADS_DZ = True
+
+
+def _heads_dz_ok(lib, n):
+    """The dz path's preconditions: the last block is a PRO / epilogue-2 launch (n >= 2), the heads' lane-per-channel
+    form and the block backward's tile-shared form."""
+    return HEADS_DZ and n >= 2 and lib.hrl_heads_set_bwd_form(0) == 2 and _block_form(lib) == 1
+
+
+def _block_form(lib):
+    form = lib.hrl_conv3x3_set_block_form(1)   # no query call: set, read the previous, put it back
+    lib.hrl_conv3x3_set_block_form(form)
+    return form
+
+
+def _chain_backward(h0, ys, coefs, unit, params, relu_in, g, need_input_grad, packed, part_in=None, nblk_in=0,
+                    heads_dz=None):
     """Backward of the chain from g = dL/d(chain output); with part_in the last BN's backward sums were already
-    formed by the consumer (fused heads).  Returns (dL/dh0 | None, parameter gradients)."""
+    formed by the consumer (fused heads).  heads_dz = (w1p, w1v): g is the heads' dz (N, 28) and the last block
+    rebuilds dL/d(chain output) from it (_heads_dz_ok).  Returns (dL/dh0 | None, parameter gradients)."""
     lib = _native.load()
     n = len(ys)
     M = h0.shape[0]
@@ -2041,6 +2061,7 @@ def _chain_backward(h0, ys, coefs, unit, params, relu_in, g, need_input_grad, pa
     # itself reads only kg
     part = torch.empty(nblk * 32 * 2, dtype=torch.float64, device=dev)
     g = g.contiguous()
+    assert heads_dz is None or (part_in is not None and n >= 2)
     grads = [None] * (3 * n)
     sums, sums_n = (part_in, nblk_in) if part_in is not None else (None, 0)   # BN_i's backward sums, if formed
     for i in reversed(range(n)):
@@ -2069,10 +2090,17 @@ def _chain_backward(h0, ys, coefs, unit, params, relu_in, g, need_input_grad, pa
             df = _defer_folds([bw])
             wsb = ws if df is None else torch.empty(ws_bytes, dtype=torch.uint8, device=dev)   # partials live on
             ev = _block_timing_start()
-            _native.check(lib.hrl_conv3x3_block_backward(
-                P(g), P(ys[i]), M, P(gamma), P(beta), P(mean), P(invstd), P(kg[0]), P(kg[1]), P(x), P(a), P(b),
-                P(packed[i, 1]), None if df is not None else P(dw), P(gin), epi, P(ep[0]), P(ep[1]), P(ep[2]),
-                P(part) if i > 0 else None, P(wsb), ws_bytes, stream), 'hrl_conv3x3_block_backward')
+            if heads_dz is not None and i == n - 1:
+                _native.check(lib.hrl_conv3x3_block_backward_dz(
+                    P(g), P(heads_dz[0]), P(heads_dz[1]), P(ys[i]), M, P(gamma), P(beta), P(mean), P(invstd),
+                    P(kg[0]), P(kg[1]), P(x), P(a), P(b), P(packed[i, 1]), None if df is not None else P(dw), P(gin),
+                    epi, P(ep[0]), P(ep[1]), P(ep[2]), P(part), P(wsb), ws_bytes, stream),
+                    'hrl_conv3x3_block_backward_dz')
+            else:
+                _native.check(lib.hrl_conv3x3_block_backward(
+                    P(g), P(ys[i]), M, P(gamma), P(beta), P(mean), P(invstd), P(kg[0]), P(kg[1]), P(x), P(a), P(b),
+                    P(packed[i, 1]), None if df is not None else P(dw), P(gin), epi, P(ep[0]), P(ep[1]), P(ep[2]),
+                    P(part) if i > 0 else None, P(wsb), ws_bytes, stream), 'hrl_conv3x3_block_backward')
             _block_timing_end(ev)
             if df is not None:   # [block][tap][ci][co] partial rows -> dW (co, ci, kh, kw): fold mode 1
                 off = ctypes.c_int64(0)
@@ -2188,17 +2216,20 @@ class _ChainHeadsFn(torch.autograd.Function):
         P = _native.ptr
         y, coef = ys[-1], coefs[-1]
         dp, dv = dp.contiguous(), dv.contiguous()
-        dh = torch.empty_like(h0)
+        use_dz = _heads_dz_ok(lib, n)
+        # dz (N, 28) in dh's place: the last block backward rebuilds dh from it
+        dh = torch.empty(N, 28, device=dev, dtype=h0.dtype) if use_dz else torch.empty_like(h0)
+        heads_backward = lib.hrl_heads_backward_dz if use_dz else lib.hrl_heads_backward
         hbufs = [_grad_buffer(x) for x in (w1p, b1p, w1v, b1v, wp, wv)]
         ws_bytes = lib.hrl_heads_workspace_bytes(N)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         nparts = lib.hrl_heads_bn_parts(N)
         bn_part = torch.empty(nparts * 64, dtype=torch.float64, device=dev)
         def call(*dws):
-            _native.check(lib.hrl_heads_backward(P(y), N, P(w1p), P(w1v), P(wp), P(wv), P(coef[2]), P(coef[3]),
-                                                 P(coef[0]), P(bn_part), P(a_p), P(a_v), P(dp), P(dv),
-                                                 P(v) if ctx.tanh_v else None, P(dh), *(P(t) for t in dws),
-                                                 P(ws), ws_bytes, _native.stream_of(dev)), 'hrl_heads_backward(bn)')
+            _native.check(heads_backward(P(y), N, P(w1p), P(w1v), P(wp), P(wv), P(coef[2]), P(coef[3]),
+                                         P(coef[0]), P(bn_part), P(a_p), P(a_v), P(dp), P(dv),
+                                         P(v) if ctx.tanh_v else None, P(dh), *(P(t) for t in dws),
+                                         P(ws), ws_bytes, _native.stream_of(dev)), 'hrl_heads_backward(bn)')
         df = _defer_folds(hbufs, 6) if lib.hrl_heads_set_bwd_form(0) == 2 else None
         if df is not None:
             _heads_backward_deferred(lib, df, hbufs, N, ws, call)
@@ -2206,7 +2237,7 @@ class _ChainHeadsFn(torch.autograd.Function):
             call(*(b[0] for b in hbufs))
         unit = _unit_coefs(dev) if ctx.relu_in else None
         g_in, grads = _chain_backward(h0, ys, coefs, unit, params, ctx.relu_in, dh, ctx.needs_input_grad[0], packed,
-                                      part_in=bn_part, nblk_in=nparts)
+                                      part_in=bn_part, nblk_in=nparts, heads_dz=(w1p, w1v) if use_dz else None)
         return (g_in, None, None, None, *(_ret(b) for b in hbufs), *grads)
 
 

@@ -222,6 +222,19 @@ int hrl_conv3x3_block_backward(const float *g, const float *y, int64_t M, const 
                                const float *in_beta, const float *packed_flip, float *dweight, float *gin,
                                int epilogue, const float *ep_mean, const float *ep_alpha, const float *ep_beta,
                                double *part, void *workspace, int64_t workspace_bytes, void *stream);
+/* hrl_conv3x3_block_backward for the chain's last block behind the fused heads (ABI 28): g is not read but rebuilt
+ * per element as ((0 + w1[0]*dz[0*9+q]) + w1[1]*dz[1*9+q]) + w1[2]*dz[2*9+q] (hrl_heads_backward's float operations)
+ * from dz (M, 28) = hrl_heads_backward_dz's output and the 1x1 head conv weights w1p [2][32], w1v [32]; every other
+ * argument as above.  The tile-shared form (hrl_conv3x3_set_block_form 1) with gin and epilogue 2 only: anything else
+ * is HRL_EINVAL before any launch.  gin, dweight / the partial rows and part are bit-identical to
+ * hrl_conv3x3_block_backward fed the materialised dh. */
+int hrl_conv3x3_block_backward_dz(const float *dz, const float *w1p, const float *w1v, const float *y, int64_t M,
+                                  const float *bn_weight, const float *bn_bias, const float *save_mean,
+                                  const float *save_invstd, const float *kcoef, const float *gmean, const float *x,
+                                  const float *in_alpha, const float *in_beta, const float *packed_flip,
+                                  float *dweight, float *gin, int epilogue, const float *ep_mean,
+                                  const float *ep_alpha, const float *ep_beta, double *part, void *workspace,
+                                  int64_t workspace_bytes, void *stream);
 
 /*
  * Fused ConvLSTM cell gates (GeisterNet DRC, handyrl/envs/geister.py:48-63;
@@ -506,6 +519,15 @@ int hrl_heads_backward(const float *h, int64_t N, const float *w1p, const float 
                        double *bn_part, const float *a_p, const float *a_v, const float *dp, const float *dv,
                        const float *v_tanh, float *dh, float *dw1p, float *db1p, float *dw1v, float *db1v, float *dwp, float *dwv,
                        void *workspace, int64_t workspace_bytes, void *stream);
+/* hrl_heads_backward without the input gradient (ABI 28): in dh's place it writes dz (N, 28; 16-byte aligned), per row
+ * the 27 gradients of the 1x1 head convs' outputs [m][q] (m = 0, 1 policy, 2 value) and a 0 pad, from which
+ * dh[c][q] = sum_m W1[m][c] dz[m][q] is rebuilt by hrl_conv3x3_block_backward_dz.  Form 2 only (HRL_EINVAL under
+ * form 1); the parameter gradients / partial rows and bn_part are bit-identical to hrl_heads_backward's. */
+int hrl_heads_backward_dz(const float *h, int64_t N, const float *w1p, const float *w1v, const float *wp,
+                          const float *wv, const float *bn_alpha, const float *bn_beta, const float *bn_mean,
+                          double *bn_part, const float *a_p, const float *a_v, const float *dp, const float *dv,
+                          const float *v_tanh, float *dz, float *dw1p, float *db1p, float *dw1v, float *db1v,
+                          float *dwp, float *dwv, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* The 3x3-board stem conv, Cin <= 3 -> 32 channels, with bias (TicTacToe, tictactoe.py:57), as fp32
  * MFMA on the dense board matrix (csrc/hrl_stem.hip): x (N, Cin, 3, 3), y (N, 32, 3, 3),

@@ -1,7 +1,8 @@
 """Time one chain block's backward: the fused hrl_conv3x3_block_backward (the default tile-shared form 1 and the
 per-wave form 0) vs the three launches it replaces.
 
-    python tools/block_bench.py [--M 131072] [--iters 20]
+    python tools/block_bench.py [--M 131072] [--iters 20] [--dz]
+--dz also times hrl_conv3x3_block_backward_dz (epilogue 2, the tile-shared form: dL/d out rebuilt from the heads' dz).
 HRL_LIB_PATH selects another build of libhrl.so (diagnostic variants).  HIP events on the launch stream.
 """
 import argparse
@@ -22,6 +23,7 @@ def main():
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--epi', type=int, default=2, help='epilogue of the fused launch: 0, 2 (BN sums) or 3 (mask)')
     ap.add_argument('--forms', default='', help='only these block forms (comma list), e.g. 1,0')
+    ap.add_argument('--dz', action='store_true', help='also time hrl_conv3x3_block_backward_dz (needs --epi 2)')
     opts = ap.parse_args()
     dev = torch.device('cuda', 0)
     lib = _native.load()
@@ -46,6 +48,13 @@ def main():
             opts.epi, P(c[8]), P(c[9]), P(c[10]), P(part) if opts.epi == 2 else None, P(ws), ws_bytes, stream),
             'block')
 
+    dz, w1p, w1v = rnd(M, 28), rnd(2, 32), rnd(1, 32)
+
+    def fused_dz():
+        _native.check(lib.hrl_conv3x3_block_backward_dz(
+            P(dz), P(w1p), P(w1v), P(y), M, *[P(t) for t in c[:6]], P(x), P(c[6]), P(c[7]), P(packed[0, 1]), P(dw),
+            P(gin), 2, P(c[8]), P(c[9]), P(c[10]), P(part), P(ws), ws_bytes, stream), 'block_dz')
+
     def three():
         _native.check(lib.hrl_bn_backward_apply(P(y), P(g), M, 32, 9, P(c[0]), P(c[1]), P(c[2]), P(c[3]), 1,
                                                 P(c[4]), P(c[5]), P(dy), stream), 'apply')
@@ -68,6 +77,8 @@ def main():
              ('three_launches_us', three, None)]
     if only is None:
         cases = [('fused_us', fused, None)] + cases
+    if opts.dz and opts.epi == 2:
+        cases.append(('fused_dz_us', fused_dz, 1))
     for name, fn, f in cases:
         if only is not None and f not in only:
             continue
