@@ -63,6 +63,17 @@ SIGNATURES = {
         _f32p, ctypes.c_void_p, _i64, _i64, _i64, _i64, _i64,
         _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _dbl, _dbl,
         ctypes.c_void_p, _i64, _f32p, _f32p, _f32p, _f32p, ctypes.c_void_p]),
+    'hrl_loss_partials': (ctypes.c_int64, [_i64, _i64, _i64, _i64, ctypes.c_void_p]),
+    'hrl_loss_forward_ex': (ctypes.c_int, [
+        _f32p, _f32p, ctypes.c_void_p, _i64, _i64, _i64, _i64, _i64,
+        _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p,
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, _dbl, _dbl, _dbl, _dbl,
+        ctypes.c_void_p, _i64, _f32p, _f32p, _f32p, _f32p, _i64, ctypes.c_int, ctypes.c_void_p]),
+    'hrl_loss_backward_ex': (ctypes.c_int, [
+        _f32p, ctypes.c_void_p, _i64, _i64, _i64, _i64, _i64,
+        _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _dbl, _dbl,
+        ctypes.c_void_p, _i64, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _i64, _f32p, _f32p,
+        ctypes.c_void_p]),
     'hrl_output_mask_forward': (ctypes.c_int, [_f32p, _f32p, _f32p, _f32p, _f32p, _i64, _i64, _i64, _i64, _f32p,
                                                _f32p, ctypes.c_void_p]),
     'hrl_output_mask_backward': (ctypes.c_int, [_f32p, _f32p, _f32p, _f32p, _i64, _i64, _i64, _i64, _f32p, _f32p,
@@ -92,6 +103,7 @@ SIGNATURES = {
     'hrl_torus_set_split': (ctypes.c_int, [ctypes.c_int]),
     'hrl_torus_set_form': (ctypes.c_int, [ctypes.c_int]),
     'hrl_conv3x3_pack_n': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _f32p, ctypes.c_void_p]),
+    'hrl_conv3x3_pack_n_zero': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _f32p, _f32p, _i64, ctypes.c_void_p]),
     'hrl_conv3x3_forward_ex': (ctypes.c_int, [_f32p, _i64, _f32p, _f32p, _f32p, _f32p, ctypes.c_int, _f32p,
                                               ctypes.c_int, _f32p, _f32p, _f32p, _f32p, ctypes.c_void_p,
                                               ctypes.c_void_p, _i64, ctypes.c_void_p]),
@@ -152,6 +164,11 @@ SIGNATURES = {
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                           ctypes.c_int, _f32p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                           ctypes.c_void_p, _i64, ctypes.c_void_p]),
+    'hrl_grad_fold_norm_ex': (ctypes.c_int, [_f32p, _i64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_int, _f32p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                             ctypes.c_void_p, _i64, ctypes.c_void_p, _i64, _dbl, _f32p,
+                                             ctypes.c_void_p]),
     'hrl_adam_clip': (ctypes.c_int, [_f32p, _i64, ctypes.c_void_p, _dbl, _f32p, ctypes.c_void_p, ctypes.c_void_p,
                                      ctypes.c_void_p, ctypes.c_int, _f32p, _f32p, _f32p, _f32p, _dbl, _dbl, _dbl,
                                      _dbl, ctypes.c_void_p, ctypes.c_int, _f32p, ctypes.c_void_p]),
@@ -241,7 +258,7 @@ SIGNATURES = {
                                                       ctypes.c_void_p]),
 }
 
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 _lib = None
 

@@ -1889,14 +1889,38 @@ constexpr int kPack = kTaps * 2 * kC * 16;
 struct WeightList {
     const float *w[8];
 };
-__global__ void conv3x3_pack_n_kernel(WeightList wl, int n, float *__restrict__ packed) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void pack_n_element(const WeightList &wl, int n, float *__restrict__ packed, int i) {
     if (i >= n * 2 * kPack) return;
     const int l = i / (2 * kPack), flip = (i / kPack) & 1, e = i % kPack;
     const int j = e % 16, k = (e / 16) % kC, ct = (e / (16 * kC)) % 2, tap = e / (16 * kC * 2);
     const int out_c = ct * 16 + j, in_c = k;
     const float *w = wl.w[l];
     packed[i] = !flip ? w[(out_c * kC + in_c) * kTaps + tap] : w[(in_c * kC + out_c) * kTaps + (kTaps - 1 - tap)];
+}
+__global__ void conv3x3_pack_n_kernel(WeightList wl, int n, float *__restrict__ packed) {
+    pack_n_element(wl, n, packed, blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+// hrl_conv3x3_pack_n_zero: the same packing in the first pack_blocks workgroups; the workgroups behind them zero
+// zero[0 .. nz) (the learner's flat gradient buffer, which is 4-byte aligned only): `head` single floats up to the
+// first 16-byte boundary, nvec float4 stores (one per thread) and the last `tail` single floats, the two ragged
+// ends by the first zeroing workgroup
+__global__ __launch_bounds__(256) void conv3x3_pack_n_zero_kernel(WeightList wl, int n, float *__restrict__ packed,
+                                                                  int pack_blocks, float *__restrict__ zero,
+                                                                  int64_t nz, int head, int64_t nvec) {
+    if ((int)blockIdx.x < pack_blocks) {
+        pack_n_element(wl, n, packed, blockIdx.x * blockDim.x + threadIdx.x);
+        return;
+    }
+    const int64_t zb = (int64_t)blockIdx.x - pack_blocks;
+    const int64_t v = zb * 256 + threadIdx.x;
+    if (v < nvec) reinterpret_cast<float4 *>(zero + head)[v] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (zb == 0) {
+        const int t = threadIdx.x;
+        const int64_t tail0 = head + nvec * 4;
+        if (t < head) zero[t] = 0.f;
+        if (tail0 + t < nz && t < 4) zero[tail0 + t] = 0.f;
+    }
 }
 
 // Forward / input-gradient arithmetic: exact-split bf16 MFMA (1, default) or fp32 MFMA (0).
@@ -2027,6 +2051,30 @@ int hrl_conv3x3_pack_n(const float *const *weights, int n, float *packed, void *
     }
     hipLaunchKernelGGL(conv3x3_pack_n_kernel, dim3((n * 2 * kPack + 255) / 256), dim3(256), 0,
                        static_cast<hipStream_t>(stream), wl, n, packed);
+    return status();
+}
+
+int hrl_conv3x3_pack_n_zero(const float *const *weights, int n, float *packed, float *zero, int64_t zero_floats,
+                            void *stream) {
+    if (n < 1 || n > 8 || !weights || !packed || zero_floats < 0 || zero_floats > ((int64_t)1 << 36)) return HRL_EINVAL;
+    if (zero_floats > 0 && (!zero || (reinterpret_cast<uintptr_t>(zero) & 3) != 0)) return HRL_EINVAL;
+    WeightList wl{};
+    for (int i = 0; i < n; ++i) {
+        if (!weights[i]) return HRL_EINVAL;
+        wl.w[i] = weights[i];
+    }
+    const int pack_blocks = (n * 2 * kPack + 255) / 256;
+    int64_t head = 0, nvec = 0;
+    if (zero_floats > 0) {
+        head = (int64_t)((16 - (reinterpret_cast<uintptr_t>(zero) & 15)) & 15) / 4;   // floats to the boundary
+        if (head > zero_floats) head = zero_floats;
+        nvec = (zero_floats - head) / 4;
+    }
+    // at least one zeroing workgroup (the ragged ends are its work) whenever there is anything to zero
+    const int64_t zero_blocks = zero_floats > 0 ? (nvec > 256 ? (nvec + 255) / 256 : 1) : 0;
+    hipLaunchKernelGGL(conv3x3_pack_n_zero_kernel, dim3((unsigned)(pack_blocks + zero_blocks)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), wl, n, packed, pack_blocks, zero, zero_floats, (int)head,
+                       nvec);
     return status();
 }
 

@@ -94,7 +94,62 @@ struct FwdArgs {
     const float *emask, *tmask, *omask, *progress, *value, *outcome, *ret_out, *ret, *reward;
     int value_mc, symmetrize;
     float ent_coef, ent_decay;
+    // the raw head outputs (hrl_loss_forward_ex): opol != NULL -> tpol / value are formed from them per element
+    const float *opol, *oval, *amask;
+    int Pq;
 };
+
+// forward_prediction's masking of the raw head outputs (train.py:176-183), per element exactly as
+// out_mask_fwd_kernel forms it: products rounded, summed from 0 in p order, then the action mask subtracted.
+// o = opol + bt*Pq*A, tm = tmask + bt*P, am = amask + bt*A; o == NULL: no raw outputs (the masked tensors are read)
+struct RawRow {
+    const float *o, *tm, *am;
+    int P, Pq;
+};
+__device__ __forceinline__ float raw_logit(const RawRow &r, int A, int q) {
+    float acc = 0.f;
+    for (int p = 0; p < r.P; ++p) acc += r.o[(r.Pq == 1 ? 0 : p) * A + q] * r.tm[p];
+    return acc - r.am[q];
+}
+// A whole row of AK logits at once, p outermost: per element the same products and the same sum order as
+// raw_logit, but each player's AK loads (for one raw row: its AK loads, once) issue together instead of one
+// dependent memory round trip per (q, p)
+template <int AK>
+__device__ __forceinline__ void raw_logits(const RawRow &r, float (&x)[AK]) {
+    float am[AK], acc[AK];
+#pragma unroll
+    for (int q = 0; q < AK; ++q) {
+        am[q] = r.am[q];
+        acc[q] = 0.f;
+    }
+    if (r.Pq == 1) {
+        float o[AK];
+#pragma unroll
+        for (int q = 0; q < AK; ++q) o[q] = r.o[q];
+        for (int p = 0; p < r.P; ++p) {
+            const float t = r.tm[p];
+#pragma unroll
+            for (int q = 0; q < AK; ++q) acc[q] += o[q] * t;
+        }
+    } else {
+        for (int p = 0; p < r.P; ++p) {
+            const float t = r.tm[p];
+#pragma unroll
+            for (int q = 0; q < AK; ++q) acc[q] += r.o[p * AK + q] * t;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < AK; ++q) x[q] = acc[q] - am[q];
+}
+__device__ __forceinline__ RawRow raw_row(const float *opol, const float *tmask, const float *amask, int64_t bt, int P,
+                                          int Pq, int A) {
+    if (!opol) return RawRow{nullptr, nullptr, nullptr, P, Pq};
+    return RawRow{opol + bt * Pq * A, tmask + bt * P, amask + bt * A, P, Pq};
+}
+// value[bt, p] = oval[bt, p|0] * omask[bt, p] (out_mask_fwd_kernel's value branch)
+__device__ __forceinline__ float raw_value(const float *oval, const float *omask, int64_t bt, int P, int Pq, int p) {
+    return oval[bt * Pq + (Pq == 1 ? 0 : p)] * omask[bt * P + p];
+}
 
 // log-softmax pieces of one row of A logits: max m and s = sum exp(z - m)
 __device__ __forceinline__ void row_stats(const float *z, int A, float &m, float &s) {
@@ -110,15 +165,21 @@ __device__ __forceinline__ void row_stats(const float *z, int A, float &m, float
 // AK = 0: any A, one action per loop trip.  Same float operations in the same order either way.
 template <int AK>
 __device__ __forceinline__ void policy_row(const float *zt, const float *zb, int A, int act, float em, float &lt,
-                                           float &crho, float &ent) {
+                                           float &crho, float &ent, const RawRow &raw) {
     float mt, st, mb, sb;
     float h = 0.f;
     if constexpr (AK > 0) {
         float xt[AK], xb[AK], et[AK];
+        if (raw.o) {   // wave-uniform: the target logits from the raw head outputs
 #pragma unroll
-        for (int q = 0; q < AK; ++q) {
-            xt[q] = zt[q];
-            xb[q] = zb[q];
+            for (int q = 0; q < AK; ++q) xb[q] = zb[q];
+            raw_logits<AK>(raw, xt);
+        } else {
+#pragma unroll
+            for (int q = 0; q < AK; ++q) {
+                xt[q] = zt[q];
+                xb[q] = zb[q];
+            }
         }
         mt = xt[0];
         mb = xb[0];
@@ -144,7 +205,7 @@ __device__ __forceinline__ void policy_row(const float *zt, const float *zb, int
 #pragma unroll
         for (int q = 0; q < AK; ++q) h += (xt[q] - lse) * (et[q] / st);
         crho = fminf(fmaxf(expf(lt - lb), 0.f), 1.f);                        // train.py:228-231
-    } else {
+    } else {   // not reached from the fused kernel (AK = 0 runs policy_row_wave); masked logits only
         row_stats(zt, A, mt, st);
         row_stats(zb, A, mb, sb);
         // F.log_softmax(x)[act] = (x - max) - log(sum exp(x - max))      (train.py:224-225)
@@ -177,26 +238,31 @@ __device__ __forceinline__ float wave_sum(float v) {
 // fixed-order butterfly reductions instead of one lane walking the row.  The same quantities as
 // policy_row; the sums run in another (fixed) order.
 __device__ __forceinline__ void policy_row_wave(const float *zt, const float *zb, int A, int act, float em, int lane,
-                                                float &lt, float &crho, float &ent) {
+                                                float &lt, float &crho, float &ent, const RawRow &raw) {
+    // a target logit: read, or (wave-uniform) formed from the raw head outputs each time it is used
+    auto Zt = [&](int q) __attribute__((always_inline)) { return raw.o ? raw_logit(raw, A, q) : zt[q]; };
     float mt = -INFINITY, mb = -INFINITY;
     for (int q = lane; q < A; q += 64) {
-        mt = fmaxf(mt, zt[q]);
+        mt = fmaxf(mt, Zt(q));
         mb = fmaxf(mb, zb[q]);
     }
     mt = wave_max(mt);
     mb = wave_max(mb);
     float st = 0.f, sb = 0.f;
     for (int q = lane; q < A; q += 64) {
-        st += expf(zt[q] - mt);
+        st += expf(Zt(q) - mt);
         sb += expf(zb[q] - mb);
     }
     st = wave_sum(st);
     sb = wave_sum(sb);
-    lt = ((zt[act] - mt) - logf(st)) * em;                                  // train.py:224-225
+    lt = ((Zt(act) - mt) - logf(st)) * em;                                  // train.py:224-225
     const float lb = ((zb[act] - mb) - logf(sb)) * em;
     const float lse = mt + logf(st);
     float h = 0.f;
-    for (int q = lane; q < A; q += 64) h += (zt[q] - lse) * (expf(zt[q] - mt) / st);
+    for (int q = lane; q < A; q += 64) {
+        const float z = Zt(q);
+        h += (z - lse) * (expf(z - mt) / st);
+    }
     ent = -wave_sum(h);
     crho = fminf(fmaxf(expf(lt - lb), 0.f), 1.f);                            // train.py:228-231
 }
@@ -307,7 +373,7 @@ __global__ __launch_bounds__(hrl_scan::kWave) void loss_fused_kernel(FusedArgs f
                 const int64_t row = bt * Pp + pp;
                 float lt, crho, ent;
                 policy_row_wave(a.tpol + row * A, a.bpol + row * A, A, (int)a.action[row], a.emask[bt], lane, lt,
-                                crho, ent);
+                                crho, ent, raw_row(a.opol, a.tmask, a.amask, bt, P, a.Pq, A));
                 if (lane == 0) {
                     const int slot = gg * Lpr + tt * rhoC + pp;
                     t_rho[slot] = crho;
@@ -328,7 +394,8 @@ __global__ __launch_bounds__(hrl_scan::kWave) void loss_fused_kernel(FusedArgs f
                 const float em = a.emask[bt];
                 const int64_t act = a.action[row];
                 float lt, crho, ent;
-                policy_row<AK>(a.tpol + row * A, a.bpol + row * A, A, (int)act, em, lt, crho, ent);
+                policy_row<AK>(a.tpol + row * A, a.bpol + row * A, A, (int)act, em, lt, crho, ent,
+                               raw_row(a.opol, a.tmask, a.amask, bt, P, a.Pq, A));
                 const int slot = gg * Lpr + tt * rhoC + pp;
                 t_rho[slot] = crho;
                 t_lt[slot] = lt;
@@ -351,11 +418,14 @@ __global__ __launch_bounds__(hrl_scan::kWave) void loss_fused_kernel(FusedArgs f
                 const int slot = gg * Lpv + tt * C + q;
                 if constexpr (HV) {
                     const float em = a.emask[bt];
-                    const float *v = a.value + bt * P;
-                    float vp = v[q];
+                    // the masked value: read, or (wave-uniform) oval * omask as out_mask_fwd_kernel forms it
+                    auto V = [&](int p) __attribute__((always_inline)) {
+                        return a.oval ? raw_value(a.oval, a.omask, bt, P, a.Pq, p) : a.value[bt * P + p];
+                    };
+                    float vp = V(q);
                     if (a.symmetrize) {   // two-player zero-sum: (v - swap(v)) / (sum omask + 1e-8)
                         const float *om = a.omask + bt * P;
-                        vp = (v[q] + (-v[1 - q])) / ((om[0] + om[1]) + 1e-8f);
+                        vp = (vp + (-V(1 - q))) / ((om[0] + om[1]) + 1e-8f);
                     }
                     t_v[slot] = vp * em + a.outcome[b * P + q] * (1.f - em);
                 }
@@ -428,7 +498,8 @@ __global__ __launch_bounds__(hrl_scan::kWave) void loss_fused_kernel(FusedArgs f
                     const int64_t i = bt * P + q;
                     if constexpr (HV) {
                         const float tv = TGT == kNone ? a.outcome[b * P + q] : t_tv[vrow + q];
-                        const float e2 = a.value[i] - tv;
+                        const float vi = a.oval ? raw_value(a.oval, a.omask, bt, P, a.Pq, q) : a.value[i];
+                        const float e2 = vi - tv;
                         acc[1] += (double)((e2 * e2) * om[q]);
                         w.tv[i] = tv;
                     }
@@ -542,12 +613,74 @@ struct BwdArgs {
     const float *dl;   // upstream gradients of p, v, r, ent, total
     float *g_tpol, *g_value, *g_ret;
     float ent_coef, ent_decay;
+    // the raw head outputs (hrl_loss_backward_ex; Pp == 1): the logits and the value are rebuilt from them as in
+    // the forward, and the gradients go to gopol (BT, Pq, A) / goval (BT, Pq) with out_mask_bwd_kernel's operations
+    const float *opol, *oval, *amask;
+    int Pq;
+    float *gopol, *goval;
 };
+
+// out_mask_bwd_kernel's policy branch for the gradient g of logit (bt, q): one raw row sums g * tmask over the
+// players from 0 in p order, per-player rows take the single product
+__device__ __forceinline__ void store_gopol(const BwdArgs &a, int64_t bt, int P, int A, int q, float g,
+                                            const float *tm) {
+    if (a.Pq == 1) {
+        float acc = 0.f;
+        for (int p = 0; p < P; ++p) acc += g * tm[p];
+        a.gopol[bt * A + q] = acc;
+    } else {
+        for (int p = 0; p < P; ++p) a.gopol[(bt * P + p) * A + q] = g * tm[p];
+    }
+}
+
+// store_gopol for a whole row of AK gradients, p outermost (the same products and sum order per element)
+template <int AK>
+__device__ __forceinline__ void store_gopol_row(const BwdArgs &a, int64_t bt, int P, const float (&g)[AK],
+                                                const float *tm) {
+    if (a.Pq == 1) {
+        float acc[AK];
+#pragma unroll
+        for (int q = 0; q < AK; ++q) acc[q] = 0.f;
+        for (int p = 0; p < P; ++p) {
+            const float t = tm[p];
+#pragma unroll
+            for (int q = 0; q < AK; ++q) acc[q] += g[q] * t;
+        }
+#pragma unroll
+        for (int q = 0; q < AK; ++q) a.gopol[bt * AK + q] = acc[q];
+    } else {
+        for (int p = 0; p < P; ++p) {
+            const float t = tm[p];
+#pragma unroll
+            for (int q = 0; q < AK; ++q) a.gopol[(bt * P + p) * AK + q] = g[q] * t;
+        }
+    }
+}
+
+// the value gradient of (bt, .) through the masking: g_value[p] as loss_backward_kernel forms it, then
+// out_mask_bwd_kernel's value branch
+__device__ __forceinline__ void store_goval(const BwdArgs &a, const Ws &w, int64_t bt, int P, float dvt,
+                                            const float *om) {
+    if (a.Pq == 1) {
+        float acc = 0.f;
+        for (int p = 0; p < P; ++p) {
+            const float gv = dvt * (raw_value(a.oval, a.omask, bt, P, 1, p) - w.tv[bt * P + p]) * om[p];
+            acc += gv * om[p];
+        }
+        a.goval[bt] = acc;
+    } else {
+        for (int p = 0; p < P; ++p) {
+            const float gv = dvt * (raw_value(a.oval, a.omask, bt, P, P, p) - w.tv[bt * P + p]) * om[p];
+            a.goval[bt * P + p] = gv * om[p];
+        }
+    }
+}
 
 template <int AK>
 __global__ __launch_bounds__(kThreads) void loss_backward_kernel(BwdArgs a, LossDims d, Ws w) {
     const int64_t bt = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (bt >= d.BT) return;
+    const RawRow raw = raw_row(a.opol, a.tmask, a.amask, bt, d.P, a.Pq, d.A);
     const float dp = a.dl[0], dv = a.dl[1], dr = a.dl[2], de = a.dl[3], dt = a.dl[4];
     const float *tm = a.tmask + bt * d.P;
     const float *om = a.omask + bt * d.P;
@@ -556,8 +689,8 @@ __global__ __launch_bounds__(kThreads) void loss_backward_kernel(BwdArgs a, Loss
     const float cp = -(dp + dt) * w.turn[bt] * em;           // d(-lt*turn)/d(lt) * d(lt)/d(log_softmax)
     for (int pp = 0; pp < d.Pp; ++pp) {
         const int64_t row = bt * d.Pp + pp;
-        const float *z = a.tpol + row * d.A;
-        float *g = a.g_tpol + row * d.A;
+        const float *z = raw.o ? nullptr : a.tpol + row * d.A;
+        float *g = raw.o ? nullptr : a.g_tpol + row * d.A;
         // entropy weights of this policy row: players p that read it (all when Pp == 1)
         float wsum = 0.f, wdec = 0.f;
         for (int p = 0; p < d.P; ++p) {
@@ -571,8 +704,12 @@ __global__ __launch_bounds__(kThreads) void loss_backward_kernel(BwdArgs a, Loss
         const int64_t act = a.action[row];
         if constexpr (AK > 0) {   // the row in registers: its loads issue at once (same float operations)
             float x[AK];
+            if (raw.o) {   // block-uniform
+                raw_logits<AK>(raw, x);
+            } else {
 #pragma unroll
-            for (int q = 0; q < AK; ++q) x[q] = z[q];
+                for (int q = 0; q < AK; ++q) x[q] = z[q];
+            }
             float m = x[0];
 #pragma unroll
             for (int q = 1; q < AK; ++q) m = fmaxf(m, x[q]);
@@ -580,14 +717,21 @@ __global__ __launch_bounds__(kThreads) void loss_backward_kernel(BwdArgs a, Loss
 #pragma unroll
             for (int q = 0; q < AK; ++q) s += expf(x[q] - m);
             const float lse = m + logf(s);
+            float gx[AK];
 #pragma unroll
             for (int q = 0; q < AK; ++q) {
                 const float pq = expf(x[q] - m) / s;
                 const float la = x[q] - lse;
                 const float onehot = (q == act) ? 1.f : 0.f;
-                g[q] = cp * (onehot - pq) + ce * (-pq * (la + h));    // dH/dz = -p (log p + H)
+                gx[q] = cp * (onehot - pq) + ce * (-pq * (la + h));    // dH/dz = -p (log p + H)
             }
-        } else {
+            if (raw.o) {
+                store_gopol_row<AK>(a, bt, d.P, gx, tm);
+            } else {
+#pragma unroll
+                for (int q = 0; q < AK; ++q) g[q] = gx[q];
+            }
+        } else {   // not launched with raw outputs (any other A runs loss_backward_wave_kernel)
             float m, s;
             row_stats(z, d.A, m, s);
             const float lse = m + logf(s);
@@ -599,6 +743,7 @@ __global__ __launch_bounds__(kThreads) void loss_backward_kernel(BwdArgs a, Loss
             }
         }
     }
+    if (raw.o) store_goval(a, w, bt, d.P, dv + dt, om);
     for (int p = 0; p < d.P; ++p) {
         const int64_t i = bt * d.P + p;
         if (a.g_value) a.g_value[i] = (dv + dt) * (a.value[i] - w.tv[i]) * om[p];
@@ -616,6 +761,7 @@ __global__ __launch_bounds__(kThreads) void loss_backward_wave_kernel(BwdArgs a,
     const int lane = threadIdx.x & 63;
     const int64_t bt = (int64_t)blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
     if (bt >= d.BT) return;
+    const RawRow raw = raw_row(a.opol, a.tmask, a.amask, bt, d.P, a.Pq, d.A);
     const float dp = a.dl[0], dv = a.dl[1], dr = a.dl[2], de = a.dl[3], dt = a.dl[4];
     const float *tm = a.tmask + bt * d.P;
     const float *om = a.omask + bt * d.P;
@@ -624,8 +770,10 @@ __global__ __launch_bounds__(kThreads) void loss_backward_wave_kernel(BwdArgs a,
     const float cp = -(dp + dt) * w.turn[bt] * em;
     for (int pp = 0; pp < d.Pp; ++pp) {
         const int64_t row = bt * d.Pp + pp;
-        const float *z = a.tpol + row * d.A;
-        float *g = a.g_tpol + row * d.A;
+        const float *z = raw.o ? nullptr : a.tpol + row * d.A;
+        float *g = raw.o ? nullptr : a.g_tpol + row * d.A;
+        // a logit: read, or (block-uniform) formed from the raw head outputs each time it is used
+        auto Z = [&](int q) __attribute__((always_inline)) { return raw.o ? raw_logit(raw, d.A, q) : z[q]; };
         float wsum = 0.f, wdec = 0.f;
         for (int p = 0; p < d.P; ++p) {
             if (d.Pp == 1 || p == pp) {
@@ -637,19 +785,23 @@ __global__ __launch_bounds__(kThreads) void loss_backward_wave_kernel(BwdArgs a,
         const float h = w.ent[row];
         const int64_t act = a.action[row];
         float m = -INFINITY;
-        for (int q = lane; q < d.A; q += 64) m = fmaxf(m, z[q]);
+        for (int q = lane; q < d.A; q += 64) m = fmaxf(m, Z(q));
         m = wave_max(m);
         float s = 0.f;
-        for (int q = lane; q < d.A; q += 64) s += expf(z[q] - m);
+        for (int q = lane; q < d.A; q += 64) s += expf(Z(q) - m);
         s = wave_sum(s);
         const float lse = m + logf(s);
         for (int q = lane; q < d.A; q += 64) {
-            const float pq = expf(z[q] - m) / s;
-            const float la = z[q] - lse;
+            const float zq = Z(q);
+            const float pq = expf(zq - m) / s;
+            const float la = zq - lse;
             const float onehot = (q == act) ? 1.f : 0.f;
-            g[q] = cp * (onehot - pq) + ce * (-pq * (la + h));    // dH/dz = -p (log p + H)
+            const float gq = cp * (onehot - pq) + ce * (-pq * (la + h));    // dH/dz = -p (log p + H)
+            if (raw.o) store_gopol(a, bt, d.P, d.A, q, gq, tm);
+            else g[q] = gq;
         }
     }
+    if (raw.o && lane == 0) store_goval(a, w, bt, d.P, dv + dt, om);
     for (int p = lane; p < d.P; p += 64) {
         const int64_t i = bt * d.P + p;
         if (a.g_value) a.g_value[i] = (dv + dt) * (a.value[i] - w.tv[i]) * om[p];
@@ -758,11 +910,38 @@ int hrl_loss_forward(const float *tpol, const float *bpol, const int64_t *action
                      const float *ret, const float *reward, int value_target, int policy_target, int symmetrize,
                      double lmb, double gamma, double ent_coef, double ent_decay, void *workspace,
                      int64_t workspace_bytes, float *losses, void *stream) {
+    if (!tpol) return HRL_EINVAL;
+    return hrl_loss_forward_ex(tpol, bpol, action, B, T, P, Pp, A, emask, tmask, omask, progress, value, outcome,
+                               ret_out, ret, reward, value_target, policy_target, symmetrize, lmb, gamma, ent_coef,
+                               ent_decay, workspace, workspace_bytes, losses, nullptr, nullptr, nullptr, 0, 1, stream);
+}
+
+int64_t hrl_loss_partials(int64_t B, int64_t T, int64_t P, int64_t Pp, int64_t *offset_bytes) {
+    LossDims d;
+    if (!dims_ok(B, T, P, Pp, 1, d)) return -1;
+    // carve()'s layout: the float arrays, then the fp64 partials at the next 16-byte boundary
+    if (offset_bytes) *offset_bytes = align16((3 * d.BT * d.Pp + 5 * d.BT * d.P + d.BT) * 4);
+    const int G = fused_G(d.B, d.P);
+    return (d.B + G - 1) / G;
+}
+
+int hrl_loss_forward_ex(const float *tpol, const float *bpol, const int64_t *action, int64_t B, int64_t T, int64_t P,
+                        int64_t Pp, int64_t A, const float *emask, const float *tmask, const float *omask,
+                        const float *progress, const float *value, const float *outcome, const float *ret_out,
+                        const float *ret, const float *reward, int value_target, int policy_target, int symmetrize,
+                        double lmb, double gamma, double ent_coef, double ent_decay, void *workspace,
+                        int64_t workspace_bytes, float *losses, const float *opol, const float *oval,
+                        const float *amask, int64_t Pq, int reduce, void *stream) {
     LossDims d;
     if (!dims_ok(B, T, P, Pp, A, d)) return HRL_EINVAL;
-    if (!tpol || !bpol || !action || !emask || !tmask || !omask || !progress || !losses || !workspace)
+    if (!bpol || !action || !emask || !tmask || !omask || !progress || !losses || !workspace) return HRL_EINVAL;
+    if (opol) {   // the raw head outputs stand for the masked policy (one row per step) and value
+        if (tpol || value || !oval || !amask || Pp != 1 || (Pq != 1 && Pq != P)) return HRL_EINVAL;
+    } else if (!tpol || oval || amask) {
         return HRL_EINVAL;
-    if (value && !outcome) return HRL_EINVAL;
+    }
+    const bool hv = value != nullptr || oval != nullptr;
+    if (hv && !outcome) return HRL_EINVAL;
     if (ret_out && (!ret || !reward)) return HRL_EINVAL;
     if (symmetrize && P != 2) return HRL_EINVAL;
     if (value_target < HRL_ALG_MC || value_target > HRL_ALG_VTRACE || policy_target < HRL_ALG_MC ||
@@ -772,10 +951,10 @@ int hrl_loss_forward(const float *tpol, const float *bpol, const int64_t *action
     hipStream_t s = static_cast<hipStream_t>(stream);
     Ws w = carve(workspace, d);
     FwdArgs a{tpol, bpol, action, emask, tmask, omask, progress, value, outcome, ret_out, ret, reward,
-              value_target == HRL_ALG_MC, symmetrize, (float)ent_coef, (float)ent_decay};
+              value_target == HRL_ALG_MC, symmetrize, (float)ent_coef, (float)ent_decay, opol, oval, amask, (int)Pq};
     FusedArgs f{a, d, w, hrl_scan::make_coef(lmb, 1.0), hrl_scan::make_coef(lmb, gamma), fused_G(B, (int)P)};
-    int rc = launch_fused_all(value_target, policy_target, f, value != nullptr, ret_out != nullptr, s);
-    if (rc) return rc;
+    int rc = launch_fused_all(value_target, policy_target, f, hv, ret_out != nullptr, s);
+    if (rc || !reduce) return rc;   // no reduce: the partials stay for hrl_grad_fold_norm_ex's fold
     hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(kThreads), 0, s, w, (float)ent_coef, losses);
     return status();
 }
@@ -785,15 +964,33 @@ int hrl_loss_backward(const float *tpol, const int64_t *action, int64_t B, int64
                       const float *value, const float *ret_out, double ent_coef, double ent_decay,
                       const void *workspace, int64_t workspace_bytes, const float *dlosses, float *g_tpol,
                       float *g_value, float *g_ret, void *stream) {
+    if (!tpol) return HRL_EINVAL;
+    return hrl_loss_backward_ex(tpol, action, B, T, P, Pp, A, emask, tmask, omask, progress, value, ret_out, ent_coef,
+                                ent_decay, workspace, workspace_bytes, dlosses, g_tpol, g_value, g_ret, nullptr,
+                                nullptr, nullptr, 0, nullptr, nullptr, stream);
+}
+
+int hrl_loss_backward_ex(const float *tpol, const int64_t *action, int64_t B, int64_t T, int64_t P, int64_t Pp,
+                         int64_t A, const float *emask, const float *tmask, const float *omask,
+                         const float *progress, const float *value, const float *ret_out, double ent_coef,
+                         double ent_decay, const void *workspace, int64_t workspace_bytes, const float *dlosses,
+                         float *g_tpol, float *g_value, float *g_ret, const float *opol, const float *oval,
+                         const float *amask, int64_t Pq, float *gopol, float *goval, void *stream) {
     LossDims d;
     if (!dims_ok(B, T, P, Pp, A, d)) return HRL_EINVAL;
-    if (!tpol || !action || !emask || !tmask || !omask || !progress || !dlosses || !g_tpol || !workspace)
+    if (!action || !emask || !tmask || !omask || !progress || !dlosses || !workspace) return HRL_EINVAL;
+    if (opol) {
+        if (tpol || value || g_tpol || g_value || !oval || !amask || !gopol || !goval || Pp != 1 ||
+            (Pq != 1 && Pq != P))
+            return HRL_EINVAL;
+    } else if (!tpol || !g_tpol || oval || amask || gopol || goval) {
         return HRL_EINVAL;
+    }
     if ((g_value && !value) || (g_ret && !ret_out)) return HRL_EINVAL;
     if (workspace_bytes < ws_bytes(d)) return HRL_EINVAL;
     Ws w = carve(const_cast<void *>(workspace), d);
     BwdArgs a{tpol, action, emask, tmask, omask, progress, value, ret_out, dlosses, g_tpol, g_value, g_ret,
-              (float)ent_coef, (float)ent_decay};
+              (float)ent_coef, (float)ent_decay, opol, oval, amask, (int)Pq, gopol, goval};
     const dim3 grid(w.nblocks), block(kThreads);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (A == 9) hipLaunchKernelGGL(loss_backward_kernel<9>, grid, block, 0, s, a, d, w);

@@ -176,11 +176,62 @@ __device__ __forceinline__ int64_t fold_dst(int mode, int64_t j) {
 
 constexpr int kFoldWaves = 16;   // waves per fold block: 16 x 8 row loads of 256 B in flight per workgroup
 
+// hrl_grad_fold_norm_ex: the fused loss's per-wave fp64 partials (csrc/hrl_loss.hip, kLossTerms sums each), folded
+// by one workgroup behind the gradient blocks instead of by loss_reduce_kernel's own launch
+constexpr int kLossTerms = 6;
+constexpr int kLossThreads = 256;
+struct LossFold {
+    const double *part;   // NULL: no loss fold (and no extra workgroup)
+    int nparts;
+    float ent_coef;
+    float *losses;
+};
+
 __global__ __launch_bounds__(64 * kFoldWaves) void step_fold_norm_kernel(float *__restrict__ g, int64_t n,
                                                                         FoldTable ft, StepCounters sc,
-                                                                        double *__restrict__ norm_part) {
-    __shared__ double red[kFoldWaves][kBlk];
+                                                                        double *__restrict__ norm_part,
+                                                                        LossFold lf) {
+    // one buffer for both roles: the gradient blocks' [kFoldWaves][kBlk] wave sums, the loss workgroup's
+    // [kLossTerms][kLossThreads] tree
+    __shared__ double shm[kLossTerms * kLossThreads];
+    static_assert(kLossTerms * kLossThreads >= kFoldWaves * kBlk, "the wave sums fit the shared buffer");
     __shared__ double sq[kBlk];
+    if (lf.part && blockIdx.x == gridDim.x - 1) {
+        // loss_reduce_kernel's fold, operation for operation: 256 threads stride the partials, then the halving tree
+        const int t = threadIdx.x;
+        if (t < kLossThreads) {
+            double acc[kLossTerms] = {0, 0, 0, 0, 0, 0};
+            for (int i = t; i < lf.nparts; i += kLossThreads) {
+#pragma unroll
+                for (int k = 0; k < kLossTerms; ++k) acc[k] += lf.part[(int64_t)i * kLossTerms + k];
+            }
+#pragma unroll
+            for (int k = 0; k < kLossTerms; ++k) shm[k * kLossThreads + t] = acc[k];
+        }
+        __syncthreads();
+        for (int s = kLossThreads / 2; s > 0; s >>= 1) {
+            if (t < s) {
+#pragma unroll
+                for (int k = 0; k < kLossTerms; ++k) shm[k * kLossThreads + t] += shm[k * kLossThreads + t + s];
+            }
+            __syncthreads();
+        }
+        if (t == 0) {
+            const float lp = (float)shm[0 * kLossThreads];
+            const float lv = (float)(shm[1 * kLossThreads] / 2.0);
+            const float lr = (float)shm[2 * kLossThreads];
+            const float le = (float)shm[3 * kLossThreads];
+            const float lew = (float)shm[4 * kLossThreads];
+            lf.losses[0] = lp;
+            lf.losses[1] = lv;
+            lf.losses[2] = lr;
+            lf.losses[3] = le;
+            lf.losses[4] = ((lp + lv) + lr) + lew * -lf.ent_coef;   // train.py:211-213
+            lf.losses[5] = (float)shm[5 * kLossThreads];
+        }
+        return;
+    }
+    double (*red)[kBlk] = reinterpret_cast<double (*)[kBlk]>(shm);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int64_t i = (int64_t)blockIdx.x * kBlk + lane;
     int f = -1;
@@ -330,9 +381,23 @@ int hrl_grad_fold_norm(float *grads, int64_t n, const float *const *parts, const
                        const int *modes, int nfolds, float *step, int64_t *const *counters,
                        const int64_t *increments, int ncounters, double *norm_part, int64_t norm_part_bytes,
                        void *stream) {
+    return hrl_grad_fold_norm_ex(grads, n, parts, strides, col0, nparts, dst, count, modes, nfolds, step, counters,
+                                 increments, ncounters, norm_part, norm_part_bytes, nullptr, 0, 0.0, nullptr, stream);
+}
+
+int hrl_grad_fold_norm_ex(float *grads, int64_t n, const float *const *parts, const int64_t *strides,
+                          const int64_t *col0, const int64_t *nparts, const int64_t *dst, const int64_t *count,
+                          const int *modes, int nfolds, float *step, int64_t *const *counters,
+                          const int64_t *increments, int ncounters, double *norm_part, int64_t norm_part_bytes,
+                          const double *loss_part, int64_t loss_nparts, double ent_coef, float *losses,
+                          void *stream) {
     if (!grads || n < 1 || nfolds < 0 || nfolds > kMaxFolds || ncounters < 0 || ncounters > kMaxCounters ||
         !norm_part || norm_part_bytes < hrl_grad_fold_norm_blocks(n) * 8)
         return HRL_EINVAL;
+    if (loss_part && (loss_nparts < 1 || loss_nparts > INT32_MAX || !losses ||
+                      (reinterpret_cast<uintptr_t>(loss_part) & 7) != 0))
+        return HRL_EINVAL;
+    const LossFold lf{loss_part, (int)loss_nparts, (float)ent_coef, losses};
     FoldTable ft{};
     for (int k = 0; k < nfolds; ++k) {
         if (!parts[k] || nparts[k] < 1 || count[k] < 1 || dst[k] < 0 || dst[k] + count[k] > n || col0[k] < 0 ||
@@ -352,8 +417,10 @@ int hrl_grad_fold_norm(float *grads, int64_t n, const float *const *parts, const
         sc.inc[k] = increments ? increments[k] : 1;
     }
     sc.nctr = ncounters;
-    hipLaunchKernelGGL(step_fold_norm_kernel, dim3((unsigned)hrl_grad_fold_norm_blocks(n)), dim3(64 * kFoldWaves), 0,
-                       static_cast<hipStream_t>(stream), grads, n, ft, sc, norm_part);
+    // the loss fold is one workgroup behind the gradient blocks (block indices, and so norm_part, unchanged)
+    const unsigned grid = (unsigned)hrl_grad_fold_norm_blocks(n) + (loss_part ? 1u : 0u);
+    hipLaunchKernelGGL(step_fold_norm_kernel, dim3(grid), dim3(64 * kFoldWaves), 0,
+                       static_cast<hipStream_t>(stream), grads, n, ft, sc, norm_part, lf);
     return status();
 }
 

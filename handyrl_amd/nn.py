@@ -288,8 +288,11 @@ class deferred_folds:
     flat gradient buffer in the step tail's first launch (hrl_grad_fold_norm, together with the clip's norm).  The
     fused chains' BatchNorm batch counters are collected here too, for the same launch."""
 
-    def __init__(self, enabled=True):
+    def __init__(self, enabled=True, take_loss=False):
         self.enabled = enabled
+        # the owner runs the step tail before anything reads the fused loss's vector, so the loss may leave its
+        # partials to that launch (set_loss); LearnerStep says so when its loss function is train.loss_terms itself
+        self.take_loss = take_loss
 
     def __enter__(self):
         global _FOLDS
@@ -298,6 +301,7 @@ class deferred_folds:
         self.counters = []   # int64 num_batches_tracked tensors
         self.increments = []  # and what each advances by
         self.keep = []       # workspaces read by the folds: referenced until the fold launch is enqueued
+        self.loss = None     # the fused loss's hand-over (set_loss): its partials are folded by the same launch
         if self.enabled:
             _FOLDS = self
         return self
@@ -324,6 +328,52 @@ class deferred_folds:
         assert len(self.counters) < self.MAX_COUNTERS, 'deferred folds: counter table full (check has_room first)'
         self.counters.append(counter)
         self.increments.append(int(inc))
+
+    def set_loss(self, ws, part, nparts, ent_coef, losses):
+        """The fused loss left its fp64 partials (`part`, a float64 view of the workspace `ws`, nparts x 6) unfolded:
+        the step tail's first launch folds them into the 6-float vector `losses` (hrl_grad_fold_norm_ex).  Until
+        then the vector is undefined; the workspace is referenced until that launch is enqueued."""
+        assert self.loss is None
+        self.loss = (part, int(nparts), float(ent_coef), losses)
+        self.keep.append(ws)
+
+
+# The fused loss leaves its per-wave partials to the step tail's fold launch when a deferred-folds context is
+# active (no loss_reduce_kernel launch; bit-identical).  False: the loss launches its own reduce.
+LOSS_FOLD = True
+
+
+def _defer_loss():
+    """The deferred-folds context that may take the loss's partials (one active, none handed over yet), or None."""
+    if not LOSS_FOLD or _FOLDS is None or not _FOLDS.take_loss or _FOLDS.loss is not None:
+        return None
+    return _FOLDS
+
+
+# The learner's flat gradient buffer is zeroed by the step's first chain forward (hrl_conv3x3_pack_n_zero: the
+# weight-packing launch with extra workgroups) instead of by a fill launch of its own.  LearnerStep posts the
+# buffer here before the forward and zeroes it itself if no chain took it.  False: the fill launch.
+PACK_ZERO = True
+_PENDING_ZERO = None
+
+
+def post_zero(flat):
+    """Offer `flat` (a float32 CUDA tensor) to the next _chain_forward for zeroing; False when the switch is off."""
+    global _PENDING_ZERO
+    if not PACK_ZERO or not flat.is_cuda or flat.dtype != torch.float32 or not flat.is_contiguous():
+        return False
+    _PENDING_ZERO = flat
+    return True
+
+
+def take_zero(device=None):
+    """The posted buffer, once (None when there is none or it lives on another device)."""
+    global _PENDING_ZERO
+    z = _PENDING_ZERO
+    if z is None or (device is not None and z.device != device):
+        return None
+    _PENDING_ZERO = None
+    return z
 
 
 def _defer_folds(bufs, nfolds=None):
@@ -1999,6 +2049,12 @@ def _chain_forward(h0, meta, relu_in, params, apply_out=True):
     weights = [params[3 * i].contiguous() for i in range(len(meta))]
     packed = torch.empty(len(weights), 2, 9216, dtype=torch.float32, device=dev)
     for k in range(0, len(weights), 8):       # hrl_conv3x3_pack_n takes up to 8 weights per launch
+        zero = take_zero(dev)                 # the step's gradient buffer, if this is its first chain forward
+        if zero is not None:
+            _native.check(lib.hrl_conv3x3_pack_n_zero(_native.ptr_array(weights[k:k + 8]), len(weights[k:k + 8]),
+                                                      P(packed[k]), P(zero), zero.numel(), stream),
+                          'hrl_conv3x3_pack_n_zero')
+            continue
         _native.check(lib.hrl_conv3x3_pack_n(_native.ptr_array(weights[k:k + 8]), len(weights[k:k + 8]),
                                              P(packed[k]), stream), 'hrl_conv3x3_pack_n')
     for i, (rm, rv, momentum, eps) in enumerate(meta):

@@ -73,12 +73,15 @@ def forward_prediction(model, hidden, batch, args):
             hidden = trimap_r(hidden, next_hidden, om, lambda h, nh, m: h * (1 - m) + nh * m)
         outputs = {k: torch.stack(o, dim=1) for k, o in per_t.items() if o[0] is not None}
 
-    result = {}
     fused = _output_mask_fusable(outputs, batch, B, T)
+    result = _RawOutputs() if (fused and RAW_LOSS) else {}
     if fused:
-        result['policy'], result['value'] = _OutputMask.apply(
-            outputs['policy'].view(B, T, -1, outputs['policy'].size(-1)),
-            outputs['value'].view(B, T, -1, 1), tmask, batch['observation_mask'], batch['action_mask'])
+        raw = (outputs['policy'].view(B, T, -1, outputs['policy'].size(-1)),
+               outputs['value'].view(B, T, -1, 1), tmask, batch['observation_mask'], batch['action_mask'])
+        if RAW_LOSS:
+            result.hold(raw)    # masked on first read; loss_terms takes the raw tensors instead
+        else:
+            result['policy'], result['value'] = _OutputMask.apply(*raw)
     for k, o in outputs.items():
         if k == 'hidden' or o is None or (fused and k in ('policy', 'value')):
             continue
@@ -88,6 +91,81 @@ def forward_prediction(model, hidden, batch, args):
         else:
             result[k] = o.mul(batch['observation_mask'])
     return result
+
+
+# forward_prediction hands the loss the raw policy / value head outputs and the fused loss kernels mask them per
+# element (hrl_loss_forward_ex / hrl_loss_backward_ex: no out_mask launches; bit-identical).  False: _OutputMask.
+RAW_LOSS = True
+
+
+class _RawOutputs(dict):
+    """forward_prediction's result while 'policy' and 'value' are still the raw head outputs: to every reader it is
+    the dict the masked path returns (same keys, same order, same values) -- the first read of either entry, or of
+    the values as a whole, runs _OutputMask -- while loss_terms takes the raw tensors (`raw`) and never masks."""
+
+    def hold(self, raw):
+        self.raw = raw              # (opol (B,T,Pq,A), oval (B,T,Pq,1), tmask, omask, amask); None once masked
+        dict.__setitem__(self, 'policy', None)
+        dict.__setitem__(self, 'value', None)
+
+    def _mask(self):
+        raw = getattr(self, 'raw', None)
+        if raw is not None:
+            self.raw = None
+            pol, val = _OutputMask.apply(*raw)
+            dict.__setitem__(self, 'policy', pol)
+            dict.__setitem__(self, 'value', val)
+
+    def __getitem__(self, k):
+        if k in ('policy', 'value'):
+            self._mask()
+        return dict.__getitem__(self, k)
+
+    def get(self, k, default=None):
+        if k in ('policy', 'value'):
+            self._mask()
+        return dict.get(self, k, default)
+
+    def __setitem__(self, k, v):
+        if k in ('policy', 'value'):
+            self._mask()
+        dict.__setitem__(self, k, v)
+
+    def __iter__(self):             # also keeps dict(x) / {**x} off the C fast path, so they read through __getitem__
+        return dict.__iter__(self)
+
+    def keys(self):
+        return dict.keys(self)
+
+    def items(self):
+        self._mask()
+        return dict.items(self)
+
+    def values(self):
+        self._mask()
+        return dict.values(self)
+
+    def pop(self, k, *default):
+        self._mask()
+        return dict.pop(self, k, *default)
+
+    def copy(self):
+        self._mask()
+        return dict(dict.items(self))
+
+    def __eq__(self, other):
+        self._mask()
+        return dict.__eq__(self, other)
+
+    def __ne__(self, other):
+        self._mask()
+        return dict.__ne__(self, other)
+
+    __hash__ = None
+
+    def __repr__(self):
+        self._mask()
+        return dict.__repr__(self)
 
 
 def _output_mask_fusable(outputs, batch, B, T):
@@ -297,12 +375,23 @@ class _FusedLoss(torch.autograd.Function):
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=tpol.device)
         losses = torch.empty(6, dtype=torch.float32, device=tpol.device)
         p = _native.ptr
-        code = lib.hrl_loss_forward(
-            p(tpol), p(bpol), p(action), B, T, P, Pp, A, p(emask), p(tmask), p(omask), p(progress),
-            p(value), p(outcome), p(ret_out), p(ret), p(reward),
-            cfg['value_target'], cfg['policy_target'], cfg['symmetrize'], cfg['lambda'], cfg['gamma'],
-            cfg['ent_coef'], cfg['ent_decay'], p(ws), ws_bytes, p(losses), _native.stream_of(tpol.device))
-        _native.check(code, 'hrl_loss_forward')
+        df = _defer_loss()
+        if df is None:
+            code = lib.hrl_loss_forward(
+                p(tpol), p(bpol), p(action), B, T, P, Pp, A, p(emask), p(tmask), p(omask), p(progress),
+                p(value), p(outcome), p(ret_out), p(ret), p(reward),
+                cfg['value_target'], cfg['policy_target'], cfg['symmetrize'], cfg['lambda'], cfg['gamma'],
+                cfg['ent_coef'], cfg['ent_decay'], p(ws), ws_bytes, p(losses), _native.stream_of(tpol.device))
+            _native.check(code, 'hrl_loss_forward')
+        else:   # the step tail folds the partials (no reduce launch)
+            code = lib.hrl_loss_forward_ex(
+                p(tpol), p(bpol), p(action), B, T, P, Pp, A, p(emask), p(tmask), p(omask), p(progress),
+                p(value), p(outcome), p(ret_out), p(ret), p(reward),
+                cfg['value_target'], cfg['policy_target'], cfg['symmetrize'], cfg['lambda'], cfg['gamma'],
+                cfg['ent_coef'], cfg['ent_decay'], p(ws), ws_bytes, p(losses), None, None, None, 0, 0,
+                _native.stream_of(tpol.device))
+            _native.check(code, 'hrl_loss_forward_ex')
+            _hand_over_loss(df, lib, ws, (B, T, P, Pp), cfg, losses)
         ctx.cfg = cfg
         ctx.has_value, ctx.has_ret = value is not None, ret_out is not None
         ctx.save_for_backward(tpol, value, ret_out, action, emask, tmask, omask, progress, ws)
@@ -327,6 +416,71 @@ class _FusedLoss(torch.autograd.Function):
         return (g_tpol, g_value, g_ret) + (None,) * 10
 
 
+def _defer_loss():
+    from .nn import _defer_loss as defer
+    return defer()
+
+
+def _hand_over_loss(df, lib, ws, dims, cfg, losses):
+    """Register the loss partials left in `ws` with the deferred-folds context: the step tail folds them into
+    `losses` (nn.deferred_folds.set_loss keeps the workspace alive until then)."""
+    import ctypes
+    off = ctypes.c_int64(0)
+    nparts = lib.hrl_loss_partials(*dims, ctypes.byref(off))
+    part = ws[off.value:off.value + nparts * 48].view(torch.float64)
+    df.set_loss(ws, part, nparts, cfg['ent_coef'], losses)
+
+
+class _FusedLossRaw(torch.autograd.Function):
+    """_OutputMask + _FusedLoss on the raw policy / value head outputs as the loss's own two launches
+    (hrl_loss_forward_ex / hrl_loss_backward_ex): the kernels form each masked logit and value where they read it and
+    write the gradients of the raw outputs directly.  Bit-identical to the two Functions."""
+
+    @staticmethod
+    def forward(ctx, opol, oval, ret_out, amask, bpol, action, emask, tmask, omask, progress, outcome, ret, reward,
+                cfg):
+        B, T, Pq, A = opol.shape
+        P = tmask.shape[2]
+        lib = _native.load()
+        ws_bytes = lib.hrl_loss_workspace_bytes(B, T, P, 1)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=opol.device)
+        losses = torch.empty(6, dtype=torch.float32, device=opol.device)
+        p = _native.ptr
+        df = _defer_loss()
+        code = lib.hrl_loss_forward_ex(
+            None, p(bpol), p(action), B, T, P, 1, A, p(emask), p(tmask), p(omask), p(progress),
+            None, p(outcome), p(ret_out), p(ret), p(reward),
+            cfg['value_target'], cfg['policy_target'], cfg['symmetrize'], cfg['lambda'], cfg['gamma'],
+            cfg['ent_coef'], cfg['ent_decay'], p(ws), ws_bytes, p(losses), p(opol), p(oval), p(amask), Pq,
+            int(df is None), _native.stream_of(opol.device))
+        _native.check(code, 'hrl_loss_forward_ex')
+        if df is not None:
+            _hand_over_loss(df, lib, ws, (B, T, P, 1), cfg, losses)
+        ctx.cfg = cfg
+        ctx.has_ret = ret_out is not None
+        ctx.save_for_backward(opol, oval, ret_out, amask, action, emask, tmask, omask, progress, ws)
+        return losses
+
+    @staticmethod
+    def backward(ctx, dlosses):
+        opol, oval, ret_out, amask, action, emask, tmask, omask, progress, ws = ctx.saved_tensors
+        B, T, Pq, A = opol.shape
+        P = tmask.shape[2]
+        dl = dlosses[:5].contiguous()
+        gopol = torch.empty_like(opol)
+        goval = torch.empty_like(oval)
+        g_ret = torch.empty_like(ret_out) if ctx.has_ret else None
+        p = _native.ptr
+        lib = _native.load()
+        code = lib.hrl_loss_backward_ex(
+            None, p(action), B, T, P, 1, A, p(emask), p(tmask), p(omask), p(progress),
+            None, p(ret_out), ctx.cfg['ent_coef'], ctx.cfg['ent_decay'], p(ws), ws.numel(), p(dl),
+            None, None, p(g_ret), p(opol), p(oval), p(amask), Pq, p(gopol), p(goval),
+            _native.stream_of(opol.device))
+        _native.check(code, 'hrl_loss_backward_ex')
+        return (gopol, goval, g_ret) + (None,) * 11
+
+
 def _fusable(outputs, batch):
     pol = outputs.get('policy')
     if pol is None or not pol.is_cuda or pol.dtype != torch.float32 or pol.dim() != 4:
@@ -341,12 +495,15 @@ def _fusable(outputs, batch):
 
 def loss_terms(outputs, batch, args):
     """train.py:220-258 and compose_losses on the HIP kernels; (losses, dcnt tensor), no host sync."""
-    if not _fusable(outputs, batch):
+    raw = _raw_fusable(outputs, batch)
+    if raw is None and not _fusable(outputs, batch):
         return loss_terms_composed(outputs, batch, args)
     alg = _native.ALG
     for k in ('value_target', 'policy_target'):
         if args[k] not in alg:
             raise ValueError('No algorithm named %s' % args[k])
+    if raw is not None:
+        return _loss_terms_raw(raw, outputs, batch, args)
     value, ret_out = outputs.get('value'), outputs.get('return')
     P = batch['turn_mask'].shape[2]
     cfg = {'value_target': alg[args['value_target']], 'policy_target': alg[args['policy_target']],
@@ -361,8 +518,12 @@ def loss_terms(outputs, batch, args):
                            c(batch['observation_mask']), c(batch['progress']),
                            c(batch['outcome']) if value is not None else None,
                            c(batch['return']) if with_ret else None, c(batch['reward']) if with_ret else None, cfg)
+    return _losses_of(vec, value is not None, with_ret)
+
+
+def _losses_of(vec, with_value, with_ret):
     losses = {'p': vec[0]}
-    if value is not None:
+    if with_value:
         losses['v'] = vec[1]
     if with_ret:
         losses['r'] = vec[2]
@@ -371,6 +532,37 @@ def loss_terms(outputs, batch, args):
     total._hrl_loss_vec = vec   # backward_total seeds the vector itself
     losses['total'] = total
     return losses, vec[5].detach()
+
+
+def _raw_fusable(outputs, batch):
+    """forward_prediction's still-unmasked raw outputs when the fused loss can take them as they are (what
+    _fusable asks of the masked tensors holds for them by _output_mask_fusable; a 'return' head must fit too)."""
+    raw = getattr(outputs, 'raw', None) if isinstance(outputs, _RawOutputs) else None
+    if raw is None or not RAW_LOSS:
+        return None
+    o = dict.get(outputs, 'return')
+    if o is not None and (o.dim() != 4 or o.shape[-1] != 1 or o.dtype != torch.float32):
+        return None
+    return raw
+
+
+def _loss_terms_raw(raw, outputs, batch, args):
+    """loss_terms on the raw head outputs (_FusedLossRaw); the masks are the ones forward_prediction held."""
+    opol, oval, tmask, omask, amask = raw
+    ret_out = dict.get(outputs, 'return')
+    P = tmask.shape[2]
+    cfg = {'value_target': _native.ALG[args['value_target']], 'policy_target': _native.ALG[args['policy_target']],
+           'symmetrize': int(bool(args['turn_based_training']) and P == 2),
+           'lambda': float(args['lambda']), 'gamma': float(args['gamma']),
+           'ent_coef': float(args['entropy_regularization']),
+           'ent_decay': float(args['entropy_regularization_decay'])}
+    c = lambda t: None if t is None else t.contiguous()  # noqa: E731
+    with_ret = ret_out is not None
+    vec = _FusedLossRaw.apply(opol, oval, c(ret_out), amask, c(batch['policy'].detach()), c(batch['action']),
+                              c(batch['episode_mask']), tmask, omask, c(batch['progress']), c(batch['outcome']),
+                              c(batch['return']) if with_ret else None, c(batch['reward']) if with_ret else None,
+                              cfg)
+    return _losses_of(vec, True, with_ret)
 
 
 _SEEDS = {}

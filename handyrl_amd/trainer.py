@@ -10,8 +10,9 @@
 differences from the reference that do not change the arithmetic:
 * no ``.item()`` in the step: loss sums and ``dcnt`` accumulate on the device
   and are read once per epoch (train.py:199, :390 sync every step);
-* gradients sit in one flat buffer (zeroed by one kernel, clipped by one
-  norm, all-reduced in a few buckets);
+* gradients sit in one flat buffer (zeroed by the first conv chain's weight
+  packing launch, or by one fill where the net has none; clipped by one norm,
+  all-reduced in a few buckets);
 * optionally the whole step is captured once in a HIP graph and replayed
   (``graph=True``): the batch tensors are then static buffers that the caller
   refills (``load_batch``), exactly like a graph's input slots.
@@ -28,6 +29,7 @@ import torch
 import torch.nn as nn
 
 from . import distributed as hdist
+from . import nn as hnn
 from .nn import accelerate, fuse_bn_relu, deferred_weight_grads, deferred_folds, direct_grads
 from .train import backward_total, forward_prediction, loss_terms
 from .util import map_r, bimap_r
@@ -102,13 +104,21 @@ class StepTail:
         i64 = _native.i64_array
         import ctypes
         stream = _native.stream_of(flat.device)
-        _native.check(lib.hrl_grad_fold_norm(
+        fold_args = (
             P(flat), self.n, _native.ptr_array([f[0] for f in fl]), i64([f[1] for f in fl]),
             i64([f[2] for f in fl]), i64([f[3] for f in fl]), i64(dst), i64([f[5] for f in fl]),
             (ctypes.c_int * max(len(fl), 1))(*[f[6] for f in fl]), len(fl), P(self.step_t),
             _native.ptr_array(counters), i64(incs) if incs else None, len(counters), P(self.norm_part),
-            self.norm_part.numel() * 8, stream),
-            'hrl_grad_fold_norm')
+            self.norm_part.numel() * 8)
+        loss = folds.loss if folds is not None else None
+        if loss is not None:
+            # the fused loss's partials -> its 6-float vector, by one workgroup more of the same launch; the vector's
+            # first reader is hrl_adam_clip below (the running statistics)
+            part, nparts, ent_coef, losses = loss
+            _native.check(lib.hrl_grad_fold_norm_ex(*fold_args, P(part), nparts, ent_coef, P(losses), stream),
+                          'hrl_grad_fold_norm_ex')
+        else:
+            _native.check(lib.hrl_grad_fold_norm(*fold_args, stream), 'hrl_grad_fold_norm')
         srcs, acc_dst = acc if acc is not None else ([], None)
         acc_src = (ctypes.c_void_p * max(len(srcs), 1))(*[None if t is self.total else t.data_ptr() for t in srcs])
         _native.check(lib.hrl_adam_clip(
@@ -254,15 +264,17 @@ class LearnerStep:
             obs = batch['observation']
             if hidden is None and isinstance(obs, torch.Tensor):
                 self.fused_pairs = fuse_bn_relu(self.net, obs[:2].reshape(-1, *obs.shape[3:]))
-        self.grads.zero()
+        # the zero rides on the first chain forward's packing launch (nn.PACK_ZERO; _forward zeroes if none took it)
+        if not hnn.post_zero(self.grads.flat):
+            self.grads.zero()
         if hidden is not None and self.defer:
             # recurrent unroll: every weight is used T times; batch its weight gradients (nn.DeferredGrads).  On
             # one GPU the single-use parameters' gradients are written in place (direct_grads: the grouped
             # BatchNorms) and the BatchNorm batch counters ride on the step tail (deferred_folds)
             single = self.reducer is None
             with deferred_weight_grads() as deferred, (direct_grads() if single else contextlib.nullcontext()), \
-                    deferred_folds(enabled=self.fold_deferral) as df:
-                outputs = forward_prediction(self.net, hidden, batch, self.args)
+                    deferred_folds(enabled=self.fold_deferral, take_loss=self.loss_fn is loss_terms) as df:
+                outputs = self._forward(hidden, batch)
                 losses, dcnt = self.loss_fn(outputs, batch, self.args)
                 backward_total(losses)
             self._folds = df if self.fold_deferral else None
@@ -278,12 +290,24 @@ class LearnerStep:
             # the HIP Functions write single-use parameter gradients straight into the flat buffer
             # (zeroed above) instead of autograd's per-parameter accumulate-adds (nn.direct_grads); on one GPU
             # they leave them as partial rows that the step tail folds (nn.deferred_folds)
-            with direct_grads(), deferred_folds(enabled=self.fold_deferral) as df:
-                outputs = forward_prediction(self.net, hidden, batch, self.args)
+            with direct_grads(), deferred_folds(enabled=self.fold_deferral, take_loss=self.loss_fn is loss_terms) as df:
+                outputs = self._forward(hidden, batch)
                 losses, dcnt = self.loss_fn(outputs, batch, self.args)
                 backward_total(losses)
             self._folds = df if self.fold_deferral else None
         return losses, dcnt
+
+    def _forward(self, hidden, batch):
+        """forward_prediction; afterwards the gradient buffer is zero or about to be: a chain forward took the
+        zero _grads posted, or (no conv chain in the net) it is zeroed here.  Nothing writes a gradient before the
+        backward, so either order is the same."""
+        try:
+            outputs = forward_prediction(self.net, hidden, batch, self.args)
+        finally:
+            pending = hnn.take_zero() is not None
+        if pending:
+            self.grads.zero()
+        return outputs
 
     def _update(self, losses, dcnt):
         """clip_grad_norm_(4.0) on the (all-reduced) gradients, then Adam (train.py:384-385)."""

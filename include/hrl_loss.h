@@ -72,6 +72,39 @@ int hrl_output_mask_backward(const float *gpol, const float *gval, const float *
                              int64_t BT, int64_t P, int64_t Pq, int64_t A, float *gopol, float *goval,
                              void *stream);
 
+/*
+ * The loss on the RAW head outputs: hrl_output_mask_forward / _backward folded into the loss launches.
+ * With opol != NULL (then oval and amask too, Pp = 1, tpol = value = NULL) every logit and value is formed as
+ * hrl_output_mask_forward forms it, from opol (BT, Pq, A), oval (BT, Pq), tmask, omask and amask (BT, A), in
+ * the same float operations; the backward writes gopol (BT, Pq, A) and goval (BT, Pq) with
+ * hrl_output_mask_backward's operations (g_tpol and g_value are not written and must be NULL).  With
+ * opol == NULL the two entries are hrl_loss_forward / hrl_loss_backward.  Results are bit-identical to the
+ * separate launches either way.
+ * reduce = 0: only the fused kernel is launched; the nparts x 6 fp64 partials stay in the workspace at
+ * hrl_loss_partials()'s offset and `losses` is written by hrl_grad_fold_norm_ex (hrl_nn.h), which must run
+ * before anything reads the vector.
+ */
+int64_t hrl_loss_partials(int64_t B, int64_t T, int64_t P, int64_t Pp, int64_t *offset_bytes);
+int hrl_loss_forward_ex(const float *tpol, const float *bpol, const int64_t *action,
+                        int64_t B, int64_t T, int64_t P, int64_t Pp, int64_t A,
+                        const float *emask, const float *tmask, const float *omask, const float *progress,
+                        const float *value, const float *outcome,
+                        const float *ret_out, const float *ret, const float *reward,
+                        int value_target, int policy_target, int symmetrize,
+                        double lmb, double gamma, double ent_coef, double ent_decay,
+                        void *workspace, int64_t workspace_bytes, float *losses,
+                        const float *opol, const float *oval, const float *amask, int64_t Pq, int reduce,
+                        void *stream);
+int hrl_loss_backward_ex(const float *tpol, const int64_t *action,
+                         int64_t B, int64_t T, int64_t P, int64_t Pp, int64_t A,
+                         const float *emask, const float *tmask, const float *omask, const float *progress,
+                         const float *value, const float *ret_out,
+                         double ent_coef, double ent_decay,
+                         const void *workspace, int64_t workspace_bytes, const float *dlosses,
+                         float *g_tpol, float *g_value, float *g_ret,
+                         const float *opol, const float *oval, const float *amask, int64_t Pq,
+                         float *gopol, float *goval, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

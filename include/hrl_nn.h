@@ -192,6 +192,12 @@ int hrl_conv3x3_set_fwd_form(int form);
  * 1 input gradient (host array of device pointers).  hrl_conv3x3_forward_ex with flip | 2 takes `weight`
  * as such a packed layout and skips its own packing launch. */
 int hrl_conv3x3_pack_n(const float *const *weights, int n, float *packed, void *stream);
+/* The same, and in the same launch zero[0 .. zero_floats) = 0 (extra workgroups: 16-byte stores over the aligned
+ * middle, single floats at both ragged ends): the learner's flat gradient buffer, zeroed by the step's first chain
+ * forward instead of by a fill launch of its own.  zero is 4-byte aligned; zero_floats = 0: nothing is zeroed
+ * (zero may be NULL). */
+int hrl_conv3x3_pack_n_zero(const float *const *weights, int n, float *packed, float *zero, int64_t zero_floats,
+                            void *stream);
 int hrl_conv3x3_forward_ex(const float *x, int64_t M, const float *in_alpha, const float *in_beta,
                            const float *weight, const float *bias, int flip, float *y, int epilogue,
                            const float *ref, const float *ep_mean, const float *ep_alpha, const float *ep_beta,
@@ -575,6 +581,18 @@ int hrl_grad_fold_norm(float *grads, int64_t n, const float *const *parts, const
                        const int *modes, int nfolds, float *step, int64_t *const *counters,
                        const int64_t *increments, int ncounters, double *norm_part, int64_t norm_part_bytes,
                        void *stream);
+/* hrl_grad_fold_norm, and with loss_part != NULL one workgroup more that folds the fused loss's loss_nparts x 6
+ * fp64 partials (hrl_loss_forward_ex with reduce = 0; hrl_loss_partials gives their place in the loss workspace)
+ * into the 6-float loss vector `losses`, with loss_reduce_kernel's operations in its order (bit-identical to
+ * hrl_loss_forward's vector).  Precondition: nothing reads `losses` between that forward and this launch --
+ * the vector is undefined until then (the learner's next reader is hrl_adam_clip's statistics); the workspace
+ * must stay allocated until this launch is enqueued. */
+int hrl_grad_fold_norm_ex(float *grads, int64_t n, const float *const *parts, const int64_t *strides,
+                          const int64_t *col0, const int64_t *nparts, const int64_t *dst, const int64_t *count,
+                          const int *modes, int nfolds, float *step, int64_t *const *counters,
+                          const int64_t *increments, int ncounters, double *norm_part, int64_t norm_part_bytes,
+                          const double *loss_part, int64_t loss_nparts, double ent_coef, float *losses,
+                          void *stream);
 int hrl_adam_clip(float *grads, int64_t n, const double *norm_part, double max_norm, float *total_norm,
                   float *const *params, const int64_t *offsets, const int *live, int ntensors, float *exp_avg,
                   float *exp_avg_sq, const float *lr, const float *step, double beta1, double beta2, double eps,
