@@ -21,7 +21,11 @@
 //     tile [t][column] whose row stride (columns+1) makes both the transposing
 //     writes and the per-lane column reads bank-conflict free;
 //   * outputs go to LDS tiles of the same shape and leave through the mirror
-//     transposition with coalesced 16-byte stores.
+//     transposition with coalesced 16-byte stores;
+//   * operands given as strided or broadcast views (hrl_compute_targets_strided)
+//     take MODE = kStrided: the same tiles, filled through SChunk, which picks
+//     16-byte or 4-byte loads per operand from its strides and alignment.
+//     C-contiguous calls of that entry launch the kScalar / kVec kernels.
 // Numerics: built with -ffp-contract=off; every recurrence performs the
 // reference's float32 operations in the reference's order with the same
 // float32-rounded coefficients, so results are bit-identical to the
@@ -50,6 +54,7 @@ constexpr int kMaxScalar = kMaxTile / kWave;         // scalar loads per lane (3
 //   global: trajectory b0+g, time t0+tt, column cx at (b0+g)*R + t0*Cx + tt*Cx + cx
 //   LDS   : trajectory-major rows, [g][tt*Cx + cx], row stride Lp
 struct Chunk {
+    typedef int ofs_t;
     const float *base;  // element (g=0, tt=0, cx=0)
     int R;              // row length of one trajectory (T*Cx)
     int L;              // span length of one trajectory in this chunk (tc*Cx)
@@ -88,12 +93,98 @@ struct Chunk {
     }
 };
 
-// Registers holding one chunk between its global loads and its LDS writes.
-template <bool VEC>
-struct Staged {
-    float x[VEC ? 4 * kMaxVec : kMaxScalar];
+// Load modes of targets_kernel.  kStrided takes per-operand element strides (hrl_compute_targets_strided) and
+// picks 16-byte or 4-byte loads per operand at run time (a wave-uniform flag of its SChunk).
+constexpr int kScalar = 0, kVec = 1, kStrided = 2;
 
-    __device__ __forceinline__ void load(const Chunk &c) {
+// Element strides of one operand of the strided entry point.  The operand's logical shape is (B, T, P, K); it is
+// staged into an LDS tile of Px*Kx columns per step: (P, K) for value-shaped operands, (1, 1), (P, 1) or (P, K)
+// for rhos / cs, the narrowest tile both fit.  An axis of the tile with extent 1 is never indexed.
+struct Strd {
+    int64_t sB;          // trajectory stride: any size, applied in 64-bit arithmetic
+    int sT, sP, sK;      // inner strides: the host proves (T-1)*sT + (P-1)*sP + (K-1)*sK < 2^31
+    int Px, Kx;          // tile columns
+    int canon;           // inner layout is the tile's own: offset = g*sB + tt*Px*Kx + cx
+};
+
+// Chunk for an operand with strides: the same LDS layout, the global offset from the strides.
+//   global: trajectory b0+g, time t0+tt, tile column cx = p*Kx + k at (b0+g)*sB + (t0+tt)*sT + p*sP + k*sK
+struct SChunk {
+    typedef int64_t ofs_t;
+    const float *base;  // element (g=0, tt=0, cx=0): the wave-uniform 64-bit part of every address
+    int64_t sB;
+    int sT, sP, sK, Kx, Cx;
+    float invCx, invKx;
+    int L, Lp, n;
+    float invL;
+    bool canon;         // offset = g*sB + rem (no (tt, p, k) split)
+    bool contig;        // canon and sB == L: offset = e, a float4 may straddle two trajectories
+    bool vec;           // 16-byte loads are legal for this operand in this wave
+
+    __device__ __forceinline__ void setup(const float *p, const Strd &s, int64_t b0, int t0, int tc, int ntraj,
+                                          int Lp_) {
+        sB = s.sB; sT = s.sT; sP = s.sP; sK = s.sK; Kx = s.Kx;
+        Cx = s.Px * s.Kx;
+        L = tc * Cx;
+        Lp = Lp_;
+        n = ntraj * L;
+        invL = 1.0f / (float)L;
+        invCx = 1.0f / (float)Cx;
+        invKx = 1.0f / (float)Kx;
+        base = p + b0 * sB + (int64_t)t0 * sT;
+        canon = s.canon != 0;
+        contig = canon && sB == (int64_t)L;
+        // as Chunk::setup with R = sB: whole-float4 spans at whole-float4 trajectory strides, or one contiguous run
+        const bool shape_ok = contig || ((L & 3) == 0 && (sB & 3) == 0);
+        vec = canon && shape_ok && ((reinterpret_cast<uintptr_t>(base) & 15) == 0);
+    }
+
+    __device__ __forceinline__ void locate(int e, int64_t &gofs, int &slot) const {
+        const int g = fdiv(e, invL);
+        const int rem = e - g * L;
+        slot = g * Lp + rem;
+        if (contig) {
+            gofs = e;
+        } else if (canon) {
+            gofs = g * sB + rem;
+        } else {
+            const int tt = fdiv(rem, invCx);
+            const int cx = rem - tt * Cx;
+            const int p = fdiv(cx, invKx);
+            const int k = cx - p * Kx;
+            gofs = g * sB + (tt * sT + p * sP + k * sK);
+        }
+    }
+    __device__ __forceinline__ int slot_after(int g, int rem, int j) const {
+        const int r = rem + j;
+        const bool wrap = r >= L;
+        return (wrap ? g + 1 : g) * Lp + (wrap ? r - L : r);
+    }
+};
+
+// Registers holding one chunk between its global loads and its LDS writes.
+template <int MODE, class CH = Chunk>
+struct Staged {
+    static_assert(4 * kMaxVec == kMaxScalar, "both load forms stage a chunk in the same registers");
+    float x[kMaxScalar];
+
+    __device__ __forceinline__ void load(const CH &c) {
+        if constexpr (MODE == kStrided) {
+            if (c.vec) load_as<true>(c); else load_as<false>(c);
+        } else {
+            load_as<MODE == kVec>(c);
+        }
+    }
+    __device__ __forceinline__ void to_lds(const CH &c, float *tile) const {
+        if constexpr (MODE == kStrided) {
+            if (c.vec) to_lds_as<true>(c, tile); else to_lds_as<false>(c, tile);
+        } else {
+            to_lds_as<MODE == kVec>(c, tile);
+        }
+    }
+
+    template <bool VEC>
+    __device__ __forceinline__ void load_as(const CH &c) {
         if (c.n <= 0) return;
         const int lane = threadIdx.x;
         if constexpr (VEC) {
@@ -104,7 +195,7 @@ struct Staged {
                 if (k * kWave >= nv) break;   // wave-uniform: small tiles issue fewer rounds
                 // clamp instead of branching so every load issues back to back
                 const int vi = min(k * kWave + lane, nv - 1);
-                int go; int slot;
+                typename CH::ofs_t go; int slot;
                 c.locate(vi * 4, go, slot);
                 const float4 q = *reinterpret_cast<const float4 *>(c.base + go);
                 x[4 * k + 0] = q.x; x[4 * k + 1] = q.y; x[4 * k + 2] = q.z; x[4 * k + 3] = q.w;
@@ -114,14 +205,15 @@ struct Staged {
             for (int k = 0; k < kMaxScalar; ++k) {
                 if (k * kWave >= c.n) break;
                 const int e = min(k * kWave + lane, c.n - 1);
-                int go; int slot;
+                typename CH::ofs_t go; int slot;
                 c.locate(e, go, slot);
                 x[k] = c.base[go];
             }
         }
     }
 
-    __device__ __forceinline__ void to_lds(const Chunk &c, float *tile) const {
+    template <bool VEC>
+    __device__ __forceinline__ void to_lds_as(const CH &c, float *tile) const {
         if (c.n <= 0) return;
         const int lane = threadIdx.x;
         if constexpr (VEC) {
@@ -140,7 +232,7 @@ struct Staged {
             // ragged tail (< 4 elements) of a contiguous span
             const int e = nv * 4 + lane;
             if (e < c.n) {
-                int go; int slot;
+                typename CH::ofs_t go; int slot;
                 c.locate(e, go, slot);
                 tile[slot] = c.base[go];
             }
@@ -150,7 +242,7 @@ struct Staged {
                 if (k * kWave >= c.n) break;
                 const int e = k * kWave + lane;
                 if (e < c.n) {
-                    int go; int slot;
+                    typename CH::ofs_t go; int slot;
                     c.locate(e, go, slot);
                     tile[slot] = x[k];
                 }
@@ -203,6 +295,20 @@ struct Args {
     Coef k;
 };
 
+// Arguments of the strided instantiations: Args (rhoC / rhoDiv describe the rho tile) plus every operand's strides.
+struct SArgs : Args {
+    Strd sv, sret, srew, srho, scs;
+    int K;          // value columns are (p, k) = (c / K, c % K)
+    int outVec;     // 16-byte stores of the (contiguous) outputs are legal
+};
+
+// Offset of time step t, value column c in an operand with strides s (without the trajectory term).
+__device__ __forceinline__ int inner_offset(const Strd &s, int t, int c, int K) {
+    const int p = fdiv(c, 1.0f / (float)K);
+    const int k = c - p * K;
+    return t * s.sT + p * s.sP + k * s.sK;
+}
+
 // TGT: algorithm whose target is written (kNone: no target output).
 // ADV: algorithm whose advantages are written.
 // REW: rewards present.  RETT: MC reads returns at every t (ret_T == T).
@@ -212,8 +318,12 @@ struct Args {
 __host__ __device__ __forceinline__ int odd_row(int tmax, int Cx) { return Cx * (tmax | 1); }
 
 // ONE: T <= kTChunk, the whole trajectory is one chunk (no prefetch path: ~70 registers instead of 216).
-template <int TGT, int ADV, bool REW, bool RETT, bool VEC, bool ONE>
-__global__ __launch_bounds__(kWave) void targets_kernel(Args a) {
+// MODE: kScalar / kVec for C-contiguous operands (the host picks), kStrided for operands with strides.
+template <int TGT, int ADV, bool REW, bool RETT, int MODE, bool ONE>
+__global__ __launch_bounds__(kWave) void targets_kernel(std::conditional_t<MODE == kStrided, SArgs, Args> a) {
+    constexpr bool STR = MODE == kStrided;
+    constexpr bool VEC = MODE == kVec;
+    using CH = std::conditional_t<STR, SChunk, Chunk>;
     constexpr bool kRho = (TGT == HRL_ALG_VTRACE) || (ADV == HRL_ALG_VTRACE);
     constexpr bool kRet = RETT && (ADV == HRL_ALG_MC);
 
@@ -251,7 +361,10 @@ __global__ __launch_bounds__(kWave) void targets_kernel(Args a) {
     HRL_STAMP(0);
     float boot = 0.f;
     if (active) {
-        boot = a.returns[(b0 + g) * (int64_t)a.retT * C + (int64_t)(a.retT - 1) * C + c];
+        if constexpr (STR)
+            boot = a.returns[(b0 + g) * a.sret.sB + inner_offset(a.sret, a.retT - 1, c, a.K)];
+        else
+            boot = a.returns[(b0 + g) * (int64_t)a.retT * C + (int64_t)(a.retT - 1) * C + c];
     }
 
     Carry s{0.f, 0.f, 0.f, 0.f, 0.f};
@@ -260,17 +373,27 @@ __global__ __launch_bounds__(kWave) void targets_kernel(Args a) {
     // Software pipeline over chunks (walking time backwards): chunk ch's inputs
     // arrive in registers one iteration ahead, so the global-load latency of
     // chunk ch-1 overlaps chunk ch's LDS transpose and recurrence.
-    Chunk cv, cr, cret, crho, ccs;
-    Staged<VEC> sv, sr, sret, srho, scs;
+    CH cv, cr, cret, crho, ccs;
+    Staged<MODE, CH> sv, sr, sret, srho, scs;
     auto setup_and_load = [&](int ch) {
         const int t0 = ch * kTChunk;
         const int tc = min(kTChunk, T - t0);
-        cv.setup(a.values, b0, T, C, t0, tc, ntraj, Lpv);
-        if constexpr (REW) cr.setup(a.rewards, b0, T, C, t0, tc, ntraj, Lpv);
-        if constexpr (kRet) cret.setup(a.returns, b0, T, C, t0, tc, ntraj, Lpv);
-        if constexpr (kRho) {
-            crho.setup(a.rhos, b0, T, a.rhoC, t0, tc, ntraj, Lpr);
-            ccs.setup(a.cs, b0, T, a.rhoC, t0, tc, ntraj, Lpr);
+        if constexpr (STR) {
+            cv.setup(a.values, a.sv, b0, t0, tc, ntraj, Lpv);
+            if constexpr (REW) cr.setup(a.rewards, a.srew, b0, t0, tc, ntraj, Lpv);
+            if constexpr (kRet) cret.setup(a.returns, a.sret, b0, t0, tc, ntraj, Lpv);
+            if constexpr (kRho) {
+                crho.setup(a.rhos, a.srho, b0, t0, tc, ntraj, Lpr);
+                ccs.setup(a.cs, a.scs, b0, t0, tc, ntraj, Lpr);
+            }
+        } else {
+            cv.setup(a.values, b0, T, C, t0, tc, ntraj, Lpv);
+            if constexpr (REW) cr.setup(a.rewards, b0, T, C, t0, tc, ntraj, Lpv);
+            if constexpr (kRet) cret.setup(a.returns, b0, T, C, t0, tc, ntraj, Lpv);
+            if constexpr (kRho) {
+                crho.setup(a.rhos, b0, T, a.rhoC, t0, tc, ntraj, Lpr);
+                ccs.setup(a.cs, b0, T, a.rhoC, t0, tc, ntraj, Lpr);
+            }
         }
         // every input's loads are issued before the first is consumed
         sv.load(cv);
@@ -303,7 +426,17 @@ __global__ __launch_bounds__(kWave) void targets_kernel(Args a) {
         if constexpr (REW) sr.to_lds(cr, t_r);
         if constexpr (kRet) sret.to_lds(cret, t_ret);
         if constexpr (kRho) { srho.to_lds(crho, t_rho); scs.to_lds(ccs, t_cs); }
-        const Chunk out = cv;          // this chunk's output geometry
+        // this chunk's output geometry: the outputs are contiguous whatever the operands' strides
+        auto out_geometry = [&] {
+            if constexpr (STR) {
+                Chunk o;
+                o.setup(a.advantages, b0, T, C, t0, tc, ntraj, Lpv);
+                return o;
+            } else {
+                return cv;
+            }
+        };
+        const Chunk out = out_geometry();
         // the next chunk's loads stay in flight through this chunk (unconditional in this
         // instantiation, so no register phi forces an early wait on them)
         if constexpr (decltype(prefetch)::value) setup_and_load(ch - 1);
@@ -319,8 +452,18 @@ __global__ __launch_bounds__(kWave) void targets_kernel(Args a) {
         HRL_STAMP(3 + 3 * (nchunks - 1 - ch));
 
         const int64_t off = b0 * (int64_t)T * C + (int64_t)t0 * C;
-        if constexpr (TGT != kNone) store_chunk<VEC>(out, t_tgt, a.targets + off);
-        store_chunk<VEC>(out, t_adv, a.advantages + off);
+        if constexpr (STR) {
+            if (a.outVec) {
+                if constexpr (TGT != kNone) store_chunk<true>(out, t_tgt, a.targets + off);
+                store_chunk<true>(out, t_adv, a.advantages + off);
+            } else {
+                if constexpr (TGT != kNone) store_chunk<false>(out, t_tgt, a.targets + off);
+                store_chunk<false>(out, t_adv, a.advantages + off);
+            }
+        } else {
+            if constexpr (TGT != kNone) store_chunk<VEC>(out, t_tgt, a.targets + off);
+            store_chunk<VEC>(out, t_adv, a.advantages + off);
+        }
         HRL_STAMP(4 + 3 * (nchunks - 1 - ch));
     };
     if constexpr (!ONE)
@@ -336,8 +479,9 @@ __global__ __launch_bounds__(kWave) void targets_kernel(Args a) {
 // one step touch the same lines as its other steps', which L1/L2 serve once), the chain runs, and each step's
 // outputs are stored as they are produced.  No LDS, no barrier, ~70 registers: enough waves in flight to hide
 // the HBM latency.  The per-column arithmetic is fused_step's, in recur_chunk's order: bit-identical results.
-template <int TGT, int ADV, bool REW, bool RETT>
-__global__ __launch_bounds__(256) void targets_lane_kernel(Args a) {
+// STR: operands with strides (SArgs): a lane's column is its own address, so the strides are just that address.
+template <int TGT, int ADV, bool REW, bool RETT, bool STR = false>
+__global__ __launch_bounds__(256) void targets_lane_kernel(std::conditional_t<STR, SArgs, Args> a) {
     constexpr bool kRho = (TGT == HRL_ALG_VTRACE) || (ADV == HRL_ALG_VTRACE);
     constexpr bool kRet = RETT && (ADV == HRL_ALG_MC);
     const int C = a.C, T = a.T, G = a.G;
@@ -347,22 +491,40 @@ __global__ __launch_bounds__(256) void targets_lane_kernel(Args a) {
     const int64_t b = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * G + g;
     if (g >= G || b >= a.B) return;            // no barrier below
     const int64_t row = b * (int64_t)T;
-    const float *pv = a.values + row * C + c;
-    const float *pr = REW ? a.rewards + row * C + c : nullptr;
-    const float *pret = kRet ? a.returns + row * C + c : nullptr;
-    const int rc = c / a.rhoDiv;
-    const float *prho = kRho ? a.rhos + row * a.rhoC + rc : nullptr;
-    const float *pcs = kRho ? a.cs + row * a.rhoC + rc : nullptr;
+    const float *pv, *pr = nullptr, *pret = nullptr, *prho = nullptr, *pcs = nullptr;
+    int sv, sr = 0, sret = 0, srho = 0, scs = 0;     // element strides of one time step
     float xv[kTChunk], xr[kTChunk], xrho[kTChunk], xc[kTChunk], xret[kTChunk];
-    const float boot = a.returns[b * (int64_t)a.retT * C + (int64_t)(a.retT - 1) * C + c];
+    float boot;
+    if constexpr (STR) {
+        // element (b, 0, p, k) of each operand; rhos / cs broadcast through their zero strides
+        auto at = [&](const float *p, const Strd &s) { return p + b * s.sB + inner_offset(s, 0, c, a.K); };
+        pv = at(a.values, a.sv); sv = a.sv.sT;
+        if constexpr (REW) { pr = at(a.rewards, a.srew); sr = a.srew.sT; }
+        if constexpr (kRet) { pret = at(a.returns, a.sret); sret = a.sret.sT; }
+        if constexpr (kRho) {
+            prho = at(a.rhos, a.srho); srho = a.srho.sT;
+            pcs = at(a.cs, a.scs); scs = a.scs.sT;
+        }
+        boot = at(a.returns, a.sret)[(a.retT - 1) * a.sret.sT];
+    } else {
+        pv = a.values + row * C + c; sv = C;
+        if constexpr (REW) { pr = a.rewards + row * C + c; sr = C; }
+        if constexpr (kRet) { pret = a.returns + row * C + c; sret = C; }
+        if constexpr (kRho) {
+            const int rc = c / a.rhoDiv;
+            prho = a.rhos + row * a.rhoC + rc; srho = a.rhoC;
+            pcs = a.cs + row * a.rhoC + rc; scs = a.rhoC;
+        }
+        boot = a.returns[b * (int64_t)a.retT * C + (int64_t)(a.retT - 1) * C + c];
+    }
 #pragma unroll
     for (int tt = 0; tt < kTChunk; ++tt) {
         if (tt < T) {
-            xv[tt] = pv[tt * C];
-            xr[tt] = REW ? pr[tt * C] : 0.f;
-            xret[tt] = kRet ? pret[tt * C] : boot;
-            xrho[tt] = kRho ? prho[tt * a.rhoC] : 0.f;
-            xc[tt] = kRho ? pcs[tt * a.rhoC] : 0.f;
+            xv[tt] = pv[tt * sv];
+            xr[tt] = REW ? pr[tt * sr] : 0.f;
+            xret[tt] = kRet ? pret[tt * sret] : boot;
+            xrho[tt] = kRho ? prho[tt * srho] : 0.f;
+            xc[tt] = kRho ? pcs[tt * scs] : 0.f;
         }
     }
     float *ptg = TGT != kNone ? a.targets + row * C + c : nullptr;
@@ -386,8 +548,8 @@ __global__ __launch_bounds__(256) void targets_lane_kernel(Args a) {
 // 2 the lane kernel always, 0 targets_kernel always
 int g_short_form = 1;
 
-template <int TGT, int ADV, bool REW, bool RETT, bool VEC>
-int launch_one(const Args &a, hipStream_t stream) {
+template <int TGT, int ADV, bool REW, bool RETT, int MODE, class A>
+int launch_one(const A &a, hipStream_t stream) {
     constexpr bool kRho = (TGT == HRL_ALG_VTRACE) || (ADV == HRL_ALG_VTRACE);
     constexpr bool kRet = RETT && (ADV == HRL_ALG_MC);
     const int G = a.G;
@@ -399,19 +561,19 @@ int launch_one(const Args &a, hipStream_t stream) {
     const int64_t blocks = (a.B + G - 1) / G;
     if (blocks > 0x7fffffff) return HRL_EINVAL;
     if (a.T <= kTChunk && (g_short_form == 2 || (g_short_form == 1 && a.B * a.C <= 32768))) {
-        Args b = a;
+        A b = a;
         b.G = kWave / a.C;
         const int64_t waves = (a.B + b.G - 1) / b.G;
         const int64_t wgs = (waves + 3) / 4;
         if (wgs > 0x7fffffff) return HRL_EINVAL;
-        hipLaunchKernelGGL((targets_lane_kernel<TGT, ADV, REW, RETT>), dim3((unsigned)wgs), dim3(4 * kWave), 0,
+        hipLaunchKernelGGL((targets_lane_kernel<TGT, ADV, REW, RETT, MODE == kStrided>), dim3((unsigned)wgs), dim3(4 * kWave), 0,
                            stream, b);
     } else {
         if (a.T <= kTChunk)
-            hipLaunchKernelGGL((targets_kernel<TGT, ADV, REW, RETT, VEC, true>), dim3((unsigned)blocks), dim3(kWave),
+            hipLaunchKernelGGL((targets_kernel<TGT, ADV, REW, RETT, MODE, true>), dim3((unsigned)blocks), dim3(kWave),
                                lds, stream, a);
         else
-            hipLaunchKernelGGL((targets_kernel<TGT, ADV, REW, RETT, VEC, false>), dim3((unsigned)blocks), dim3(kWave),
+            hipLaunchKernelGGL((targets_kernel<TGT, ADV, REW, RETT, MODE, false>), dim3((unsigned)blocks), dim3(kWave),
                                lds, stream, a);
     }
     const hipError_t err = hipGetLastError();
@@ -430,20 +592,30 @@ bool vector_ok(const Args &a) {
     return ((a.T * a.C) & 3) == 0 && ((a.T * a.rhoC) & 3) == 0;
 }
 
-template <int TGT, int ADV, bool REW>
-int launch_vec(const Args &a, hipStream_t s) {
+template <int TGT, int ADV, bool REW, class A>
+int launch_vec(const A &a, hipStream_t s) {
     const bool rett = (ADV == HRL_ALG_MC) && a.retT == a.T && a.T > 1;
-    if (vector_ok(a)) return rett ? launch_one<TGT, ADV, REW, true, true>(a, s) : launch_one<TGT, ADV, REW, false, true>(a, s);
-    return rett ? launch_one<TGT, ADV, REW, true, false>(a, s) : launch_one<TGT, ADV, REW, false, false>(a, s);
+    if constexpr (std::is_same_v<A, SArgs>) {
+        // one strided form per algorithm pair (16- or 4-byte loads are its run-time choice), and RETT only where
+        // it changes the kernel (ADV == MC)
+        if constexpr (ADV == HRL_ALG_MC) {
+            if (rett) return launch_one<TGT, ADV, REW, true, kStrided>(a, s);
+        }
+        return launch_one<TGT, ADV, REW, false, kStrided>(a, s);
+    } else {
+        if (vector_ok(a))
+            return rett ? launch_one<TGT, ADV, REW, true, kVec>(a, s) : launch_one<TGT, ADV, REW, false, kVec>(a, s);
+        return rett ? launch_one<TGT, ADV, REW, true, kScalar>(a, s) : launch_one<TGT, ADV, REW, false, kScalar>(a, s);
+    }
 }
 
-template <int TGT, int ADV>
-int launch_flags(const Args &a, hipStream_t s) {
+template <int TGT, int ADV, class A>
+int launch_flags(const A &a, hipStream_t s) {
     return a.rewards != nullptr ? launch_vec<TGT, ADV, true>(a, s) : launch_vec<TGT, ADV, false>(a, s);
 }
 
-template <int TGT>
-int launch_adv(int adv, const Args &a, hipStream_t s) {
+template <int TGT, class A>
+int launch_adv(int adv, const A &a, hipStream_t s) {
     switch (adv) {
         case HRL_ALG_MC: return launch_flags<TGT, HRL_ALG_MC>(a, s);
         case HRL_ALG_TD: return launch_flags<TGT, HRL_ALG_TD>(a, s);
@@ -453,7 +625,8 @@ int launch_adv(int adv, const Args &a, hipStream_t s) {
     }
 }
 
-int dispatch(int tgt, int adv, const Args &a, hipStream_t s) {
+template <class A>
+int dispatch(int tgt, int adv, const A &a, hipStream_t s) {
     switch (tgt) {
         case kNone: return launch_adv<kNone>(adv, a, s);
         case HRL_ALG_TD: return launch_adv<HRL_ALG_TD>(adv, a, s);
@@ -464,6 +637,17 @@ int dispatch(int tgt, int adv, const Args &a, hipStream_t s) {
 }
 
 bool valid_alg(int alg) { return alg >= HRL_ALG_MC && alg <= HRL_ALG_VTRACE; }
+
+// Waves per launch: a wave's trajectories are walked by one serial chain, so at small B
+// spread them over at least ~1024 waves (one per SIMD) instead of filling every lane.
+// G stays a multiple of 4 (or 64 / C itself), so every wave's first trajectory starts
+// 16-byte aligned whenever the tensors are (the float4 path's precondition).
+int trajectories_per_wave(int64_t B, int C) {
+    const int gmax = kWave / C;
+    int g = gmax < 4 ? gmax : 4;
+    while (g * 2 <= gmax && B / (g * 2) >= 1024) g *= 2;
+    return g;
+}
 
 int prepare(int target_alg, int adv_alg, const float *values, const float *returns, const float *rewards,
             const float *rhos, const float *cs, int64_t B, int64_t T, int64_t C, int64_t ret_T,
@@ -486,15 +670,114 @@ int prepare(int target_alg, int adv_alg, const float *values, const float *retur
     a.targets = targets; a.advantages = advantages;
     a.B = B; a.T = (int)T; a.C = (int)C; a.retT = (int)ret_T; a.rhoC = (int)rho_C; a.rhoDiv = (int)rho_div;
     a.k = make_coef(lmb, gamma);
-    // Waves per launch: a wave's trajectories are walked by one serial chain, so at small B
-    // spread them over at least ~1024 waves (one per SIMD) instead of filling every lane.
+    a.G = trajectories_per_wave(B, a.C);
+    const int tgt = (targets == nullptr || target_alg == HRL_ALG_MC) ? kNone : target_alg;
+    return dispatch(tgt, adv_alg, a, static_cast<hipStream_t>(stream));
+}
+
+// ---- hrl_compute_targets_strided: operands given as (B, T, P, K) views with element strides
+
+struct HostStrides {
+    int64_t sB, sT, sP, sK;
+};
+
+// The strides of an operand of extents (B, Tx, P, K), with every axis of extent 1 (never stepped along) set to 0.
+HostStrides normalised(const int64_t *row, int64_t B, int64_t Tx, int64_t P, int64_t K) {
+    return {B > 1 ? row[0] : 0, Tx > 1 ? row[1] : 0, P > 1 ? row[2] : 0, K > 1 ? row[3] : 0};
+}
+
+// The operand is a C-contiguous (Tx, Px, Kx) block per trajectory, where (Px, Kx) is (1, 1), (P, 1) or (P, K) and
+// the axes outside the block are broadcast (stride 0).  `whole`: the trajectories are contiguous too.
+bool block_layout(const HostStrides &s, int64_t B, int64_t Tx, int64_t P, int64_t K, int64_t Px, int64_t Kx,
+                  bool whole) {
+    if (Kx == 1 ? s.sK != 0 : (K > 1 && s.sK != 1)) return false;
+    if (Px == 1 ? s.sP != 0 : (P > 1 && s.sP != Kx)) return false;
+    if (Tx > 1 && s.sT != Px * Kx) return false;
+    return !whole || B == 1 || s.sB == Tx * Px * Kx;
+}
+
+// Largest element offset of the operand: the inner part must fit 31 bits (the kernels add it as an int to a
+// 64-bit trajectory base), the whole must not wrap a 64-bit byte offset.
+bool offsets_ok(const HostStrides &s, int64_t B, int64_t Tx, int64_t P, int64_t K) {
+    const int64_t lim = (int64_t)1 << 31;
+    if (s.sT >= lim || s.sP >= lim || s.sK >= lim) return false;
+    const int64_t inner = (Tx - 1) * s.sT + (P - 1) * s.sP + (K - 1) * s.sK;   // < 2^24 * 2^31 + 2 * 2^6 * 2^31
+    if (inner >= lim) return false;
+    const unsigned __int128 top = (unsigned __int128)(B - 1) * (unsigned __int128)s.sB + (unsigned __int128)inner;
+    return top < ((unsigned __int128)1 << 60);
+}
+
+Strd device_strides(const HostStrides &s, int64_t Px, int64_t Kx, bool canon) {
+    Strd d;
+    d.sB = s.sB; d.sT = (int)s.sT; d.sP = (int)s.sP; d.sK = (int)s.sK;
+    d.Px = (int)Px; d.Kx = (int)Kx; d.canon = canon ? 1 : 0;
+    return d;
+}
+
+int prepare_strided(int target_alg, int adv_alg, const float *values, const float *returns, const float *rewards,
+                    const float *rhos, const float *cs, const int64_t *strides, int64_t B, int64_t T, int64_t P,
+                    int64_t K, int64_t ret_T, double lmb, double gamma, float *targets, float *advantages,
+                    void *stream) {
+    if (!valid_alg(target_alg) || !valid_alg(adv_alg) || strides == nullptr) return HRL_EINVAL;
+    if (P < 1 || K < 1 || P > kWave || K > kWave || P * K > kWave) return HRL_EINVAL;
+    const int64_t C = P * K;
+    if (B < 0 || T < 1 || T > (1 << 24)) return HRL_EINVAL;
+    if (ret_T != 1 && ret_T != T) return HRL_EINVAL;
+    if (target_alg == HRL_ALG_MC && targets != nullptr) return HRL_EINVAL;
+    const float *ops[5] = {values, returns, rewards, rhos, cs};
+    for (int i = 0; i < 5; ++i) {
+        if (ops[i] == nullptr) continue;        // the strides row of a NULL operand is ignored
+        for (int j = 0; j < 4; ++j)
+            if (strides[4 * i + j] < 0) return HRL_EINVAL;
+    }
+    const bool need_rho = target_alg == HRL_ALG_VTRACE || adv_alg == HRL_ALG_VTRACE;
+    if (B == 0) return HRL_OK;  // empty batch: nothing to read or write (data pointers may be NULL)
+    if (!values || !returns || !advantages || (need_rho && (!rhos || !cs))) return HRL_EINVAL;
+    if (B * T * C > (int64_t)1 << 40 || T * C * kWave >= ((int64_t)1 << 31)) return HRL_EINVAL;
+
+    const HostStrides zero = {0, 0, 0, 0};
+    const HostStrides hv = normalised(strides, B, T, P, K);
+    const HostStrides hret = normalised(strides + 4, B, ret_T, P, K);
+    const HostStrides hrew = rewards ? normalised(strides + 8, B, T, P, K) : zero;
+    const HostStrides hrho = need_rho ? normalised(strides + 12, B, T, P, K) : zero;
+    const HostStrides hcs = need_rho ? normalised(strides + 16, B, T, P, K) : zero;
+    if (!offsets_ok(hv, B, T, P, K) || !offsets_ok(hret, B, ret_T, P, K) || !offsets_ok(hrew, B, T, P, K) ||
+        !offsets_ok(hrho, B, T, P, K) || !offsets_ok(hcs, B, T, P, K))
+        return HRL_EINVAL;
+
+    // The rho tile: the narrowest of (1, 1), (P, 1), (P, K) that both rhos and cs broadcast from.
+    int64_t rP = 1, rK = 1;
+    if (need_rho) {
+        if (hrho.sK != 0 || hcs.sK != 0) { rP = P; rK = K; }
+        else if (hrho.sP != 0 || hcs.sP != 0) { rP = P; }
+    }
+
+    // C-contiguous operands (and a rho layout the contiguous entry points know): the very kernels they launch.
+    if (block_layout(hv, B, T, P, K, P, K, true) && block_layout(hret, B, ret_T, P, K, P, K, true) &&
+        (!rewards || block_layout(hrew, B, T, P, K, P, K, true)) &&
+        (!need_rho || (block_layout(hrho, B, T, P, K, rP, rK, true) && block_layout(hcs, B, T, P, K, rP, rK, true))))
+        return prepare(target_alg, adv_alg, values, returns, rewards, need_rho ? rhos : nullptr,
+                       need_rho ? cs : nullptr, B, T, C, ret_T, rP * rK, C / (rP * rK), lmb, gamma, targets,
+                       advantages, stream);
+
+    SArgs a;
+    a.values = values; a.returns = returns; a.rewards = rewards; a.rhos = rhos; a.cs = cs;
+    a.targets = targets; a.advantages = advantages;
+    a.B = B; a.T = (int)T; a.C = (int)C; a.retT = (int)ret_T; a.rhoC = (int)(rP * rK); a.rhoDiv = (int)(C / (rP * rK));
+    a.k = make_coef(lmb, gamma);
+    a.G = trajectories_per_wave(B, a.C);
+    a.K = (int)K;
+    a.sv = device_strides(hv, P, K, block_layout(hv, B, T, P, K, P, K, false));
+    a.sret = device_strides(hret, P, K, block_layout(hret, B, ret_T, P, K, P, K, false));
+    a.srew = device_strides(hrew, P, K, block_layout(hrew, B, T, P, K, P, K, false));
+    a.srho = device_strides(hrho, rP, rK, block_layout(hrho, B, T, P, K, rP, rK, false));
+    a.scs = device_strides(hcs, rP, rK, block_layout(hcs, B, T, P, K, rP, rK, false));
+    // 16-byte stores of the contiguous outputs: aligned tensors, and every wave's chunks at whole float4s
     {
-        // G stays a multiple of 4 (or 64 / C itself), so every wave's first trajectory starts
-        // 16-byte aligned whenever the tensors are (the float4 path's precondition).
-        const int gmax = kWave / a.C;
-        int g = gmax < 4 ? gmax : 4;
-        while (g * 2 <= gmax && B / (g * 2) >= 1024) g *= 2;
-        a.G = g;
+        auto aligned = [](const void *p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+        const int64_t row = T * C;
+        a.outVec = aligned(targets) && aligned(advantages) &&
+                   (T <= kTChunk ? ((a.G * row) & 3) == 0 : (row & 3) == 0);
     }
     const int tgt = (targets == nullptr || target_alg == HRL_ALG_MC) ? kNone : target_alg;
     return dispatch(tgt, adv_alg, a, static_cast<hipStream_t>(stream));
@@ -510,7 +793,7 @@ int hrl_debug_set_stamps_targets(void *buf) {
 }
 #endif
 
-int hrl_abi_version(void) { return 29; }
+int hrl_abi_version(void) { return 30; }
 
 int hrl_targets_set_short_form(int form) {
     const int prev = g_short_form;
@@ -539,6 +822,14 @@ int hrl_compute_targets_fused(int target_alg, int adv_alg, const float *values, 
                               double gamma, float *targets, float *advantages, void *stream) {
     return prepare(target_alg, adv_alg, values, returns, rewards, rhos, cs, B, T, C, ret_T, rho_C, rho_div, lmb,
                    gamma, targets, advantages, stream);
+}
+
+int hrl_compute_targets_strided(int target_alg, int adv_alg, const float *values, const float *returns,
+                                const float *rewards, const float *rhos, const float *cs, const int64_t *strides,
+                                int64_t B, int64_t T, int64_t P, int64_t K, int64_t ret_T, double lmb, double gamma,
+                                float *targets, float *advantages, void *stream) {
+    return prepare_strided(target_alg, adv_alg, values, returns, rewards, rhos, cs, strides, B, T, P, K, ret_T, lmb,
+                           gamma, targets, advantages, stream);
 }
 
 }  // extern "C"

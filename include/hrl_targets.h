@@ -9,7 +9,9 @@
  *  :43-58 vtrace) and its two/four call sites in compute_loss
  * (handyrl/train.py:245-253).
  *
- * Conventions (all pointers are DEVICE pointers, fp32, C-contiguous):
+ * Conventions (all pointers are DEVICE pointers, fp32; C-contiguous for
+ * hrl_compute_target and hrl_compute_targets_fused, any non-negative strides
+ * for hrl_compute_targets_strided, see there):
  *   values   (B, T, C)       C = P*K value columns (P players x K value dims)
  *   returns  (B, ret_T, C)   ret_T in {1, T}; TD/UPGO/VTRACE read only the
  *                            last time step (the bootstrap), MC reads all
@@ -91,6 +93,51 @@ int hrl_compute_targets_fused(int target_alg, int adv_alg,
                               double lmb, double gamma,
                               float *targets, float *advantages,
                               void *stream);
+
+/*
+ * The fused form for operands that are VIEWS: a time window of a longer
+ * buffer, a time-major buffer seen as (B, T, ...), a column slice, an outcome
+ * expanded over value dimensions.  Nothing is copied or allocated.
+ *
+ * Every operand has the logical shape (B, T, P, K) (returns: (B, ret_T, P, K))
+ * with C = P*K <= 64 value columns, and is addressed as
+ *     base[b*sB + t*sT + p*sP + k*sK]
+ * strides: HOST array of 5 x 4 int64 ELEMENT strides (sB, sT, sP, sK) for
+ *   values, returns, rewards, rhos, cs, in that order; read before the call
+ *   returns.  A stride of 0 broadcasts along that axis; the stride of an axis
+ *   of extent 1 is ignored, as is the whole row of a NULL operand.  Strides
+ *   are non-negative.
+ * The strides alone say how rhos / cs broadcast (this replaces rho_C and
+ * rho_div), and rhos and cs may differ: (B,T,1,1), (B,T,P,1), (B,T,1,K),
+ * (B,1,P,1) over time, ... all pass as stride-0 axes.
+ * target_alg == adv_alg gives the single-algorithm form of hrl_compute_target.
+ * Outputs are C-contiguous (B, T, P, K) and MUST NOT alias any input (an
+ * input element may be read after the output element of another trajectory
+ * has been written).
+ *
+ * Addressing: the trajectory term b*sB is applied in 64-bit arithmetic, so
+ * sB may be of any size; the kernels add the inner term t*sT + p*sP + k*sK
+ * as a 32-bit integer, so a call whose largest inner offset
+ *     (T-1)*sT + (P-1)*sP + (K-1)*sK
+ * (ret_T-1 for returns) reaches 2^31 elements, or whose largest offset
+ * reaches 2^60 elements, is rejected with HRL_EINVAL.
+ *
+ * HRL_EINVAL, before any HIP call, for: NULL strides; a negative stride;
+ * P < 1, K < 1 or P*K > 64; and what the entry points above reject (unknown
+ * algorithm, T < 1, ret_T not in {1, T}, MC with targets, V-trace without
+ * rhos / cs, a NULL values / returns / advantages).  B == 0 returns HRL_OK
+ * and touches nothing.
+ * A call whose operands are all C-contiguous, with rhos and cs both
+ * (B,T,1,1), both (B,T,P,1) or both (B,T,P,K), launches the same kernel as
+ * hrl_compute_targets_fused.
+ */
+int hrl_compute_targets_strided(int target_alg, int adv_alg,
+                                const float *values, const float *returns, const float *rewards,
+                                const float *rhos, const float *cs, const int64_t *strides,
+                                int64_t B, int64_t T, int64_t P, int64_t K, int64_t ret_T,
+                                double lmb, double gamma,
+                                float *targets, float *advantages,
+                                void *stream);
 
 #ifdef __cplusplus
 }
