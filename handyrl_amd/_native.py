@@ -259,7 +259,33 @@ SIGNATURES = {
                                                       ctypes.c_void_p, _i64, ctypes.c_int, _f32p, _f32p,
                                                       ctypes.c_void_p, ctypes.c_void_p, _i64, _f32p, _f32p,
                                                       ctypes.c_void_p]),
+    'hrl_replay_gather': (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p, _i64, _i64, ctypes.c_void_p, ctypes.c_void_p]),
+    'hrl_replay_draw': (ctypes.c_int, [_f32p, _i64, _i64, _i64, _i64, _i64, ctypes.c_void_p, _i64, _i64,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
 }
+
+# include/hrl_replay.h
+REPLAY_MAX_LEAVES = 8
+REPLAY_U8, REPLAY_F32 = 0, 1
+REPLAY_LAYOUT = {'mover_records': 0, 'players_all': 1, 'players_solo': 2, 'players_mover': 3}
+
+
+class ReplayRing(ctypes.Structure):
+    """struct hrl_replay_ring"""
+    _fields_ = ([('N', _i64), ('Tm', _i64), ('P', _i64), ('A', _i64), ('nleaves', ctypes.c_int32),
+                 ('obs_type', ctypes.c_int32 * REPLAY_MAX_LEAVES), ('obs_width', _i64 * REPLAY_MAX_LEAVES),
+                 ('obs', ctypes.c_void_p * REPLAY_MAX_LEAVES)]
+                + [(k, ctypes.c_void_p) for k in ('policy', 'amask', 'action', 'value', 'reward', 'ret', 'length',
+                                                  'outcome', 'turn', 'tmask', 'omask')])
+
+
+class ReplayBatch(ctypes.Structure):
+    """struct hrl_replay_batch"""
+    _fields_ = ([('obs', ctypes.c_void_p * REPLAY_MAX_LEAVES)]
+                + [(k, ctypes.c_void_p) for k in ('policy', 'amask', 'action', 'value', 'outcome', 'reward', 'ret',
+                                                  'episode_mask', 'turn_mask', 'observation_mask', 'progress')])
+
 
 ABI_VERSION = 30
 

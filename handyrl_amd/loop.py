@@ -43,6 +43,7 @@ class SelfPlayTrainer:
         self.rng = torch.Generator(device=device).manual_seed(seed)
         self.episodes = 0
         self.steps = 0
+        self._batch = None   # the one batch every step gathers into (train_steps)
 
     def generate(self):
         ep = self.gen.generate(generator=self.rng)
@@ -52,8 +53,13 @@ class SelfPlayTrainer:
 
     def train_steps(self, n):
         B, T = self.args['batch_size'], self.args['forward_steps']
+        if self._batch is None:
+            self._batch = self.replay.alloc_batch(B, T)
         for _ in range(n):
-            batch = self.replay.sample(B, T, generator=self.rng)
+            # One batch for every step: the gather writes it in place and a graph learner captures it as its
+            # static input, so no step copies a batch.  Reuse is safe by stream order: the gather is enqueued on
+            # the stream on which the previous step, the last reader of these tensors, ran.
+            batch = self.replay.sample(B, T, generator=self.rng, out=self._batch)
             self.learner.step(batch, self.hidden)
             self.steps += 1
 

@@ -28,7 +28,10 @@ written) with the actors and the learner on the GPU:
   reference's workers hold the latest published model), recency-weighted
   replay of ``maximum_episodes``; training starts once ``minimum_episodes``
   are stored.  The three counts are global, as in the reference: under
-  torchrun each rank generates and keeps 1/world of them;
+  torchrun each rank generates and keeps 1/world of them.  The device
+  replays assemble every batch in one launch into one reused batch;
+  ``window_draw: inverse`` in train_args also draws the windows in one
+  launch (default ``multinomial``: the seeded ``sample_windows`` stream);
 * ``trainer.Trainer`` runs the epoch (its lr / data-count EMA schedule is the
   reference's, train.py:394-401) for ``steps_per_epoch`` steps (default: the
   epoch's new env-steps of ALL ranks over the global batch world*B*T, at
@@ -84,9 +87,17 @@ class ReplayBatcher:
 
     def __init__(self, replay, args, generator):
         self.replay, self.args, self.g = replay, args, generator
+        self._out = None
 
     def batch(self):
-        return self.replay.sample(self.args['batch_size'], self.args['forward_steps'], generator=self.g)
+        B, T = self.args['batch_size'], self.args['forward_steps']
+        if not hasattr(self.replay, 'alloc_batch'):   # the host replay assembles a fresh batch
+            return self.replay.sample(B, T, generator=self.g)
+        # One batch for every step, gathered in place (a graph learner keeps it as its static input).  Reuse is
+        # safe by stream order: the gather runs on the stream of the step that last read these tensors.
+        if self._out is None:
+            self._out = self.replay.alloc_batch(B, T)
+        return self.replay.sample(B, T, generator=self.g, out=self._out)
 
 
 def _per_rank(n, world):
@@ -136,10 +147,11 @@ def train_main(args, device=None, loss_fn=None, model_dir='models', log=print):
         if per_player:
             replay = PlayerReplay(maximum, batched.MAX_PLIES, batched.OBS_SHAPE, batched.A, batched.P, device,
                                   maximum_episodes=maximum, obs_dtype=torch.uint8, solo=not tbt,
-                                  mover=tbt and not observe)
+                                  mover=tbt and not observe, draw=targs.get('window_draw', 'multinomial'))
         else:
             replay = DeviceReplay(maximum, batched.MAX_PLIES, batched.OBS_SHAPE, batched.A, batched.P, device,
-                                  maximum_episodes=maximum, obs_dtype=torch.uint8)
+                                  maximum_episodes=maximum, obs_dtype=torch.uint8,
+                                  draw=targs.get('window_draw', 'multinomial'))
 
         def play():
             ep = gen.generate(generator=rng)

@@ -36,6 +36,7 @@ players sampled, per-player records with the turn and observation masks;
 """
 
 import contextlib
+import ctypes
 
 import numpy as np
 import torch
@@ -606,16 +607,31 @@ class DeviceGenerator:
         return out
 
 
+# True: on a GPU ``gather`` is the one launch of hrl_replay_gather (include/hrl_replay.h) instead of the torch ops
+# below, which stay as the CPU path and as the formulation the kernel is tested against (bit-identical).
+FUSED_GATHER = True
+
+_DRAWS = ('multinomial', 'inverse')
+
+
 class DeviceReplay:
     """Ring buffer of episodes in HBM; windows gathered into the make_batch layout.
 
     ``obs_shape`` is a shape or {name: shape}; ``obs_dtype`` lets binary
     observation planes (TicTacToe, Geister) live in HBM as uint8, a quarter
-    of the bytes, widened to fp32 by the gather.
+    of the bytes, widened to fp32 by the gather.  ``draw``: how ``sample``
+    picks its windows, ``'multinomial'`` (``sample_windows``) or ``'inverse'``
+    (``draw_windows``: one uniform draw and one launch).
     """
 
+    solo = mover = False
+    _lead = 2    # leading axes of a record, (N, Tm); PlayerReplay: (N, Tm, P)
+
     def __init__(self, capacity, max_plies, obs_shape, A, P, device, maximum_episodes=None,
-                 obs_dtype=torch.float32):
+                 obs_dtype=torch.float32, draw='multinomial'):
+        if draw not in _DRAWS:
+            raise ValueError('draw must be one of %s, not %r' % (_DRAWS, draw))
+        self.draw = draw
         self.N, self.Tm, self.P, self.device = capacity, max_plies, P, device
         self.maximum_episodes = maximum_episodes or capacity
         f = dict(device=device)
@@ -667,8 +683,134 @@ class DeviceReplay:
         start = torch.minimum((u * cand).long(), cand - 1)
         return slots, start
 
-    def gather(self, slots, start, T):
-        """make_batch-layout batch of the windows [start, start+T) of episodes `slots` (train.py:33-133)."""
+    def draw_windows(self, B, T, generator=None, u=None):
+        """(slot, start, player) of B windows from ``u`` (3, B) uniforms in [0, 1) (drawn here when None), by the
+        integer rule of hrl_replay_draw (include/hrl_replay.h): the inverse of the cumulative integer weights
+        M - (n-1-i) of ``sample_windows``' distribution.  On a GPU one ``torch.rand`` and one launch; elsewhere the
+        torch formulation of the same rule, which the kernel equals exactly."""
+        if self.count < 1:
+            raise ValueError('draw_windows on an empty replay')
+        if u is None:
+            u = torch.rand(3, B, device=self.device, generator=generator)
+        if u.shape != (3, B) or u.dtype != torch.float32:
+            raise ValueError('u must be (3, %d) float32' % B)
+        M, P = int(self.maximum_episodes), self.P
+        if u.is_cuda:
+            from . import _native
+            idx = torch.empty(3, B, dtype=torch.long, device=u.device)
+            u = u.contiguous()
+            w = B * 8
+            _native.check(_native.load().hrl_replay_draw(
+                _native.ptr(u), B, self.ptr, self.count, self.N, M, _native.ptr(self.length), T, P,
+                idx.data_ptr(), idx.data_ptr() + w, idx.data_ptr() + 2 * w, _native.stream_of(u.device)),
+                'hrl_replay_draw')
+            return idx[0], idx[1], idx[2]
+        n = min(self.count, M)
+        i = torch.arange(n, device=u.device)
+        cum = (i + 1) * (M - n + 1) + i * (i + 1) // 2
+        total = n * (M - n + 1) + (n - 1) * n // 2
+        x = torch.floor(u[0].double() * float(total)).long()
+        pick = torch.searchsorted(cum, x, right=True).clamp_(max=n - 1)
+        slots = (self.ptr - n + pick) % self.N
+        cand = 1 + torch.clamp(self.length[slots] - T, min=0)
+        start = torch.minimum((u[1] * cand).long(), cand - 1)
+        players = torch.clamp((u[2] * float(P)).long(), max=P - 1)
+        return slots, start, players
+
+    def _player_axes(self, solo, mover):
+        """(Pm, Pn): the player axis of observation / policy / action_mask / action, and of the other fields."""
+        return 1, self.P
+
+    def _batch_spec(self, B, T, Pm, Pn):
+        """{key: shape} of a batch; 'observation': the shapes of its leaves, in ``_leaves`` order."""
+        A = self.policy.shape[-1]
+        return {'observation': [(B, T, Pm) + tuple(o.shape[self._lead:]) for o in _leaves(self.obs)],
+                'policy': (B, T, Pm, A), 'value': (B, T, Pn, 1), 'action': (B, T, Pm, 1),
+                'outcome': (B, 1, Pn, 1), 'reward': (B, T, Pn, 1), 'return': (B, T, Pn, 1),
+                'episode_mask': (B, T, 1, 1), 'turn_mask': (B, T, Pn, 1), 'observation_mask': (B, T, Pn, 1),
+                'action_mask': (B, T, Pm, A), 'progress': (B, T, 1)}
+
+    def _alloc_spec(self, spec):
+        f = dict(device=self.policy.device)
+        out = {k: torch.empty(s, dtype=torch.long if k == 'action' else torch.float32, **f)
+               for k, s in spec.items() if k != 'observation'}
+        shapes = iter(spec['observation'])
+        out['observation'] = map_r(self.obs, lambda o: torch.empty(next(shapes), **f))
+        return out
+
+    def alloc_batch(self, B, T):
+        """A batch dict for ``gather(..., out=)`` / ``sample(..., out=)`` that the caller keeps and reuses."""
+        return self._alloc_spec(self._batch_spec(B, T, *self._player_axes(self.solo, self.mover)))
+
+    def _gather_native(self, slots, start, T, players, mover, out):
+        """hrl_replay_gather: one launch fills ``out`` (allocated here when None); no torch op on the batch."""
+        from . import _native
+        B = slots.shape[0]
+        per_player = self._lead == 3
+        Pm, Pn = self._player_axes(players is not None, mover)
+        spec = self._batch_spec(B, T, Pm, Pn)
+        if out is None:
+            out = self._alloc_spec(spec)
+        src, dst, shapes = _leaves(self.obs), _leaves(out['observation']), spec['observation']
+        if len(src) > _native.REPLAY_MAX_LEAVES:
+            raise ValueError('hrl_replay_gather takes at most %d observation leaves' % _native.REPLAY_MAX_LEAVES)
+        if len(dst) != len(src):
+            raise ValueError("out['observation'] does not have the replay's leaves")
+        for name, t, shape, dtype in ([(k, out[k], spec[k], torch.long if k == 'action' else torch.float32)
+                                       for k in spec if k != 'observation']
+                                      + [('observation', t, s, torch.float32) for t, s in zip(dst, shapes)]):
+            if tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError('out[%r]: expected a contiguous %s GPU tensor of shape %s, got %s %s'
+                                 % (name, dtype, tuple(shape), t.dtype, tuple(t.shape)))
+        for name, t in (('slots', slots), ('start', start), ('players', players)):
+            if t is not None and (t.dtype != torch.long or t.shape != (B,) or not t.is_contiguous() or not t.is_cuda):
+                raise ValueError('%s must be a contiguous (B,) int64 GPU tensor' % name)
+        ring = _native.ReplayRing()
+        ring.N, ring.Tm, ring.P, ring.A, ring.nleaves = self.N, self.Tm, self.P, self.policy.shape[-1], len(src)
+        for l, o in enumerate(src):
+            if o.dtype not in (torch.uint8, torch.bool, torch.float32):
+                raise ValueError('observation records are uint8, bool or float32, not %s' % o.dtype)
+            ring.obs[l] = o.data_ptr()
+            ring.obs_type[l] = _native.REPLAY_F32 if o.dtype == torch.float32 else _native.REPLAY_U8
+            ring.obs_width[l] = int(np.prod(o.shape[self._lead:], dtype=np.int64))
+        for k in ('policy', 'amask', 'action', 'value', 'reward', 'ret', 'length', 'outcome'):
+            setattr(ring, k, getattr(self, k).data_ptr())
+        if per_player:
+            ring.tmask, ring.omask = self.tmask.data_ptr(), self.omask.data_ptr()
+            layout = 'players_mover' if mover else ('players_all' if players is None else 'players_solo')
+        else:
+            ring.turn = self.turn.data_ptr()
+            layout = 'mover_records'
+        batch = _native.ReplayBatch()
+        for l, t in enumerate(dst):
+            batch.obs[l] = t.data_ptr()
+        for k, key in (('policy', 'policy'), ('amask', 'action_mask'), ('action', 'action'), ('value', 'value'),
+                       ('outcome', 'outcome'), ('reward', 'reward'), ('ret', 'return'),
+                       ('episode_mask', 'episode_mask'), ('turn_mask', 'turn_mask'),
+                       ('observation_mask', 'observation_mask'), ('progress', 'progress')):
+            setattr(batch, k, out[key].data_ptr())
+        _native.check(_native.load().hrl_replay_gather(
+            _native.REPLAY_LAYOUT[layout], ctypes.byref(ring), _native.ptr(slots), _native.ptr(start),
+            _native.ptr(players), B, T, ctypes.byref(batch), _native.stream_of(slots.device)), 'hrl_replay_gather')
+        return out
+
+    @staticmethod
+    def _fill(out, batch):
+        """The CPU / torch path of ``out=``: copy the formulation's result into the caller's tensors."""
+        if out is None:
+            return batch
+        for k, v in batch.items():
+            bimap_r(out[k], v, lambda dst, s: dst.copy_(s))
+        return out
+
+    def gather(self, slots, start, T, out=None):
+        """make_batch-layout batch of the windows [start, start+T) of episodes `slots` (train.py:33-133).
+        ``out``: a batch dict (``alloc_batch``) that is filled and returned."""
+        if FUSED_GATHER and self.policy.is_cuda:
+            return self._gather_native(slots, start, T, None, False, out)
+        return self._fill(out, self._gather_torch(slots, start, T))
+
+    def _gather_torch(self, slots, start, T):
         B, P, dev = slots.shape[0], self.P, self.device
         t = start.view(-1, 1) + torch.arange(T, device=dev).view(1, -1)      # (B, T)
         length = self.length[slots].view(-1, 1)
@@ -702,9 +844,12 @@ class DeviceReplay:
             'progress': progress.unsqueeze(-1).contiguous(),
         }
 
-    def sample(self, B, T, generator=None):
-        slots, start = self.sample_windows(B, T, generator)
-        return self.gather(slots, start, T)
+    def sample(self, B, T, generator=None, out=None):
+        if self.draw == 'inverse':
+            slots, start, _ = self.draw_windows(B, T, generator)
+        else:
+            slots, start = self.sample_windows(B, T, generator)
+        return self.gather(slots, start, T, out=out)
 
 
 class PlayerReplay(DeviceReplay):
@@ -717,8 +862,13 @@ class PlayerReplay(DeviceReplay):
     action mask from each ply's first turn player and the rest per player, as make_batch's first branch does
     (train.py:62-66)."""
 
+    _lead = 3
+
     def __init__(self, capacity, max_plies, obs_shape, A, P, device, maximum_episodes=None,
-                 obs_dtype=torch.float32, solo=False, mover=False):
+                 obs_dtype=torch.float32, solo=False, mover=False, draw='multinomial'):
+        if draw not in _DRAWS:
+            raise ValueError('draw must be one of %s, not %r' % (_DRAWS, draw))
+        self.draw = draw
         self.solo, self.mover = bool(solo), bool(mover)
         self.N, self.Tm, self.P, self.device = capacity, max_plies, P, device
         self.maximum_episodes = maximum_episodes or capacity
@@ -749,11 +899,21 @@ class PlayerReplay(DeviceReplay):
         self.ptr = (self.ptr + E) % self.N
         self.count = min(self.count + E, self.N)
 
-    def gather(self, slots, start, T, players=None, mover=None):
+    def _player_axes(self, solo, mover):
+        Pn = 1 if solo else self.P
+        return (1 if mover else Pn), Pn
+
+    def gather(self, slots, start, T, players=None, mover=None, out=None):
         """make_batch of the windows [start, start+T) of episodes ``slots`` over every player, or over one
         player per window (``players`` (B,) long); ``mover`` (default: the replay's): observation, policy, action
-        and action mask of each ply's first turn player."""
+        and action mask of each ply's first turn player.  ``out``: a batch dict (``alloc_batch``) that is filled
+        and returned."""
         mover = self.mover if mover is None else mover
+        if FUSED_GATHER and self.policy.is_cuda:
+            return self._gather_native(slots, start, T, players, bool(mover), out)
+        return self._fill(out, self._gather_torch(slots, start, T, players, mover))
+
+    def _gather_torch(self, slots, start, T, players, mover):
         B, dev = slots.shape[0], self.device
         t = start.view(-1, 1) + torch.arange(T, device=dev).view(1, -1)      # (B, T)
         length = self.length[slots].view(-1, 1)
@@ -799,11 +959,15 @@ class PlayerReplay(DeviceReplay):
             'progress': progress.unsqueeze(-1).contiguous(),
         }
 
-    def sample(self, B, T, generator=None):
+    def sample(self, B, T, generator=None, out=None):
         """B windows; solo replays: one uniformly chosen player per window (train.py:55-56)."""
-        slots, start = self.sample_windows(B, T, generator)
-        players = torch.randint(self.P, (B,), device=self.device, generator=generator) if self.solo else None
-        return self.gather(slots, start, T, players)
+        if self.draw == 'inverse':
+            slots, start, players = self.draw_windows(B, T, generator)
+            players = players if self.solo else None
+        else:
+            slots, start = self.sample_windows(B, T, generator)
+            players = torch.randint(self.P, (B,), device=self.device, generator=generator) if self.solo else None
+        return self.gather(slots, start, T, players, out=out)
 
 
 def player_episodes_to_wire(ep, compress_steps=4):

@@ -140,6 +140,15 @@ def split_torus_tower(net, on=True):
         torus[0].tower_split = (len(torus) + 1) // 2 if on else None
 
 
+def _same_tensors(a, b):
+    """Two batch structures hold the very same tensor objects (identity, no device work)."""
+    if a is b:
+        return True
+    if isinstance(a, dict):
+        return isinstance(b, dict) and a.keys() == b.keys() and all(_same_tensors(v, b[k]) for k, v in a.items())
+    return False
+
+
 class LearnerStep:
     def __init__(self, net, args, device, lr=None, graph=False, reduce_group=None, world_size=1,
                  bucket_bytes=256 * 1024, hip_layers=True, loss_fn=None, segment_backward=True):
@@ -385,7 +394,9 @@ class LearnerStep:
             if self._graph is None:
                 self._capture(batch, hidden)
             else:
-                if batch is not self._static:
+                # a batch made of the static tensors themselves (a replay that gathers into them, out=) is
+                # already in place, whatever dict holds it
+                if not _same_tensors(batch, self._static):
                     self.load_batch(batch)
                 if hidden is not None and hidden is not self._static_hidden:
                     bimap_r(self._static_hidden, hidden, lambda dst, src: dst.copy_(src, non_blocking=True))
