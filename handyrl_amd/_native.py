@@ -259,6 +259,18 @@ SIGNATURES = {
                                                       ctypes.c_void_p, _i64, ctypes.c_int, _f32p, _f32p,
                                                       ctypes.c_void_p, ctypes.c_void_p, _i64, _f32p, _f32p,
                                                       ctypes.c_void_p]),
+    'hrl_geister_observation_record_at': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                         ctypes.c_void_p, _i64, ctypes.c_int, _f32p, _f32p,
+                                                         ctypes.c_void_p, ctypes.c_void_p, _i64, _f32p, _f32p,
+                                                         ctypes.c_void_p]),
+    'hrl_selfplay_sample_record_stream': (ctypes.c_int, [_f32p, _i64, ctypes.c_void_p, ctypes.c_uint64,
+                                                         ctypes.c_void_p, ctypes.c_void_p, _f32p, ctypes.c_void_p,
+                                                         ctypes.c_void_p, ctypes.c_void_p, _i64, _i64, _i64, _i64,
+                                                         ctypes.c_void_p, _f32p, _f32p, ctypes.c_void_p, _f32p,
+                                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'hrl_selfplay_harvest': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _f32p, _dbl,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_void_p]),
     'hrl_replay_gather': (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_void_p, _i64, _i64, ctypes.c_void_p, ctypes.c_void_p]),
     'hrl_replay_draw': (ctypes.c_int, [_f32p, _i64, _i64, _i64, _i64, _i64, ctypes.c_void_p, _i64, _i64,
@@ -285,6 +297,13 @@ class ReplayBatch(ctypes.Structure):
     _fields_ = ([('obs', ctypes.c_void_p * REPLAY_MAX_LEAVES)]
                 + [(k, ctypes.c_void_p) for k in ('policy', 'amask', 'action', 'value', 'outcome', 'reward', 'ret',
                                                   'episode_mask', 'turn_mask', 'observation_mask', 'progress')])
+
+
+class SelfplaySlots(ctypes.Structure):
+    """struct hrl_selfplay_slots (include/hrl_env.h)"""
+    _fields_ = ([('E', _i64), ('Tm', _i64), ('P', _i64), ('A', _i64), ('nleaves', ctypes.c_int32),
+                 ('obs_width', _i64 * REPLAY_MAX_LEAVES), ('obs', ctypes.c_void_p * REPLAY_MAX_LEAVES)]
+                + [(k, ctypes.c_void_p) for k in ('policy', 'amask', 'action', 'value', 'turn', 'reward')])
 
 
 ABI_VERSION = 30

@@ -123,6 +123,55 @@ __global__ void observation_kernel(const int8_t *__restrict__ board, const int64
     }
 }
 
+// observation_kernel for the streaming generator: every game records at its own ply index ply[e]; an inactive
+// game (or one whose ply is outside [0, Tm)) stores nothing into the record.  A kernel of its own, so that the
+// lockstep one above stays the code it was.
+__global__ void observation_at_kernel(const int8_t *__restrict__ board, const int64_t *__restrict__ color,
+                                      const int64_t *__restrict__ cnt, const int64_t *__restrict__ player,
+                                      int64_t E, int full, float *__restrict__ planes, float *__restrict__ scalar,
+                                      const uint8_t *__restrict__ active, const int64_t *__restrict__ ply,
+                                      int64_t Tm, float *__restrict__ rec_planes, float *__restrict__ rec_scalar) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= E * kCells) return;
+    const int64_t e = i / kCells;
+    const int cell = (int)(i - e * kCells);
+    const int c = (int)color[e];
+    const bool turn_view = player[e] == c;
+    const int me = turn_view ? c : 1 - c, opp = 1 - me;
+    const int p = board[e * kCells + (me == 1 ? kCells - 1 - cell : cell)];
+    const bool blue_c = p == me * 2, red_c = p == me * 2 + 1;
+    const bool own = blue_c || red_c;
+    const bool opp_all = p >= 0 && !own;
+    const bool blue_o = full && p == opp * 2, red_o = full && p == opp * 2 + 1;
+    const float pv[7] = {1.0f, own ? 1.0f : 0.0f, opp_all ? 1.0f : 0.0f, blue_c ? 1.0f : 0.0f,
+                         red_c ? 1.0f : 0.0f, blue_o ? 1.0f : 0.0f, red_o ? 1.0f : 0.0f};
+    float *o = planes + e * 7 * kCells + cell;
+#pragma unroll
+    for (int k = 0; k < 7; ++k) o[k * kCells] = pv[k];
+    const int64_t t = ply[e];
+    const bool live = active[e] != 0 && t >= 0 && t < Tm;
+    const int64_t slot = live ? e * Tm + t : 0;
+    if (live) {
+        float *r = rec_planes + slot * 7 * kCells + cell;
+#pragma unroll
+        for (int k = 0; k < 7; ++k) r[k * kCells] = pv[k];
+    }
+    if (cell < 18) {
+        float v;
+        if (cell == 0) {
+            v = me == 0 ? 1.0f : 0.0f;
+        } else if (cell == 1) {
+            v = turn_view ? 1.0f : 0.0f;
+        } else {
+            const int k = cell - 2, which = k >> 2, n = (k & 3) + 1;
+            const int side = which < 2 ? me : opp;
+            v = cnt[e * 4 + side * 2 + (which & 1)] == n ? 1.0f : 0.0f;
+        }
+        scalar[e * 18 + cell] = v;
+        if (live) rec_scalar[slot * 18 + cell] = v;
+    }
+}
+
 __global__ void step_kernel(int8_t *__restrict__ board, int64_t *__restrict__ color, int64_t *__restrict__ turn_count,
                             int64_t *__restrict__ win, int64_t *__restrict__ cnt, const int64_t *__restrict__ action,
                             const uint8_t *active, const int8_t *__restrict__ layout_type,
@@ -198,6 +247,20 @@ int hrl_geister_observation_record(const int8_t *board, const int64_t *color, co
     const Rec rec{active, t, Tm, rec_planes, rec_planes ? rec_scalar : nullptr};
     hipLaunchKernelGGL(observation_kernel, dim3(grid_for(E * kCells)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), board, color, cnt, player, E, full, planes, scalar, rec);
+    { const hipError_t err = hipGetLastError(); return err == hipSuccess ? HRL_OK : HRL_ELAUNCH_BASE - (int)err; }
+}
+
+int hrl_geister_observation_record_at(const int8_t *board, const int64_t *color, const int64_t *cnt,
+                                      const int64_t *player, int64_t E, int full, float *planes, float *scalar,
+                                      const uint8_t *active, const int64_t *ply, int64_t Tm, float *rec_planes,
+                                      float *rec_scalar, void *stream) {
+    if (!board || !color || !cnt || !player || !planes || !scalar || !active || !ply || !rec_planes || !rec_scalar ||
+        E < 0 || Tm < 1)
+        return HRL_EINVAL;
+    if (E == 0) return HRL_OK;
+    hipLaunchKernelGGL(observation_at_kernel, dim3(grid_for(E * kCells)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), board, color, cnt, player, E, full, planes, scalar, active,
+                       ply, Tm, rec_planes, rec_scalar);
     { const hipError_t err = hipGetLastError(); return err == hipSuccess ? HRL_OK : HRL_ELAUNCH_BASE - (int)err; }
 }
 

@@ -12,6 +12,12 @@
 //   (policy 0, action mask 1e32, action / value / turn / reward 0).
 // The ply index t is read from device memory, so the launch is replayed unchanged by the ply's HIP graph.
 // HBM-light (E*A*(4+1+4 in, 4+4 out) bytes, ~18 MB per ply at E=2048, A=214): latency bound.
+//
+// The streaming generator (rollout.StreamGenerator: every slot at its own ply, finished games restart in place)
+// has its own tail, sample_record_stream_kernel -- slot (e, ply[e]), uniforms from Philox4x32-10 inside the wave,
+// no (Tm, E, A) uniform buffer -- and its harvest: harvest_kernel copies a finished game's records into the replay
+// ring (DeviceReplay.add's ten index_copy_ launches and the return loop as one launch), harvest_advance_kernel
+// restarts the slots and advances the ring state, which lives in device memory.
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -81,6 +87,286 @@ __global__ __launch_bounds__(kWave *kGamesPerBlock) void sample_record_kernel(
     }
 }
 
+// ---- the streaming generator's tail: per-game ply index, uniforms from a counter-based generator ----
+// Philox4x32-10 (Salmon et al., SC'11).  The rule (key, counter, word, uniform) is public: include/hrl_env.h and
+// rollout.stream_uniforms, which this reproduces bit for bit.
+__device__ __forceinline__ uint32_t philox_word(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2,
+                                                uint32_t c3, int word) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0;
+        c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1;
+        c3 = lo0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return word == 0 ? c0 : word == 1 ? c1 : word == 2 ? c2 : c3;
+}
+
+// sample_record_kernel with the slot (e, ply[e]) and u computed here; an inactive game stores no record.
+__global__ __launch_bounds__(kWave *kGamesPerBlock) void sample_record_stream_kernel(
+    const float *__restrict__ logits, int64_t lstride, const uint8_t *__restrict__ legal, uint32_t k0, uint32_t k1,
+    const int64_t *__restrict__ game, const int64_t *__restrict__ ply, const float *__restrict__ value,
+    const uint8_t *__restrict__ active, const int64_t *__restrict__ player, const double *__restrict__ reward,
+    int64_t E, int A, int64_t Tm, int P, int64_t *__restrict__ action, float *__restrict__ policy_buf,
+    float *__restrict__ amask_buf, int64_t *__restrict__ action_buf, float *__restrict__ value_buf,
+    int64_t *__restrict__ turn_buf, double *__restrict__ reward_buf) {
+    const int lane = threadIdx.x % kWave;
+    const int64_t e = (int64_t)blockIdx.x * kGamesPerBlock + threadIdx.x / kWave;
+    if (e >= E) return;
+    const int64_t t = ply[e];
+    if (!active[e] || t < 0 || t >= Tm) {   // wave-uniform
+        if (lane == 0) action[e] = 0;
+        return;
+    }
+    const uint64_t n = (uint64_t)game[e];
+    const uint32_t n0 = (uint32_t)n, n1 = (uint32_t)(n >> 32), tw = (uint32_t)t;
+    const float *lg = logits + e * lstride;
+    const uint8_t *lm = legal + e * A;
+    float *pol = policy_buf + (e * Tm + t) * A;
+    float *am = amask_buf + (e * Tm + t) * A;
+    float best = 0.0f;
+    int ib = A;   // no label yet
+    for (int j = lane; j < A; j += kWave) {
+        const uint32_t x = philox_word(k0, k1, n0, n1, tw, (uint32_t)(j >> 2), j & 3);
+        const float u = ((float)(x >> 9) + 0.5f) * 0x1p-23f;
+        const float m = lm[j] ? 0.0f : 1e32f;
+        const float p = lg[j] - m;
+        const float g = p - logf(-logf(u));
+        if (ib == A || better(g, j, best, ib)) {
+            best = g;
+            ib = j;
+        }
+        pol[j] = p;
+        am[j] = m;
+    }
+    for (int off = kWave / 2; off > 0; off >>= 1) {
+        const float ob = __shfl_xor(best, off);
+        const int oi = __shfl_xor(ib, off);
+        if (oi != A && (ib == A || better(ob, oi, best, ib))) {
+            best = ob;
+            ib = oi;
+        }
+    }
+    if (lane == 0) {
+        action[e] = ib;
+        const int64_t s = e * Tm + t;
+        action_buf[s] = ib;
+        value_buf[s] = value[e];
+        turn_buf[s] = player[e];
+        if (reward && reward_buf)
+            for (int q = 0; q < P; ++q) reward_buf[s * P + q] = reward[e * P + q];
+    }
+}
+
+// ---- the streaming generator's harvest: finished games -> ring rows, their slots restarted ----
+// Grid (E / kSlotsPerBlock, kHarvestSplit + 1): a block skips a slot that is not done; for a done one it counts
+// the done slots below it (the ring row); kHarvestSplit of them copy a share each of every record of the episode and the
+// last one forms the returns (harvest_returns) and stores length, outcome and game number.  A slot's record of one
+// field is Tm * width contiguous floats, in the slot and in the ring row alike, so it is copied as one flat run:
+// 16 bytes per lane where Tm * width is a multiple of four (every Geister field: Tm = 202 is even and the widths
+// 252, 18 and 214 are; value's 202 is not), else element by element.  A ply's validity is a bound on the flat
+// index (t < L  <=>  i < L * width), so no lane divides.  ~570 KB per Geister episode, HBM-bound.
+constexpr int kHarvestThreads = 256;
+constexpr int kHarvestSplit = 8;
+constexpr int kFloatFields = HRL_REPLAY_MAX_LEAVES + 3;   // obs leaves, policy, amask, value
+
+struct HarvestArgs {
+    const float *fsrc[kFloatFields];
+    void *fdst[kFloatFields];
+    int64_t fwidth[kFloatFields];
+    float ffill[kFloatFields];
+    int32_t ftype[kFloatFields];   // HRL_REPLAY_U8 / HRL_REPLAY_F32
+    int32_t fvec[kFloatFields];    // 16-byte loads (and 16- / 4-byte stores) are aligned for every slot and row
+    int32_t nf, P;
+    const int64_t *action, *turn;
+    int64_t *r_action, *r_turn;
+    const double *reward;
+    float *r_reward, *r_ret, *r_outcome;
+    int64_t *r_length, *ring_game;
+    const float *outcome;
+    const int64_t *game, *ply, *state;
+    const uint8_t *done;
+    int64_t E, Tm, N;
+    double gamma;
+};
+
+// ret[t] = reward[t] + gamma * ret[t+1] per player, fp64 from t = L-1 down, stored as fp32; zeros from L on.  The
+// scan is a dependent chain, so its operands must not come from HBM one by one (202 round trips: 40 us measured):
+// the block stages kScanElems rewards at a time in LDS, lane q scans player q there in place, and the block
+// stores the chunk coalesced.  More players than lanes or than a chunk holds: the plain loop.
+constexpr int kScanElems = 2048;
+__device__ void harvest_returns(const HarvestArgs &a, int64_t e, int64_t row, int64_t L) {
+    __shared__ double s_rew[kScanElems];
+    const int P = a.P;
+    const int64_t TP = a.Tm * P;
+    float *ret = a.r_ret + row * TP;
+    for (int64_t i = L * P + threadIdx.x; i < TP; i += kHarvestThreads) ret[i] = 0.0f;
+    if (L == 0) return;
+    const double *rew = a.reward + e * TP;
+    if (P > kHarvestThreads || P > kScanElems) {
+        for (int q = threadIdx.x; q < P; q += kHarvestThreads) {
+            double acc = 0.0;
+            for (int64_t t = L - 1; t >= 0; --t) {
+                acc = rew[t * P + q] + a.gamma * acc;
+                ret[t * P + q] = (float)acc;
+            }
+        }
+        return;
+    }
+    const int64_t per = kScanElems / P;   // plies per chunk
+    double acc = 0.0;                     // lane q's carry across the chunks
+    for (int64_t hi = L; hi > 0; hi -= per) {
+        const int64_t lo = hi > per ? hi - per : 0;
+        const int64_t n = (hi - lo) * P;
+        for (int64_t i = threadIdx.x; i < n; i += kHarvestThreads) s_rew[i] = rew[lo * P + i];
+        __syncthreads();
+        if ((int)threadIdx.x < P)
+            for (int64_t t = hi - lo - 1; t >= 0; --t) {
+                acc = s_rew[t * P + threadIdx.x] + a.gamma * acc;
+                s_rew[t * P + threadIdx.x] = acc;
+            }
+        __syncthreads();
+        for (int64_t i = threadIdx.x; i < n; i += kHarvestThreads) ret[lo * P + i] = (float)s_rew[i];
+        __syncthreads();
+    }
+}
+
+// One done slot e, by the block's share blockIdx.y; every branch that leaves is block-uniform.
+__device__ void harvest_slot(const HarvestArgs &a, int64_t e, int *s_r, int *s_c) {
+    int r = 0, c = 0;
+    for (int64_t i = threadIdx.x; i < a.E; i += kHarvestThreads) {
+        const int d = a.done[i] != 0;
+        c += d;
+        r += d & (i < e);
+    }
+    for (int off = kWave / 2; off > 0; off >>= 1) {
+        r += __shfl_xor(r, off);
+        c += __shfl_xor(c, off);
+    }
+    if (threadIdx.x % kWave == 0) {
+        s_r[threadIdx.x / kWave] = r;
+        s_c[threadIdx.x / kWave] = c;
+    }
+    __syncthreads();
+    r = c = 0;
+    for (int w = 0; w < kHarvestThreads / kWave; ++w) {
+        r += s_r[w];
+        c += s_c[w];
+    }
+    if ((int64_t)r + a.N < (int64_t)c) return;   // a higher slot claims this row in the same call
+    int64_t base = a.state[0] % a.N;
+    if (base < 0) base += a.N;
+    const int64_t row = (base + r) % a.N;
+    int64_t L = a.ply[e];
+    L = L < 0 ? 0 : L > a.Tm ? a.Tm : L;
+    const int64_t TP = a.Tm * a.P;
+    if (blockIdx.y == kHarvestSplit) {   // the slot's last block: the returns, length, outcome, game number
+        harvest_returns(a, e, row, a.reward ? L : 0);
+        for (int q = threadIdx.x; q < a.P; q += kHarvestThreads) a.r_outcome[row * a.P + q] = a.outcome[e * a.P + q];
+        if (threadIdx.x == 0) {
+            a.r_length[row] = L;
+            a.ring_game[row] = a.game[e];
+        }
+        return;
+    }
+    const int64_t first = (int64_t)blockIdx.y * kHarvestThreads + threadIdx.x;
+    const int64_t step = (int64_t)kHarvestSplit * kHarvestThreads;
+    for (int f = 0; f < a.nf; ++f) {
+        const int64_t total = a.Tm * a.fwidth[f], lim = L * a.fwidth[f];
+        const float *src = a.fsrc[f] + e * total;
+        const float fill = a.ffill[f];
+        const bool u8 = a.ftype[f] == HRL_REPLAY_U8;
+        float *df = static_cast<float *>(a.fdst[f]) + row * total;
+        uint8_t *db = static_cast<uint8_t *>(a.fdst[f]) + row * total;
+        if (a.fvec[f]) {
+            for (int64_t i = first; i < total / 4; i += step) {
+                float4 v = reinterpret_cast<const float4 *>(src)[i];
+                const int64_t j = i * 4;
+                v.x = j < lim ? v.x : fill;
+                v.y = j + 1 < lim ? v.y : fill;
+                v.z = j + 2 < lim ? v.z : fill;
+                v.w = j + 3 < lim ? v.w : fill;
+                if (u8)
+                    reinterpret_cast<uchar4 *>(db)[i] =
+                        make_uchar4((uint8_t)(int)v.x, (uint8_t)(int)v.y, (uint8_t)(int)v.z, (uint8_t)(int)v.w);
+                else
+                    reinterpret_cast<float4 *>(df)[i] = v;
+            }
+        } else {
+            for (int64_t i = first; i < total; i += step) {
+                const float v = i < lim ? src[i] : fill;
+                if (u8)
+                    db[i] = (uint8_t)(int)v;
+                else
+                    df[i] = v;
+            }
+        }
+    }
+    for (int64_t i = first; i < a.Tm; i += step) {
+        a.r_action[row * a.Tm + i] = i < L ? a.action[e * a.Tm + i] : 0;
+        a.r_turn[row * a.Tm + i] = i < L ? a.turn[e * a.Tm + i] : 0;
+    }
+    for (int64_t i = first; i < TP; i += step)
+        a.r_reward[row * TP + i] = (a.reward && i < L * a.P) ? (float)a.reward[e * TP + i] : 0.0f;
+}
+
+// A block looks at kSlotsPerBlock slots.  One per block is the measured choice: eight per block (a ninth of the
+// workgroups that only read one byte) was slower, 28 against 22 us per Geister ply at E = 2,048 and 31 against 21 us
+// for TicTacToe at E = 4,096, where some 500 games end per ply and a block then copies its done slots in turn.
+constexpr int kSlotsPerBlock = 1;
+__global__ __launch_bounds__(kHarvestThreads) void harvest_kernel(const HarvestArgs a) {
+    __shared__ int s_r[kHarvestThreads / kWave], s_c[kHarvestThreads / kWave];
+    const int64_t e0 = (int64_t)blockIdx.x * kSlotsPerBlock;
+    for (int k = 0; k < kSlotsPerBlock && e0 + k < a.E; ++k) {
+        if (!a.done[e0 + k]) continue;   // block-uniform
+        harvest_slot(a, e0 + k, s_r, s_c);
+        __syncthreads();                 // the next slot reuses the LDS words
+    }
+}
+
+// One workgroup, after harvest_kernel on the stream: the done slots restart (next game number, ply 0, pending) and
+// the ring state advances.  Thread k owns the slots [k * chunk, (k + 1) * chunk).
+__global__ __launch_bounds__(kHarvestThreads) void harvest_advance_kernel(
+    const uint8_t *__restrict__ done, int64_t E, int64_t N, int64_t *__restrict__ game, int64_t *__restrict__ ply,
+    uint8_t *__restrict__ pending, int64_t *__restrict__ state) {
+    __shared__ int s_wave[kHarvestThreads / kWave];
+    const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
+    const int64_t chunk = (E + kHarvestThreads - 1) / kHarvestThreads;
+    const int64_t lo = threadIdx.x * chunk < E ? threadIdx.x * chunk : E, hi = lo + chunk < E ? lo + chunk : E;
+    int cnt = 0;
+    for (int64_t i = lo; i < hi; ++i) cnt += done[i] != 0;
+    int incl = cnt;   // inclusive scan over the wave's lanes, then over the waves
+    for (int off = 1; off < kWave; off <<= 1) {
+        const int v = __shfl_up(incl, off);
+        if (lane >= off) incl += v;
+    }
+    if (lane == kWave - 1) s_wave[wave] = incl;
+    const int64_t base = state[0], emitted = state[1], next = state[2];
+    __syncthreads();
+    int64_t pre = incl - cnt, total = 0;
+    for (int w = 0; w < kHarvestThreads / kWave; ++w) {
+        pre += w < wave ? s_wave[w] : 0;
+        total += s_wave[w];
+    }
+    for (int64_t i = lo; i < hi; ++i)
+        if (done[i]) {
+            game[i] = next + pre++;
+            ply[i] = 0;
+            pending[i] = 1;
+        }
+    if (threadIdx.x == 0 && total > 0) {
+        int64_t b = base % N;
+        if (b < 0) b += N;
+        state[0] = (b + total) % N;
+        state[1] = emitted + total;
+        state[2] = next + total;
+    }
+}
+
 // ---- the movers' recurrent state advance (generation.py:38-41): dst[l] row e <- src[l] row e where mask[e] ----
 constexpr int kMaxRowLeaves = 16;
 struct RowLeaves {
@@ -140,6 +426,96 @@ int hrl_selfplay_sample_record(const float *logits, int64_t logit_stride, const 
                        reward, E, (int)A, Tm, (int)P, action, policy_buf, amask_buf, action_buf, value_buf, turn_buf,
                        reward_buf);
     const hipError_t err = hipGetLastError();
+    return err == hipSuccess ? HRL_OK : HRL_ELAUNCH_BASE - (int)err;
+}
+
+int hrl_selfplay_sample_record_stream(const float *logits, int64_t logit_stride, const uint8_t *legal, uint64_t seed,
+                                      const int64_t *game, const int64_t *ply, const float *value,
+                                      const uint8_t *active, const int64_t *player, const double *reward, int64_t E,
+                                      int64_t A, int64_t Tm, int64_t P, int64_t *action, float *policy_buf,
+                                      float *amask_buf, int64_t *action_buf, float *value_buf, int64_t *turn_buf,
+                                      double *reward_buf, void *stream) {
+    if (!logits || !legal || !game || !ply || !value || !active || !player || !action || !policy_buf || !amask_buf ||
+        !action_buf || !value_buf || !turn_buf || E < 0 || A < 1 || A > (1 << 20) || Tm < 1 || P < 1 ||
+        P > 0x7fffffff || logit_stride < A || ((reward == nullptr) != (reward_buf == nullptr)))
+        return HRL_EINVAL;
+    if (E == 0) return HRL_OK;
+    const int blocks = (int)((E + kGamesPerBlock - 1) / kGamesPerBlock);
+    hipLaunchKernelGGL(sample_record_stream_kernel, dim3(blocks), dim3(kWave * kGamesPerBlock), 0,
+                       static_cast<hipStream_t>(stream), logits, logit_stride, legal, (uint32_t)seed,
+                       (uint32_t)(seed >> 32), game, ply, value, active, player, reward, E, (int)A, Tm, (int)P, action,
+                       policy_buf, amask_buf, action_buf, value_buf, turn_buf, reward_buf);
+    const hipError_t err = hipGetLastError();
+    return err == hipSuccess ? HRL_OK : HRL_ELAUNCH_BASE - (int)err;
+}
+
+int hrl_selfplay_harvest(const uint8_t *done, const hrl_selfplay_slots *slots, int64_t *ply, const float *outcome,
+                         double gamma, const hrl_replay_ring *ring, int64_t *ring_game, int64_t *game,
+                         uint8_t *pending, int64_t *state, void *stream) {
+    if (!done || !slots || !ply || !outcome || !ring || !ring_game || !game || !pending || !state) return HRL_EINVAL;
+    const int64_t E = slots->E, Tm = slots->Tm, P = slots->P, A = slots->A, N = ring->N;
+    const int nl = slots->nleaves;
+    if (E < 0 || E > 0x7fffffff || Tm < 1 || P < 1 || A < 1 || N < 1 || ring->Tm != Tm || ring->P != P ||
+        ring->A != A || nl < 1 || nl > HRL_REPLAY_MAX_LEAVES || ring->nleaves != nl)
+        return HRL_EINVAL;
+    constexpr int64_t kMaxRecord = (int64_t)1 << 31;
+    if (Tm >= kMaxRecord || A >= kMaxRecord || P >= kMaxRecord || Tm * A >= kMaxRecord || Tm * P >= kMaxRecord)
+        return HRL_EINVAL;
+    if (!slots->policy || !slots->amask || !slots->action || !slots->value || !slots->turn || !ring->policy ||
+        !ring->amask || !ring->action || !ring->value || !ring->turn || !ring->reward || !ring->ret || !ring->length ||
+        !ring->outcome)
+        return HRL_EINVAL;
+    HarvestArgs a{};
+    auto field = [&a, Tm](const float *src, const void *dst, int64_t width, int type, float fill) {
+        const int f = a.nf++;
+        a.fsrc[f] = src;
+        a.fdst[f] = const_cast<void *>(dst);
+        a.fwidth[f] = width;
+        a.ftype[f] = type;
+        a.ffill[f] = fill;
+        a.fvec[f] = (Tm * width) % 4 == 0 && (uintptr_t)src % 16 == 0 &&
+                    (uintptr_t)dst % (type == HRL_REPLAY_U8 ? 4 : 16) == 0;
+    };
+    for (int l = 0; l < nl; ++l) {
+        const int64_t w = slots->obs_width[l];
+        const int type = ring->obs_type[l];
+        if (w < 1 || w != ring->obs_width[l] || w >= kMaxRecord || Tm * w >= kMaxRecord || !slots->obs[l] ||
+            !ring->obs[l] || (type != HRL_REPLAY_U8 && type != HRL_REPLAY_F32))
+            return HRL_EINVAL;
+        field(slots->obs[l], ring->obs[l], w, type, 0.0f);
+    }
+    field(slots->policy, ring->policy, A, HRL_REPLAY_F32, 0.0f);
+    field(slots->amask, ring->amask, A, HRL_REPLAY_F32, 1e32f);
+    field(slots->value, ring->value, 1, HRL_REPLAY_F32, 0.0f);
+    if (E == 0) return HRL_OK;
+    a.P = (int32_t)P;
+    a.action = slots->action;
+    a.turn = slots->turn;
+    a.r_action = const_cast<int64_t *>(ring->action);
+    a.r_turn = const_cast<int64_t *>(ring->turn);
+    a.reward = slots->reward;
+    a.r_reward = const_cast<float *>(ring->reward);
+    a.r_ret = const_cast<float *>(ring->ret);
+    a.r_outcome = const_cast<float *>(ring->outcome);
+    a.r_length = const_cast<int64_t *>(ring->length);
+    a.ring_game = ring_game;
+    a.outcome = outcome;
+    a.game = game;
+    a.ply = ply;
+    a.state = state;
+    a.done = done;
+    a.E = E;
+    a.Tm = Tm;
+    a.N = N;
+    a.gamma = gamma;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(harvest_kernel, dim3((unsigned)((E + kSlotsPerBlock - 1) / kSlotsPerBlock), kHarvestSplit + 1),
+                       dim3(kHarvestThreads), 0, s, a);
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return HRL_ELAUNCH_BASE - (int)err;
+    hipLaunchKernelGGL(harvest_advance_kernel, dim3(1), dim3(kHarvestThreads), 0, s, done, E, N, game, ply, pending,
+                       state);
+    err = hipGetLastError();
     return err == hipSuccess ? HRL_OK : HRL_ELAUNCH_BASE - (int)err;
 }
 

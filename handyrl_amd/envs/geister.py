@@ -620,6 +620,22 @@ class GeisterBatch:
         if getattr(self, 'pidx', None) is not None:
             self.pidx.fill_(-1)
 
+    def state_tensors(self):
+        """Every tensor of the game state (StreamGenerator saves and restores them around a graph capture)."""
+        return [self.board, self.color, self.turn_count, self.win, self.cnt, self.live] + (
+            [] if self.pidx is None else [self.pidx])
+
+    def reset_where(self, mask):
+        """reset() for the games of ``mask`` (E,) bool only, in place (StreamGenerator: finished games restart)."""
+        self.live.masked_fill_(mask, True)
+        self.board.masked_fill_(mask.view(-1, 1), -1)
+        self.color.masked_fill_(mask, 0)
+        self.turn_count.masked_fill_(mask, -2)
+        self.win.masked_fill_(mask, -1)
+        self.cnt.masked_fill_(mask.view(-1, 1), 0)
+        if self.pidx is not None:
+            self.pidx.masked_fill_(mask.view(-1, 1), -1)
+
     pidx = None   # (E, 36) piece index (colour*8 + slot) per cell, kept only when piece_order(True) asked for it
 
     def piece_order(self, on=True):
@@ -768,6 +784,25 @@ class GeisterBatch:
             ptr(self.board), ptr(self.color), ptr(self.cnt), ptr(player), self.E, int(bool(self.COMPLETE_INFO)),
             ptr(planes), ptr(scalar), ptr(active), ptr(t), Tm, ptr(rec['board']), ptr(rec['scalar']),
             stream_of(self.board.device)), 'hrl_geister_observation_record')
+        return {'board': planes, 'scalar': scalar}
+
+    def observation_record_at(self, player, rec, ply, active):
+        """observation_record for StreamGenerator: game e records at its own ply index ply[e] ((E,) int64), and
+        an inactive game stores nothing into the record (hrl_geister_observation_record_at)."""
+        from .._native import load, check, ptr, stream_of
+        player = player.to(torch.long).contiguous()
+        active = active.contiguous()
+        assert player.shape == (self.E,) and active.shape == (self.E,) and active.dtype == torch.bool
+        assert ply.shape == (self.E,) and ply.dtype == torch.long and ply.is_contiguous()
+        Tm = rec['board'].shape[1]
+        assert rec['board'].shape == (self.E, Tm, BOARD_PLANES, *BOARD) and rec['board'].is_contiguous()
+        assert rec['scalar'].shape == (self.E, Tm, SCALARS) and rec['scalar'].is_contiguous()
+        planes = torch.empty(self.E, BOARD_PLANES, *BOARD, device=self.device)
+        scalar = torch.empty(self.E, SCALARS, device=self.device)
+        check(load().hrl_geister_observation_record_at(
+            ptr(self.board), ptr(self.color), ptr(self.cnt), ptr(player), self.E, int(bool(self.COMPLETE_INFO)),
+            ptr(planes), ptr(scalar), ptr(active), ptr(ply), Tm, ptr(rec['board']), ptr(rec['scalar']),
+            stream_of(self.board.device)), 'hrl_geister_observation_record_at')
         return {'board': planes, 'scalar': scalar}
 
     def observation(self, player, full=False):

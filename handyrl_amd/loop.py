@@ -17,7 +17,7 @@ import time
 
 import torch
 
-from .rollout import DeviceGenerator, DeviceReplay, TicTacToeBatch
+from .rollout import DeviceGenerator, DeviceReplay, StreamGenerator, TicTacToeBatch
 from .trainer import LearnerStep
 from .util import map_r
 
@@ -26,16 +26,22 @@ __all__ = ['SelfPlayTrainer', 'evaluate_vs_random']
 
 class SelfPlayTrainer:
     """``env_cls``: a batched env (TicTacToeBatch, envs.geister.GeisterBatch); recurrent nets
-    train from a zero hidden state at every window start (train.py:375)."""
+    train from a zero hidden state at every window start (train.py:375).  ``stream``: play with
+    ``rollout.StreamGenerator`` (``games_per_round`` slots that restart in place; a round plays until that many
+    more games are in the ring) instead of the lockstep ``DeviceGenerator``."""
 
     def __init__(self, net, args, device, games_per_round=4096, capacity=65536, graph=False, seed=0,
-                 env_cls=TicTacToeBatch, obs_dtype=torch.uint8):
+                 env_cls=TicTacToeBatch, obs_dtype=torch.uint8, stream=False):
         self.args = args
         self.device = device
         self.env = env_cls(games_per_round, device)
-        self.gen = DeviceGenerator(self.env, net, gamma=args['gamma'])
         self.replay = DeviceReplay(capacity, env_cls.MAX_PLIES, env_cls.OBS_SHAPE, env_cls.A, env_cls.P, device,
                                    maximum_episodes=args.get('maximum_episodes', capacity), obs_dtype=obs_dtype)
+        self.stream = bool(stream)
+        if self.stream:
+            self.gen = StreamGenerator(self.env, net, self.replay, gamma=args['gamma'], seed=seed)
+        else:
+            self.gen = DeviceGenerator(self.env, net, gamma=args['gamma'])
         self.learner = LearnerStep(net, args, device, graph=graph)
         self.hidden = None
         if hasattr(net, 'init_hidden'):
@@ -46,6 +52,10 @@ class SelfPlayTrainer:
         self._batch = None   # the one batch every step gathers into (train_steps)
 
     def generate(self):
+        if self.stream:
+            out = self.gen.generate(self.env.E)
+            self.episodes += out['episodes']
+            return out
         ep = self.gen.generate(generator=self.rng)
         self.replay.add(ep)
         self.episodes += ep['length'].shape[0]

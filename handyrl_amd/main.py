@@ -24,6 +24,12 @@ written) with the actors and the learner on the GPU:
   envs, one batched GPU forward per ply, generation.py's semantics) into
   ``hostgen.MomentReplay``; ``generator: host`` in train_args forces that
   path for every env;
+* ``self_play: stream`` in train_args (default ``lockstep``) plays the stock mode of an alternating env with
+  ``rollout.StreamGenerator`` instead: ``stream_slots`` game slots (default: the rank's ``update_episodes``), a
+  finished game written into the ``DeviceReplay`` ring by one launch and its slot restarted at once, so no slot
+  waits for the longest game of a batch.  Every call plays until ``update_episodes`` more games are in the ring
+  (it may overshoot by less than one check interval) and the episode counts follow what was actually emitted;
+  any other mode with ``stream`` raises at start-up;
 * ``update_episodes`` games per epoch with the current weights (the
   reference's workers hold the latest published model), recency-weighted
   replay of ``maximum_episodes``; training starts once ``minimum_episodes``
@@ -54,7 +60,8 @@ import yaml
 from . import distributed as hdist
 from .environment import make_env, prepare_env
 from .hostgen import HostBatchGenerator, MomentReplay
-from .rollout import DeviceGenerator, DeviceReplay, ParallelTicTacToeBatch, PlayerReplay, TicTacToeBatch
+from .rollout import (DeviceGenerator, DeviceReplay, ParallelTicTacToeBatch, PlayerReplay, StreamGenerator,
+                      TicTacToeBatch)
 from .trainer import Trainer
 
 
@@ -140,7 +147,27 @@ def train_main(args, device=None, loss_fn=None, model_dir='models', log=print):
     minimum = _per_rank(targs['minimum_episodes'], world)
     maximum = _per_rank(targs['maximum_episodes'], world)
     rng = torch.Generator(device=device).manual_seed(seed)
-    if use_device:
+    self_play = targs.get('self_play', 'lockstep')
+    if self_play not in ('lockstep', 'stream'):
+        raise ValueError("train_args['self_play'] must be lockstep or stream, not %r" % (self_play,))
+    if self_play == 'stream' and (not use_device or per_player or not getattr(batched, 'ALTERNATING', False)):
+        raise ValueError("train_args['self_play']: 'stream' plays the mover-only ply of an alternating env with a "
+                         "batched (device) form (turn_based_training without observation); this configuration is "
+                         "played by the lockstep generator (self_play: lockstep)")
+    played = None   # a generator that reports what it emitted (stream): episodes of the last play()
+    if use_device and self_play == 'stream':
+        slots = int(targs.get('stream_slots') or games)
+        replay = DeviceReplay(maximum, batched.MAX_PLIES, batched.OBS_SHAPE, batched.A, batched.P, device,
+                              maximum_episodes=maximum, obs_dtype=torch.uint8,
+                              draw=targs.get('window_draw', 'multinomial'))
+        gen = StreamGenerator(batched(slots, device), net, replay, gamma=targs['gamma'], seed=seed)
+        played = [0]
+
+        def play():
+            out = gen.generate(games)       # at least `games` more episodes, straight into the ring
+            played[0] = out['episodes']
+            return float(out['env_steps'])
+    elif use_device:
         gen = DeviceGenerator(batched(games, device), net, gamma=targs['gamma'], observation=observe,
                               per_player=per_player)
         # binary observation planes live in HBM as uint8 (widened by the gather)
@@ -173,8 +200,9 @@ def train_main(args, device=None, loss_fn=None, model_dir='models', log=print):
 
     def generate():
         nonlocal episodes
-        episodes += games
-        return play()
+        steps = play()
+        episodes += games if played is None else played[0]
+        return steps
 
     def global_steps(n):
         """Every rank's new env-steps summed: all ranks derive the same step count from it."""

@@ -44,7 +44,8 @@ import torch
 from .util import map_r, bimap_r
 
 __all__ = ['TicTacToeBatch', 'ParallelTicTacToeBatch', 'DeviceGenerator', 'DeviceReplay', 'PlayerReplay',
-           'episodes_to_wire', 'player_episodes_to_wire', 'reference_uniforms']
+           'episodes_to_wire', 'player_episodes_to_wire', 'reference_uniforms', 'StreamGenerator', 'stream_uniforms',
+           'philox4x32']
 
 
 class TicTacToeBatch:
@@ -117,6 +118,17 @@ class TicTacToeBatch:
     def turns_mask(self):
         """(E, P) bool: the players to move (turns(), environment.py:107-113): the side to move."""
         return torch.nn.functional.one_hot(self.turn(), self.P).bool()
+
+    def state_tensors(self):
+        """Every tensor of the game state (StreamGenerator saves and restores them around a graph capture)."""
+        return [self.board, self.color, self.nmoves, self.winner]
+
+    def reset_where(self, mask):
+        """reset() for the games of ``mask`` (E,) bool only, in place (StreamGenerator: finished games restart)."""
+        self.board.masked_fill_(mask.view(-1, 1), 0)
+        self.color.masked_fill_(mask, 1)
+        self.nmoves.masked_fill_(mask, 0)
+        self.winner.masked_fill_(mask, 0)
 
 
 class ParallelTicTacToeBatch(TicTacToeBatch):
@@ -605,6 +617,441 @@ class DeviceGenerator:
             out[key] = st[k].clone()
         out.update(length=env.plies().long(), outcome=env.outcome(), reward=st['reward'].float())
         return out
+
+
+# ---- streaming self-play: every slot at its own ply, finished games restart in place (StreamGenerator) ----
+
+# True: on a GPU the streaming ply's tail and harvest are the launches of hrl_selfplay_sample_record_stream,
+# hrl_geister_observation_record_at and hrl_selfplay_harvest (include/hrl_env.h) instead of the torch ops below,
+# which stay as the CPU path and as the formulation the kernels are tested against (bit-identical).
+FUSED_STREAM = True
+
+_M32 = 0xffffffff
+_PHILOX_M = (0xD2511F53, 0xCD9E8D57)
+_PHILOX_W = (0x9E3779B9, 0xBB67AE85)
+
+
+def philox4x32(counter, key):
+    """Philox4x32-10 (Salmon et al., SC'11) in host integer arithmetic: ``counter`` four and ``key`` two 32-bit
+    words (ints or broadcastable integer arrays); returns the four output words as uint64 arrays."""
+    c = [np.asarray(x, dtype=np.uint64) & np.uint64(_M32) for x in counter]
+    k = [np.asarray(x, dtype=np.uint64) & np.uint64(_M32) for x in key]
+    m0, m1 = (np.uint64(m) for m in _PHILOX_M)
+    w0, w1 = (np.uint64(w) for w in _PHILOX_W)
+    mask, s32 = np.uint64(_M32), np.uint64(32)
+    for _ in range(10):
+        p0, p1 = m0 * c[0], m1 * c[2]            # 32 x 32 -> 64 bits: no overflow in uint64
+        c = [(p1 >> s32) ^ c[1] ^ k[0], p1 & mask, (p0 >> s32) ^ c[3] ^ k[1], p0 & mask]
+        k = [(k[0] + w0) & mask, (k[1] + w1) & mask]
+    return c
+
+
+def stream_uniforms(seed, game, ply, A):
+    """The uniforms game number ``game`` samples its ply ``ply`` with, one per action label: (A,) float32 (``game``
+    / ``ply`` may be integer arrays: (..., A)).  The public sampling rule of the streaming generator, which
+    hrl_selfplay_sample_record_stream reproduces bit for bit: Philox4x32-10 with key (seed & 0xffffffff,
+    seed >> 32) and counter (game & 0xffffffff, game >> 32, ply, a // 4); label a takes output word a % 4, and
+    u = ((x >> 9) + 0.5) * 2**-23, exact in fp32 and inside [2**-24, 1 - 2**-24] (no 0, no 1, no clamp).  A game's
+    uniforms depend on (seed, game, ply, label) only -- not on the slot or the moment it is played."""
+    seed = int(seed) & 0xffffffffffffffff
+    game = np.asarray(game, dtype=np.int64).astype(np.uint64)[..., None]
+    ply = np.asarray(ply, dtype=np.int64).astype(np.uint64)[..., None]
+    a = np.arange(A, dtype=np.uint64)
+    out = philox4x32((game, game >> np.uint64(32), ply, a >> np.uint64(2)), (seed & _M32, seed >> 32))
+    word = np.broadcast_to(a & np.uint64(3), np.broadcast_shapes(out[0].shape, a.shape))
+    x = np.select([word == 0, word == 1, word == 2], out[:3], out[3])
+    return ((x >> np.uint64(9)).astype(np.float32) + np.float32(0.5)) * np.float32(2.0 ** -23)
+
+
+def stream_uniforms_torch(seed, game, ply, A):
+    """``stream_uniforms`` for E games as torch ops: game, ply (E,) int64 -> (E, A) float32.  32-bit words held in
+    int64; a 32 x 32 product wraps in int64 to the right 64 bits."""
+    seed = int(seed) & 0xffffffffffffffff
+    E = game.shape[0]
+    a = torch.arange(A, device=game.device)
+    c0 = (game & _M32).view(E, 1).expand(E, A)
+    c1 = ((game >> 32) & _M32).view(E, 1).expand(E, A)
+    c2 = (ply & _M32).view(E, 1).expand(E, A)
+    c3 = (a >> 2).view(1, A).expand(E, A)
+    k0, k1 = seed & _M32, seed >> 32
+    for _ in range(10):
+        p0, p1 = c0 * _PHILOX_M[0], c2 * _PHILOX_M[1]
+        c0, c1, c2, c3 = ((p1 >> 32) & _M32) ^ c1 ^ k0, p1 & _M32, ((p0 >> 32) & _M32) ^ c3 ^ k1, p0 & _M32
+        k0, k1 = (k0 + _PHILOX_W[0]) & _M32, (k1 + _PHILOX_W[1]) & _M32
+    w = (a & 3).view(1, A)
+    x = torch.where(w == 0, c0, torch.where(w == 1, c1, torch.where(w == 2, c2, c3)))
+    return ((x >> 9).float() + 0.5) * (2.0 ** -23)
+
+
+def _record_at(buf, rows, ply, x, active):
+    """Slot (e, ply[e]) of ``buf`` (E, Tm, ...) becomes x[e] where active[e]; an inactive game stores nothing (its
+    ply may equal Tm: the index is clamped and the old value written back)."""
+    idx = ply.clamp(0, buf.shape[1] - 1)
+    live = active.view(-1, *([1] * (x.dim() - 1)))
+    buf[rows, idx] = torch.where(live, x.to(buf.dtype), buf[rows, idx])
+
+
+def sample_record_stream_torch(st, seed, logits, legal, value, active, player, reward):
+    """The streaming ply's sampling and recording tail as torch ops: ``sample_record_torch`` with the uniforms of
+    ``stream_uniforms`` for (st['game'][e], st['ply'][e]) and the records at slot (e, st['ply'][e]); an inactive
+    game gets action 0 and no record store."""
+    rows, ply = st['rows'], st['ply']
+    m = torch.where(legal, 0.0, 1e32)
+    p = logits.float() - m
+    u = stream_uniforms_torch(seed, st['game'], ply, logits.shape[1])
+    a = torch.argmax(p - torch.log(-torch.log(u)), dim=-1)
+    a = torch.where(active, a, torch.zeros_like(a))
+    _record_at(st['policy'], rows, ply, p, active)
+    _record_at(st['amask'], rows, ply, m, active)
+    _record_at(st['action'], rows, ply, a, active)
+    _record_at(st['value'], rows, ply, value.reshape(-1).float(), active)
+    _record_at(st['turn'], rows, ply, player, active)
+    if reward is not None:
+        _record_at(st['reward'], rows, ply, reward, active)
+    return a
+
+
+def sample_record_stream_hip(st, seed, logits, legal, value, active, player, reward):
+    """sample_record_stream_torch as ONE launch (hrl_selfplay_sample_record_stream, one wave per game)."""
+    from . import _native
+    E, A = logits.shape
+    Tm = st['action'].shape[1]
+    P = st['reward'].shape[2]
+    logits = logits.float()
+    if logits.stride(1) != 1:
+        logits = logits.contiguous()
+    value = value.reshape(E).float().contiguous()
+    legal, active = legal.contiguous(), active.contiguous()
+    player = player.to(torch.long).contiguous()
+    assert legal.shape == (E, A) and legal.dtype == torch.bool and active.shape == (E,) and player.shape == (E,)
+    assert active.dtype == torch.bool and st['policy'].shape == (E, Tm, A)
+    for k in ('game', 'ply'):
+        assert st[k].shape == (E,) and st[k].dtype == torch.long and st[k].is_contiguous()
+    if reward is not None:
+        reward = reward.to(torch.float64).contiguous()
+        assert reward.shape == (E, P)
+    a = torch.empty(E, dtype=torch.long, device=logits.device)
+    _native.check(_native.load().hrl_selfplay_sample_record_stream(
+        _native.ptr(logits), logits.stride(0), _native.ptr(legal), int(seed) & 0xffffffffffffffff,
+        _native.ptr(st['game']), _native.ptr(st['ply']), _native.ptr(value), _native.ptr(active), _native.ptr(player),
+        _native.ptr(reward), E, A, Tm, P, _native.ptr(a), _native.ptr(st['policy']), _native.ptr(st['amask']),
+        _native.ptr(st['action']), _native.ptr(st['value']), _native.ptr(st['turn']),
+        None if reward is None else _native.ptr(st['reward']), _native.stream_of(logits.device)),
+        'hrl_selfplay_sample_record_stream')
+    return a
+
+
+def harvest_torch(st, done, outcome, gamma, replay, ring_game, has_reward=True):
+    """The streaming generator's harvest as torch ops, without a host read (graph-capturable): the episodes of the
+    ``done`` slots go to the ring rows (ring_ptr + r) mod N, r = the number of done slots below, and their slots
+    restart (the contract of hrl_selfplay_harvest, include/hrl_env.h, which equals this bit for bit).  Formed over
+    the W = min(E, N) rows the call can write: row k of them is written when k < c (the done count), by the last
+    done slot that claims it.  ``st``: the slot records and 'ply', 'game', 'pending', 'state', 'rows'."""
+    E, N, Tm = done.shape[0], replay.N, replay.Tm
+    dev = done.device
+    if dev.type == 'cpu' and not bool(done.any()):
+        return      # nothing changes; on the CPU the look costs nothing (a GPU call must not read the device)
+    state, ply, game = st['state'], st['ply'], st['game']
+    W = min(E, N)
+    d = done.long()
+    r = torch.cumsum(d, 0) - d
+    c = d.sum()
+    e_idx = st['rows']
+    order = torch.empty_like(e_idx).scatter_(0, torch.where(done, r, c + (e_idx - r)), e_idx)   # done slots first
+    k = torch.arange(W, device=dev)
+    written = k < c
+    last = k + N * torch.div(torch.clamp(c - 1 - k, min=0), N, rounding_mode='floor')
+    slot = order[torch.where(written, last, k)]
+    rows = (state[0] + k) % N
+    L = ply[slot].clamp(0, Tm)
+    valid = torch.arange(Tm, device=dev).view(1, Tm) < L.view(W, 1)
+
+    def put(dst, new):
+        w = written.view(W, *([1] * (new.dim() - 1)))
+        dst.index_copy_(0, rows, torch.where(w, new.to(dst.dtype), dst.index_select(0, rows)))
+
+    def plies(src, fill=0):
+        v = valid.view(W, Tm, *([1] * (src.dim() - 2)))
+        return torch.where(v, src.index_select(0, slot), fill)
+    bimap_r(replay.obs, st['obs'], lambda dst, src: put(dst, plies(src.to(dst.dtype))))
+    put(replay.policy, plies(st['policy']))
+    put(replay.amask, plies(st['amask'], 1e32))
+    put(replay.action, plies(st['action']))
+    put(replay.value, plies(st['value']))
+    put(replay.turn, plies(st['turn']))
+    rew = plies(st['reward']) if has_reward else torch.zeros(W, Tm, replay.P, dtype=torch.float64, device=dev)
+    put(replay.reward, rew.float())
+    ret = torch.zeros(W, Tm, replay.P, device=dev)
+    acc = torch.zeros_like(rew[:, 0])
+    for t in range(Tm - 1, -1, -1):       # DeviceGenerator._returns: fp64 from the top
+        acc = rew[:, t] + gamma * acc
+        ret[:, t].copy_(acc)
+    put(replay.ret, ret)
+    put(replay.length, L)
+    put(replay.outcome, outcome.index_select(0, slot))
+    put(ring_game, game.index_select(0, slot))
+    game.copy_(torch.where(done, state[2] + r, game))
+    ply.masked_fill_(done, 0)
+    st['pending'].logical_or_(done)
+    state[0:1].copy_(((state[0] + c) % N).view(1))
+    state[1:3].add_(c)
+
+
+def _ring_struct(replay):
+    """struct hrl_replay_ring of a DeviceReplay / PlayerReplay (the struct keeps no tensor alive)."""
+    from . import _native
+    src = _leaves(replay.obs)
+    if len(src) > _native.REPLAY_MAX_LEAVES:
+        raise ValueError('at most %d observation leaves' % _native.REPLAY_MAX_LEAVES)
+    ring = _native.ReplayRing()
+    ring.N, ring.Tm, ring.P, ring.A, ring.nleaves = replay.N, replay.Tm, replay.P, replay.policy.shape[-1], len(src)
+    for l, o in enumerate(src):
+        if o.dtype not in (torch.uint8, torch.float32):
+            raise ValueError('observation records are uint8 or float32, not %s' % o.dtype)
+        ring.obs[l] = o.data_ptr()
+        ring.obs_type[l] = _native.REPLAY_F32 if o.dtype == torch.float32 else _native.REPLAY_U8
+        ring.obs_width[l] = int(np.prod(o.shape[replay._lead:], dtype=np.int64))
+    for k in ('policy', 'amask', 'action', 'value', 'reward', 'ret', 'length', 'outcome'):
+        setattr(ring, k, getattr(replay, k).data_ptr())
+    ring.turn = replay.turn.data_ptr()
+    return ring
+
+
+def harvest_hip(st, done, outcome, gamma, replay, ring_game, has_reward=True):
+    """harvest_torch as the two launches of hrl_selfplay_harvest."""
+    from . import _native
+    E, Tm, A = st['policy'].shape
+    src = _leaves(st['obs'])
+    slots = _native.SelfplaySlots()
+    slots.E, slots.Tm, slots.P, slots.A, slots.nleaves = E, Tm, st['reward'].shape[2], A, len(src)
+    for l, o in enumerate(src):
+        assert o.dtype == torch.float32 and o.is_contiguous() and o.shape[:2] == (E, Tm)
+        slots.obs[l] = o.data_ptr()
+        slots.obs_width[l] = int(np.prod(o.shape[2:], dtype=np.int64))
+    for k in ('policy', 'amask', 'action', 'value', 'turn'):
+        assert st[k].is_contiguous()
+        setattr(slots, k, st[k].data_ptr())
+    slots.reward = st['reward'].data_ptr() if has_reward else None
+    done, outcome = done.contiguous(), outcome.float().contiguous()
+    assert done.shape == (E,) and done.dtype == torch.bool and outcome.shape == (E, replay.P)
+    assert st['pending'].dtype == torch.bool and st['state'].shape == (3,) and st['state'].dtype == torch.long
+    assert ring_game.shape == (replay.N,) and ring_game.dtype == torch.long and ring_game.is_contiguous()
+    ring = _ring_struct(replay)
+    _native.check(_native.load().hrl_selfplay_harvest(
+        _native.ptr(done), ctypes.byref(slots), _native.ptr(st['ply']), _native.ptr(outcome), float(gamma),
+        ctypes.byref(ring), _native.ptr(ring_game), _native.ptr(st['game']), _native.ptr(st['pending']),
+        _native.ptr(st['state']), _native.stream_of(done.device)), 'hrl_selfplay_harvest')
+
+
+class StreamGenerator:
+    """Continuous batched self-play: E slots, each at its own ply; a finished game goes straight into the replay
+    ring and its slot starts a new game (the reference's workers start an episode the moment one ends,
+    generation.py:20-88, worker.py:58-77).  ``DeviceGenerator`` plays its E games in lockstep instead, and a
+    finished game's slot idles until the longest game of the batch ends.
+
+    Scope: the mover-only ply of ALTERNATING envs (TicTacToe, Geister, CIGeister in the stock mode) into a
+    ``DeviceReplay``; per-player records, ``observation`` and ``SIMULTANEOUS`` envs stay with the lockstep
+    ``DeviceGenerator``.
+
+    A global step counter s fixes the mover m = s % P of every live game, as in lockstep (so the P captured ply
+    graphs, ``h[mover]`` as a view and GeisterNet's in-place session all carry over); to keep that invariant a
+    finished slot restarts only at a step with s % P == 0 -- a game of odd length waits one ply.  Each slot
+    carries its ply index and its game number; game n samples ply t with ``stream_uniforms(seed, n, t, A)``
+    whatever slot it is played in and whenever, so every episode can be checked on its own (``ring_game`` names
+    the game in each ring row) and no (Tm, E, A) uniform buffer exists.  The harvest
+    (hrl_selfplay_harvest) writes the finished games' records, returns, lengths and outcomes into the ring in slot
+    order and keeps the ring state {ring_ptr, emitted, next_game} in device memory; ``DeviceReplay.add`` is not
+    used.  ``generate`` mirrors that state into ``replay.ptr`` / ``replay.count`` on return, so ``replay.sample``,
+    ``draw_windows`` and the gather work unchanged.
+
+    Weights: every call enters the net's ``inference_session``, which refreshes the inference weights in place;
+    games in flight continue under the new weights.  That is sound for IMPALA-style off-policy learning (V-trace /
+    UPGO with importance ratios) because every ply records the policy it was sampled from.
+
+    State persists across calls: ``generate(64)`` and four ``generate(16)`` emit the same first 64 episodes.
+    ``games_started``: game numbers handed out so far (the next new game's number).
+    """
+
+    def __init__(self, env_batch, net, replay, gamma=0.8, seed=0, check_every=16, graph=None, observation=False,
+                 per_player=False):
+        if (observation or per_player or getattr(env_batch, 'SIMULTANEOUS', False)
+                or not getattr(env_batch, 'ALTERNATING', False) or getattr(replay, '_lead', 2) != 2):
+            raise ValueError('StreamGenerator plays the mover-only ply of an alternating env into a DeviceReplay; '
+                             'per-player records, observation=True and simultaneous envs are played by the lockstep '
+                             'generator (rollout.DeviceGenerator)')
+        if (replay.Tm, replay.P, replay.policy.shape[-1]) != (env_batch.MAX_PLIES, env_batch.P, env_batch.A):
+            raise ValueError('the replay does not have the env\'s MAX_PLIES, P and A')
+        self.env, self.net, self.replay = env_batch, net, replay
+        self.gamma, self.seed = float(gamma), int(seed) & 0xffffffffffffffff
+        self.check_every = max(1, int(check_every or 1))
+        self.graph = graph
+        self.s = 0                         # global steps run: the mover of step s is s % P
+        self.games_started = env_batch.E
+        self._emitted = 0
+        self._steps = 0                    # env-steps of the emitted episodes
+        self._st = None
+        self._graphs = None
+        self.ring_game = torch.full((replay.N,), -1, dtype=torch.long, device=env_batch.device)
+
+    def _use_graph(self):
+        dev = torch.device(self.env.device)
+        return dev.type == 'cuda' and (self.graph is None or bool(self.graph))
+
+    def _state(self):
+        """The slots' buffers, allocated once: the games live in them across calls."""
+        if self._st is not None:
+            return self._st
+        env, E, dev = self.env, self.env.E, self.env.device
+        Tm, A, P = env.MAX_PLIES, env.A, env.P
+        st = {'obs': _alloc(env.OBS_SHAPE, (E, Tm), dev),
+              'policy': torch.zeros(E, Tm, A, device=dev),
+              'amask': torch.full((E, Tm, A), 1e32, device=dev),
+              'action': torch.zeros(E, Tm, dtype=torch.long, device=dev),
+              'value': torch.zeros(E, Tm, device=dev),
+              'turn': torch.zeros(E, Tm, dtype=torch.long, device=dev),
+              'reward': torch.zeros(E, Tm, P, device=dev, dtype=torch.float64),
+              'ply': torch.zeros(E, dtype=torch.long, device=dev),
+              'game': torch.arange(E, dtype=torch.long, device=dev),
+              'pending': torch.zeros(E, dtype=torch.bool, device=dev),
+              'played': torch.zeros(E, dtype=torch.long, device=dev),     # plies played by the slot, all games
+              'state': torch.tensor([self.replay.ptr, 0, E], dtype=torch.long, device=dev),
+              'rows': torch.arange(E, device=dev),
+              'hidden': None, 'pmajor': False, 'obs_dev': torch.device(dev).type}
+        if hasattr(self.net, 'inference_hidden') and st['obs_dev'] == 'cuda':
+            st['hidden'] = self.net.inference_hidden(E, P, dev)   # leaves (P, E, ...), the net's own layout
+            st['pmajor'] = True
+        elif hasattr(self.net, 'init_hidden'):
+            st['hidden'] = map_r(self.net.init_hidden([E, P]), lambda h: h.to(dev).contiguous())
+        env.reset()
+        self._st = st
+        return st
+
+    def _persistent(self, st):
+        """Everything a ply changes besides the slot records and the ring."""
+        hidden = [] if st['hidden'] is None else _leaves(st['hidden'])
+        return self.env.state_tensors() + hidden + [st[k] for k in ('ply', 'game', 'pending', 'played', 'state')]
+
+    def _ply(self, st, mover, dry=False):
+        """One global step with mover ``mover`` = s % P; ``dry``: nothing is harvested (capture warm-up)."""
+        env, E, Tm = self.env, self.env.E, self.env.MAX_PLIES
+        fused = FUSED_STREAM and st['obs_dev'] == 'cuda'
+        ply, rows, hidden = st['ply'], st['rows'], st['hidden']
+        if mover == 0:
+            # finished games restart here only, so that s % P is the mover of every live game
+            pending = st['pending']
+            env.reset_where(pending)
+            if hidden is not None:
+                def clear(h):
+                    shape = (1, E) if st['pmajor'] else (E, 1)
+                    h.masked_fill_(pending.view(*shape, *([1] * (h.dim() - 2))), 0)
+                map_r(hidden, clear)
+            pending.zero_()
+        # a snapshot: GeisterBatch.active() is state its step updates in place
+        active = env.active().clone() if hasattr(env, 'active') else ~env.terminal()
+        player = env.turn()
+        obs_recorded = fused and hasattr(env, 'observation_record_at')
+        o = env.observation_record_at(player, st['obs'], ply, active) if obs_recorded else env.observation(player)
+        if hidden is None:
+            h_in = None
+        else:
+            h_in = map_r(hidden, (lambda h: h[mover]) if st['pmajor'] else (lambda h: h[:, mover]))
+        out = self.net(o, h_in)
+        has_reward = hasattr(env, 'reward')
+        early = has_reward and getattr(env, 'REWARD_STATELESS', False)
+        reward = env.reward() if early else None
+        if not obs_recorded:
+            bimap_r(st['obs'], o, lambda b, x: _record_at(b, rows, ply, x, active))
+        sample = sample_record_stream_hip if fused else sample_record_stream_torch
+        a = sample(st, self.seed, out['policy'], env.legal(), out['value'], active, player, reward)
+        if hidden is not None and st['obs_dev'] == 'cuda':
+            dst = [h[mover] if st['pmajor'] else h[:, mover] for h in _leaves(hidden)]
+            src = _leaves(out['hidden'])
+            # a net that advanced its stacked state in place left nothing to copy (DeviceGenerator._ply); a
+            # finished game's state moves too, and is zeroed when its slot restarts
+            if not all(d.data_ptr() == x.data_ptr() and d.stride() == x.stride() for d, x in zip(dst, src)):
+                from .nn import masked_rows_copy_
+                masked_rows_copy_(dst, src, active.contiguous())
+        elif hidden is not None:
+            def advance(h, nh):
+                live = active.view(-1, *([1] * (nh.dim() - 1)))
+                h[:, mover].copy_(torch.where(live, nh, h[:, mover]))
+            bimap_r(hidden, out['hidden'], advance)
+        env.step(a, active)
+        if has_reward and not early:
+            _record_at(st['reward'], rows, ply, env.reward().to(st['reward'].dtype), active)
+        ply.add_(active)
+        st['played'].add_(active)
+        done = active & (env.terminal() | (ply >= Tm))
+        if dry:
+            done = torch.zeros_like(done)
+        harvest = harvest_hip if fused else harvest_torch
+        harvest(st, done, env.outcome(), self.gamma, self.replay, self.ring_game, has_reward)
+
+    def _capture(self, st):
+        """One graph per mover.  Warm-up plies run first on a side stream (library workspaces) and harvest
+        nothing; the games, the ring state and the recurrent state are then put back, so that warm-up and capture
+        leave no trace (a slot record the warm-up wrote is written again by the ply that owns it)."""
+        dev = torch.device(self.env.device)
+        P = self.env.P
+        keep = [t.clone() for t in self._persistent(st)]
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            for m in range(P):
+                self._ply(st, m, dry=True)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        graphs, pool = {}, None
+        for m in range(P):
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, pool=pool):
+                self._ply(st, m)
+            pool = g.pool()
+            graphs[m] = g
+        for t, k in zip(self._persistent(st), keep):
+            t.copy_(k)
+        return graphs
+
+    @torch.no_grad()
+    def generate(self, episodes):
+        """Run global steps until ``episodes`` more games have been emitted into the ring (checked every
+        ``check_every`` steps, so a call may overshoot).  Returns {'episodes': emitted by this call, 'env_steps':
+        the sum of their lengths, 'plies': global steps run}."""
+        st = self._state()
+        was_training = self.net.training
+        self.net.eval()
+        session = getattr(self.net, 'inference_session', None)
+        with session(inplace_state=st['pmajor']) if session is not None else contextlib.nullcontext():
+            out = self._generate(st, int(episodes))
+        self.net.train(was_training)
+        return out
+
+    def _generate(self, st, episodes):
+        P, N = self.env.P, self.replay.N
+        graphs = None
+        if self._use_graph():
+            # a captured ply reads the net's parameters and buffers where they live: recapture if any moved (the
+            # games stay); the switch between the kernels and their torch formulation is part of the capture too
+            key = (FUSED_STREAM,) + tuple(t.data_ptr() for t in list(self.net.parameters()) + list(self.net.buffers()))
+            if self._graphs is None or self._graphs[0] != key:
+                self._graphs = (key, self._capture(st))
+            graphs = self._graphs[1]
+        emitted0, steps0, s0 = self._emitted, self._steps, self.s
+        target = emitted0 + episodes
+        emitted = emitted0
+        while emitted < target:
+            for _ in range(self.check_every):
+                if graphs is not None:
+                    graphs[self.s % P].replay()
+                else:
+                    self._ply(st, self.s % P)
+                self.s += 1
+            emitted = int(st['state'][1])
+        ring_ptr, emitted, next_game = (int(v) for v in st['state'].tolist())
+        self._steps = int(st['played'].sum()) - int(st['ply'].sum())   # all plies played less the games in flight
+        self.replay.ptr = ring_ptr
+        self.replay.count = min(self.replay.count + emitted - emitted0, N)
+        self._emitted, self.games_started = emitted, next_game
+        return {'episodes': emitted - emitted0, 'env_steps': self._steps - steps0, 'plies': self.s - s0}
 
 
 # True: on a GPU ``gather`` is the one launch of hrl_replay_gather (include/hrl_replay.h) instead of the torch ops

@@ -1,5 +1,6 @@
 /*
- * hrl_env.h — C ABI of the batched Geister rules and of the self-play ply tail (libhrl.so).
+ * hrl_env.h — C ABI of the batched Geister rules, of the self-play ply tail and of the streaming
+ * generator's harvest (libhrl.so).
  *
  * Replaces the per-game rules of handyrl/envs/geister.py (Environment.legal_actions :460-487,
  * Environment.observation :495-535, Environment.play :359-394), which generation.py:20-88 calls
@@ -17,6 +18,8 @@
 #define HRL_ENV_H
 
 #include <stdint.h>
+
+#include "hrl_replay.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -42,6 +45,16 @@ int hrl_geister_observation_record(const int8_t *board, const int64_t *color, co
                                    const uint8_t *active, const int64_t *t, int64_t Tm, float *rec_planes,
                                    float *rec_scalar, void *stream);
 
+/* hrl_geister_observation_record for the streaming generator (rollout.StreamGenerator): every game records
+ * at its own ply index ply[e] (device memory) instead of one shared slot t.  An active game (active[e] != 0,
+ * 0 <= ply[e] < Tm) gets its view in slot (e, ply[e]) of rec_planes / rec_scalar; an inactive game stores
+ * NOTHING into the record (its ply[e] may equal Tm).  planes / scalar are written for every game.  All
+ * pointers required; HRL_EINVAL (before any HIP call) for a NULL one, E < 0 or Tm < 1; E == 0: HRL_OK. */
+int hrl_geister_observation_record_at(const int8_t *board, const int64_t *color, const int64_t *cnt,
+                                      const int64_t *player, int64_t E, int full, float *planes, float *scalar,
+                                      const uint8_t *active, const int64_t *ply, int64_t Tm, float *rec_planes,
+                                      float *rec_scalar, void *stream);
+
 /* Play action (E,) in every game whose active byte is set (geister.py:359-394): layouts, moves,
  * captures, escapes, piece counts, winner, the 200-move draw; the side to move flips.
  * layout_type (70,8) int8 piece type per initial slot, opos (2,8) int64 initial cells per colour.
@@ -62,6 +75,67 @@ int hrl_selfplay_sample_record(const float *logits, int64_t logit_stride, const 
                                const double *reward, int64_t E, int64_t A, int64_t Tm, int64_t P, int64_t *action,
                                float *policy_buf, float *amask_buf, int64_t *action_buf, float *value_buf,
                                int64_t *turn_buf, double *reward_buf, void *stream);
+
+/* hrl_selfplay_sample_record for the streaming generator: no uniform buffer and no shared ply index.  Game e
+ * is game number game[e] at ply ply[e] (both (E,) int64 device arrays); the wave computes its uniforms itself
+ * by the public rule of rollout.stream_uniforms, bit for bit:
+ *   Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85; ten rounds),
+ *   key (seed & 0xffffffff, seed >> 32), counter (game & 0xffffffff, game >> 32, ply, a / 4),
+ *   label a takes output word x = out[a % 4],  u = ((float)(x >> 9) + 0.5f) * 2^-23  (exact, in (0, 1)).
+ * Otherwise the fp32 operations, the tie order and the records of hrl_selfplay_sample_record, written to slot
+ * (e, ply[e]).  An inactive game gets action[e] = 0 and NO record store at all (its ply[e] may equal Tm); an
+ * active game's ply[e] must lie in [0, Tm) (a game outside it is treated as inactive).
+ * HRL_EINVAL (before any HIP call) for a NULL required pointer, E < 0, A < 1, Tm < 1, P < 1, logit_stride < A,
+ * reward / reward_buf given one without the other; E == 0: HRL_OK, no launch. */
+int hrl_selfplay_sample_record_stream(const float *logits, int64_t logit_stride, const uint8_t *legal, uint64_t seed,
+                                      const int64_t *game, const int64_t *ply, const float *value,
+                                      const uint8_t *active, const int64_t *player, const double *reward, int64_t E,
+                                      int64_t A, int64_t Tm, int64_t P, int64_t *action, float *policy_buf,
+                                      float *amask_buf, int64_t *action_buf, float *value_buf, int64_t *turn_buf,
+                                      double *reward_buf, void *stream);
+
+/* The slot records of the streaming generator (DeviceGenerator's mover-only layout), DEVICE pointers to
+ * C-contiguous fp32 / int64 / fp64 tensors; the struct itself is HOST memory read before the call returns:
+ *   obs[l] (E, Tm, obs_width[l]) fp32, l < nleaves <= 8      policy, amask (E, Tm, A) fp32
+ *   action, turn (E, Tm) int64    value (E, Tm) fp32           reward (E, Tm, P) fp64 or NULL (no reward) */
+typedef struct hrl_selfplay_slots {
+    int64_t E, Tm, P, A;
+    int32_t nleaves;
+    int64_t obs_width[HRL_REPLAY_MAX_LEAVES];
+    const float *obs[HRL_REPLAY_MAX_LEAVES];
+    const float *policy, *amask;
+    const int64_t *action;
+    const float *value;
+    const int64_t *turn;
+    const double *reward;
+} hrl_selfplay_slots;
+
+/* Finished games leave their slots for the replay ring (rollout.StreamGenerator calls this once per ply, after
+ * the env step).  done (E,) bytes marks them; ply[e] is a finished game's length L (0 <= L <= Tm; clamped).
+ * With c the number of done slots and r(e) the number of done slots below e (slot order: deterministic, no
+ * atomics), base = state[0]:
+ *   ring row (base + r) mod N receives the whole episode of slot e, over the ring's WRITABLE records
+ *   (`ring` as in hrl_replay_gather, layout HRL_REPLAY_MOVER_RECORDS; its tmask / omask are ignored):
+ *     plies t < L   the slot's records; an observation leaf converted as src.to(dst.dtype) does (HRL_REPLAY_U8:
+ *                   (uint8)x, x in [0, 255]), the reward narrowed to fp32,
+ *                   ret[t] = reward[t] + gamma * ret[t+1] per player in fp64 from t = L-1 down (ret[L] = 0),
+ *                   stored as fp32 (DeviceGenerator._returns; the library is built with -ffp-contract=off);
+ *     plies t >= L  the reset values: obs 0, policy 0, amask 1e32, action, value, turn, reward, ret 0;
+ *     length = L, outcome = outcome[e] ((E, P) fp32), ring_game[row] = game[e]  (ring_game (N,) int64).
+ *   When c > N a row is claimed more than once in the call; the highest slot wins, as if the slots were emitted
+ *   one after another.
+ * A second launch of one workgroup, ordered after the first by the stream, then restarts the slots and advances
+ * the state with plain stores: game[e] = state[2] + r, ply[e] = 0, pending[e] = 1 for the done slots, and
+ * state = {ring_ptr, emitted, next_game} (3 int64) becomes {(base + c) mod N, emitted + c, next_game + c}.
+ * A call with no done slot changes nothing.  slots->reward NULL: the ring's reward and ret get zeros.
+ * HRL_EINVAL (before any HIP call) for: a NULL done / slots / ply / outcome / ring / ring_game / game / pending /
+ * state; E < 0; Tm, P, A or N < 1; ring Tm, P, A or leaf count / widths other than the slots'; nleaves not in
+ * [1, 8]; an obs_type other than HRL_REPLAY_U8 / HRL_REPLAY_F32; an obs_width < 1; a NULL required record (all but
+ * slots->reward, ring->tmask, ring->omask); a record of 2^31 elements or more per slot.  E == 0 passes the same
+ * validation, returns HRL_OK and launches nothing.  Ring offsets are formed in 64 bits. */
+int hrl_selfplay_harvest(const uint8_t *done, const hrl_selfplay_slots *slots, int64_t *ply, const float *outcome,
+                         double gamma, const hrl_replay_ring *ring, int64_t *ring_game, int64_t *game,
+                         uint8_t *pending, int64_t *state, void *stream);
 
 /* Masked row copy for the movers' recurrent state (generation.py:38-41: only the mover's hidden state
  * advances): for each of nleaves (<= 16) fp32 tensors, row e of dst[l] (E rows of F[l] contiguous floats,

@@ -1,0 +1,245 @@
+"""The streaming generator's three entries against their torch formulations (rollout.sample_record_stream_torch,
+rollout.harvest_torch, GeisterBatch.observation + rollout._record_at), bit for bit, on guard-band buffers
+(tests/guarded.py).  Every record is an ``inout`` payload: elements the contract leaves alone must keep their
+prefill.  The same calls on plain tensors give the same bytes."""
+
+import pytest
+import torch
+
+from tests.guarded import Arena, Plain, bits
+from handyrl_amd import rollout
+from handyrl_amd.rollout import DeviceReplay
+
+pytestmark = pytest.mark.gpu
+
+E, TM = 13, 5
+
+
+def _eq(a, b, what):
+    assert torch.equal(bits(a), bits(b)), what
+
+
+def _tail_inputs(A, dev, reward):
+    g = torch.Generator().manual_seed(A)
+    lstride = A + 3                                      # strided logit rows
+    logits = torch.randn(E, lstride, generator=g)
+    legal = torch.rand(E, A, generator=g) < 0.6
+    legal[4] = False                                     # rows with no legal action
+    legal[9] = False
+    ply = torch.tensor([0, 1, 2, 3, 4, 0, 4, 2, 1, 3, TM, 0, 4])
+    active = torch.ones(E, dtype=torch.bool)
+    active[2] = active[7] = active[10] = False           # inactive slots; slot 10 sits at ply == Tm
+    game = torch.tensor([3, 0, (1 << 40) + 5, 17, 4, 9, 1, 2, 8, 1000003, 6, 7, 12])
+    rec = {'policy': torch.randn(E, TM, A, generator=g), 'amask': torch.randn(E, TM, A, generator=g),
+           'action': torch.randint(0, A, (E, TM), generator=g), 'value': torch.randn(E, TM, generator=g),
+           'turn': torch.randint(0, 2, (E, TM), generator=g),
+           'reward': torch.randn(E, TM, 2, generator=g, dtype=torch.float64)}
+    inp = {'logits': logits, 'legal': legal, 'value': torch.randn(E, 1, generator=g),
+           'player': torch.randint(0, 2, (E,), generator=g),
+           'reward': torch.randn(E, 2, generator=g, dtype=torch.float64) if reward else None}
+    inp = {k: None if v is None else v.to(dev) for k, v in inp.items()}
+    return inp, rec, ply, active, game, lstride
+
+
+@pytest.mark.parametrize('reward', [True, False])
+@pytest.mark.parametrize('A', [9, 214])
+def test_tail_matches_torch(cuda, A, reward):
+    inp, rec, ply, active, game, lstride = _tail_inputs(A, cuda, reward)
+    seed = 0x9e3779b97f4a7c15
+    results = []
+    for maker in (None, Arena(cuda), Plain(cuda)):
+        keep = (lambda t: t.clone().to(cuda)) if maker is None else maker.inout
+        st = {k: keep(v) for k, v in rec.items()}
+        st.update(ply=ply.to(cuda), game=game.to(cuda), rows=torch.arange(E, device=cuda))
+        fn = rollout.sample_record_stream_torch if maker is None else rollout.sample_record_stream_hip
+        a = fn(st, seed, inp['logits'][:, :A], inp['legal'], inp['value'], active.to(cuda), inp['player'],
+               inp['reward'])
+        if maker is not None:
+            maker.check()
+        results.append((a, st))
+    (a0, s0) = results[0]
+    assert int(a0[2]) == int(a0[7]) == int(a0[10]) == 0
+    for a, st in results[1:]:
+        _eq(a, a0, 'action')
+        for k in rec:
+            _eq(st[k], s0[k], k)
+    # the inactive slots' records and every other ply keep their prefill (no record store at all)
+    for k, v in rec.items():
+        for e in (2, 7, 10):
+            _eq(results[1][1][k][e], v[e].to(cuda), (k, e))
+        if not reward and k == 'reward':
+            _eq(results[1][1][k], v.to(cuda), k)
+    # a row with no legal action: argmax over p = logit - 1e32
+    assert bool((results[1][1]['amask'][4, 4] == 1e32).all())
+
+
+PATTERNS = {'none': [], 'all': list(range(E)), 'first': [0], 'last': [E - 1], 'some': [1, 4, 5, 11]}
+
+
+def _harvest_case(dev, obs_dtype, pattern, reward, N=7, ring_ptr=5):
+    g = torch.Generator().manual_seed(len(pattern) + 31 * N)
+    A, P = 9, 2
+    shape = {'board': (3, 4), 'scalar': (5,)}
+    rec = {'obs': {k: torch.randint(0, 2, (E, TM) + s, generator=g).float() for k, s in shape.items()},
+           'policy': torch.randn(E, TM, A, generator=g), 'amask': torch.randn(E, TM, A, generator=g),
+           'action': torch.randint(0, A, (E, TM), generator=g), 'value': torch.randn(E, TM, generator=g),
+           'turn': torch.randint(0, 2, (E, TM), generator=g),
+           'reward': torch.randn(E, TM, P, generator=g, dtype=torch.float64)}
+    done = torch.zeros(E, dtype=torch.bool)
+    done[pattern] = True
+    ply = torch.tensor([TM, 1, 3, 2, TM, 1, 4, 2, 5, 3, 1, TM, 1])     # lengths 1 and Tm among the done slots
+    state = torch.tensor([ring_ptr, 100, 1000])
+    game = torch.arange(E) * 3 + 50
+    pending = torch.zeros(E, dtype=torch.bool)
+    pending[6] = True
+    outcome = torch.randn(E, P, generator=g)
+    replay = DeviceReplay(N, TM, shape, A, P, 'cpu', obs_dtype=obs_dtype)
+    ring = {k: torch.randn(getattr(replay, k).shape, generator=g) for k in ('policy', 'amask', 'value', 'reward',
+                                                                             'ret', 'outcome')}
+    ring.update({k: torch.randint(0, 5, getattr(replay, k).shape, generator=g) for k in ('action', 'turn', 'length')})
+    ring['obs'] = {k: torch.randint(0, 2, v.shape, generator=g).to(obs_dtype) for k, v in replay.obs.items()}
+    ring_game = torch.randint(0, 40, (N,), generator=g)
+    return dict(rec=rec, done=done, ply=ply, state=state, game=game, pending=pending, outcome=outcome, ring=ring,
+                ring_game=ring_game, shape=shape, A=A, P=P, N=N, reward=reward)
+
+
+def _run_harvest(case, dev, maker, fn, obs_dtype):
+    keep = (lambda t: t.clone().to(dev)) if maker is None else maker.inout
+    rec = case['rec']
+    st = {k: v.to(dev) for k, v in rec.items() if k != 'obs'}
+    st['obs'] = {k: v.to(dev) for k, v in rec['obs'].items()}
+    st.update(ply=keep(case['ply']), game=keep(case['game']), pending=keep(case['pending']),
+              state=keep(case['state']), rows=torch.arange(E, device=dev))
+    replay = DeviceReplay(case['N'], TM, case['shape'], case['A'], case['P'], dev, obs_dtype=obs_dtype)
+    for k, v in case['ring'].items():
+        if k == 'obs':
+            replay.obs = {kk: keep(vv) for kk, vv in v.items()}
+        else:
+            setattr(replay, k, keep(v))
+    ring_game = keep(case['ring_game'])
+    fn(st, case['done'].to(dev), case['outcome'].to(dev), 0.8, replay, ring_game, case['reward'])
+    if maker is not None:
+        maker.check()
+    out = {k: getattr(replay, k) for k in case['ring'] if k != 'obs'}
+    out.update({'obs.' + k: v for k, v in replay.obs.items()})
+    out.update(ring_game=ring_game, ply=st['ply'], game=st['game'], pending=st['pending'], state=st['state'])
+    return out
+
+
+@pytest.mark.parametrize('reward', [True, False])
+@pytest.mark.parametrize('obs_dtype', [torch.uint8, torch.float32])
+@pytest.mark.parametrize('pattern', list(PATTERNS))
+def test_harvest_matches_torch(cuda, pattern, obs_dtype, reward):
+    case = _harvest_case(cuda, obs_dtype, PATTERNS[pattern], reward)
+    ref = _run_harvest(case, cuda, None, rollout.harvest_torch, obs_dtype)
+    for maker in (Arena(cuda), Plain(cuda)):
+        got = _run_harvest(case, cuda, maker, rollout.harvest_hip, obs_dtype)
+        for k in ref:
+            _eq(got[k], ref[k], (pattern, k))
+    n = len(PATTERNS[pattern])
+    assert ref['state'].tolist() == [(5 + n) % 7, 100 + n, 1000 + n]
+    if pattern == 'none':        # a ply with no done slot changes nothing
+        for k, v in case['ring'].items():
+            if k != 'obs':
+                _eq(ref[k], v.to(cuda), k)
+        _eq(ref['ply'], case['ply'].to(cuda), 'ply')
+    if pattern == 'first':       # ring_ptr = 5: row 5; slot 0 has length Tm
+        assert int(ref['ring_game'][5]) == 50 and int(ref['length'][5]) == TM
+        assert int(ref['game'][0]) == 1000 and int(ref['ply'][0]) == 0 and bool(ref['pending'][0])
+    if pattern == 'some':        # rows 5, 6, 0, 1: the write wraps
+        assert ref['ring_game'][[5, 6, 0, 1]].tolist() == [53, 62, 65, 83]
+        assert ref['length'][[5, 6, 0, 1]].tolist() == [1, TM, 1, TM]
+    if pattern == 'all':         # 13 games into 7 rows: the last claimant of a row wins, slots 6..12 stay
+        assert sorted(ref['ring_game'].tolist()) == [50 + 3 * e for e in range(6, 13)]
+
+
+def test_harvest_matches_a_sequential_emission(cuda):
+    """harvest_torch itself against the plain statement of the contract: the done slots emitted one after another
+    in slot order through DeviceReplay.add-style row writes."""
+    case = _harvest_case(cuda, torch.float32, PATTERNS['all'], True)
+    got = _run_harvest(case, cuda, Arena(cuda), rollout.harvest_hip, torch.float32)
+    ptr, rec = 5, case['rec']
+    want = {k: v.clone() for k, v in case['ring'].items() if k != 'obs'}
+    want_game = case['ring_game'].clone()
+    for e in PATTERNS['all']:
+        L = int(case['ply'][e])
+        acc = torch.zeros(2, dtype=torch.float64)
+        for k in ('policy', 'action', 'value', 'turn', 'reward', 'ret'):
+            want[k][ptr] = 0
+        want['amask'][ptr] = 1e32
+        for t in range(L - 1, -1, -1):
+            acc = rec['reward'][e, t] + 0.8 * acc
+            want['ret'][ptr, t] = acc.float()
+        for k in ('policy', 'amask', 'action', 'value', 'turn'):
+            want[k][ptr, :L] = rec[k][e, :L]
+        want['reward'][ptr, :L] = rec['reward'][e, :L].float()
+        want['length'][ptr] = L
+        want['outcome'][ptr] = case['outcome'][e]
+        want_game[ptr] = case['game'][e]
+        ptr = (ptr + 1) % 7
+    for k, v in want.items():
+        _eq(got[k], v.to(cuda), k)
+    _eq(got['ring_game'], want_game.to(cuda), 'ring_game')
+
+
+@pytest.mark.parametrize('Tm,P', [(1100, 2), (3, 300), (700, 3)])
+def test_harvest_returns_beyond_one_staged_chunk(cuda, Tm, P):
+    """The return scan stages 2,048 rewards at a time: an episode of 1,100 plies x 2 players takes two chunks with
+    the carry between them, 700 x 3 one that is no multiple of the chunk's 682 plies, and 300 players (more than
+    the workgroup has lanes) the plain loop.  Against harvest_torch, bit for bit."""
+    n, A, N = 3, 2, 4
+    g = torch.Generator().manual_seed(Tm + P)
+    rec = {'obs': torch.randint(0, 2, (n, Tm, 2), generator=g).float(), 'policy': torch.randn(n, Tm, A, generator=g),
+           'amask': torch.randn(n, Tm, A, generator=g), 'action': torch.randint(0, A, (n, Tm), generator=g),
+           'value': torch.randn(n, Tm, generator=g), 'turn': torch.randint(0, P, (n, Tm), generator=g),
+           'reward': torch.randn(n, Tm, P, generator=g, dtype=torch.float64)}
+    outcome = torch.randn(n, P, generator=g)
+    results = []
+    for fn, maker in ((rollout.harvest_torch, None), (rollout.harvest_hip, Arena(cuda))):
+        st = {k: v.to(cuda) for k, v in rec.items()}
+        st.update(ply=torch.tensor([Tm, Tm - 1, 1], device=cuda), game=torch.tensor([7, 8, 9], device=cuda),
+                  pending=torch.zeros(n, dtype=torch.bool, device=cuda), state=torch.tensor([3, 0, 10], device=cuda),
+                  rows=torch.arange(n, device=cuda))
+        replay = DeviceReplay(N, Tm, (2,), A, P, cuda, obs_dtype=torch.uint8)
+        if maker is not None:
+            replay.ret, replay.reward = maker.inout(replay.ret.cpu()), maker.inout(replay.reward.cpu())
+        ring_game = torch.full((N,), -1, dtype=torch.long, device=cuda)
+        fn(st, torch.tensor([True, True, True], device=cuda), outcome.to(cuda), 0.8, replay, ring_game, True)
+        if maker is not None:
+            maker.check()
+        results.append({k: getattr(replay, k) for k in ('ret', 'reward', 'length', 'outcome', 'policy', 'obs')})
+        results[-1]['ring_game'] = ring_game
+    for k in results[0]:
+        _eq(results[1][k], results[0][k], k)
+    assert results[0]['ring_game'].tolist() == [8, 9, -1, 7]
+    assert bool((results[0]['ret'][3] != 0).all())
+
+
+def test_geister_observation_record_at_matches_torch(cuda):
+    from handyrl_amd.envs.geister import GeisterBatch
+    g = torch.Generator().manual_seed(3)
+    env = GeisterBatch(E, cuda)
+    twin = GeisterBatch(E, 'cpu')          # the torch rules, the formulation the kernel is held to
+    live = torch.ones(E, dtype=torch.bool)
+    for step in range(7):                  # both layouts and a few moves, random legal actions
+        legal = twin.legal()
+        a = torch.multinomial(legal.float(), 1, generator=g).view(-1)
+        twin.step(a, live)
+        env.step(a.to(cuda), live.to(cuda))
+    ply = torch.tensor([0, 1, 2, 3, 4, 0, 4, 2, 1, 3, TM, 0, 4])
+    active = torch.ones(E, dtype=torch.bool)
+    active[2] = active[7] = active[10] = False
+    player = twin.turn().clone()
+    player[3] = 1 - player[3]              # a non-turn view
+    rec0 = {'board': torch.randn(E, TM, 7, 6, 6, generator=g), 'scalar': torch.randn(E, TM, 18, generator=g)}
+    view = twin.observation(player)
+    want = {k: v.clone() for k, v in rec0.items()}
+    for k in want:
+        rollout._record_at(want[k], torch.arange(E), ply, view[k], active)
+    for maker in (Arena(cuda), Plain(cuda)):
+        rec = {k: maker.inout(v) for k, v in rec0.items()}
+        o = env.observation_record_at(player.to(cuda), rec, ply.to(cuda), active.to(cuda))
+        maker.check()
+        for k in want:
+            _eq(o[k], view[k].to(cuda), k)
+            _eq(rec[k], want[k].to(cuda), k)
