@@ -1,0 +1,241 @@
+// hrl_eval.hip — the device evaluator's ply (handyrl/evaluation.py:64-87, agent.py:13-19, 55-110): the model on one
+// seat of every game, a uniform random agent on the others, E slots that restart in place until G games are played.
+//
+// evaluation.DeviceEvaluator runs, per global step, the env's observation and the net's forward, then
+//   eval_act_kernel      one wave per slot, lanes over the A labels: the model seat's argmax (or Gumbel-max at a
+//                        temperature) of the masked logits, the random seat's k-th legal label (eval_pick);
+//   the env's step;
+//   eval_finish_kernel   one workgroup: ply += 1, the finished games' outcome and length stored BY GAME NUMBER, the
+//                        slots restarted with the next game numbers in slot order or retired, the state advanced.
+// Nothing is recorded but the result, so the ply costs two launches besides the env's and the net's.  The rules are
+// public (include/hrl_env.h); evaluation.py holds the torch formulation the kernels equal bit for bit.
+// masked_rows_fill_kernel zeroes a restarting slot's recurrent-state rows (the twin of hrl_masked_rows_copy).
+
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "../../include/hrl_env.h"
+#include "../../include/hrl_targets.h"
+#include "hrl_pick.h"
+
+namespace {
+
+constexpr int kSlotsPerBlock = 4;
+
+struct EvalTrace {   // all four or none (action NULL: no trace)
+    int64_t *action, *picked;
+    float *policy;
+    uint8_t *model_ply;
+};
+
+__global__ __launch_bounds__(kWave *kSlotsPerBlock) void eval_act_kernel(
+    const float *__restrict__ logits, int64_t lstride, const uint8_t *__restrict__ legal, uint32_t k0, uint32_t k1,
+    float inv_t, const int64_t *__restrict__ game, const int64_t *__restrict__ ply,
+    const uint8_t *__restrict__ active, const int64_t *__restrict__ seat, int64_t mover,
+    const int64_t *__restrict__ forced, int64_t E, int A, int64_t Tm, int64_t G, int64_t *__restrict__ action,
+    EvalTrace tr) {
+    const int lane = threadIdx.x % kWave;
+    const int64_t e = (int64_t)blockIdx.x * kSlotsPerBlock + threadIdx.x / kWave;
+    if (e >= E) return;
+    const int64_t t = ply[e], g = game[e];
+    if (!active[e] || t < 0 || t >= Tm || g < 0 || g >= G) {   // wave-uniform
+        if (lane == 0) action[e] = 0;
+        return;
+    }
+    const uint32_t g0 = (uint32_t)(uint64_t)g, g1 = (uint32_t)((uint64_t)g >> 32), tw = (uint32_t)t;
+    const uint8_t *lm = legal + e * A;
+    const bool model = seat[e] == mover;   // wave-uniform
+    int pick = 0;
+    if (model) {
+        const float *lg = logits + e * lstride;
+        float *pol = tr.action ? tr.policy + (g * Tm + t) * A : nullptr;
+        float best = 0.0f;
+        int ib = A;   // no label yet
+        for (int j = lane; j < A; j += kWave) {
+            const float m = lm[j] ? 0.0f : 1e32f;
+            const float p = lg[j] - m;
+            float v = p;
+            if (inv_t > 0.0f) {   // Gumbel-max over p / temperature: the fp32 operations of the streaming tail
+                const uint32_t x = philox_word(k0, k1, g0, g1, tw, (uint32_t)(j >> 2), j & 3);
+                const float u = ((float)(x >> 9) + 0.5f) * 0x1p-23f;
+                v = p * inv_t - logf(-logf(u));
+            }
+            if (ib == A || better(v, j, best, ib)) {
+                best = v;
+                ib = j;
+            }
+            if (pol) pol[j] = p;
+        }
+        for (int off = kWave / 2; off > 0; off >>= 1) {
+            const float ob = __shfl_xor(best, off);
+            const int oi = __shfl_xor(ib, off);
+            if (oi != A && (ib == A || better(ob, oi, best, ib))) {
+                best = ob;
+                ib = oi;
+            }
+        }
+        pick = ib;
+    } else {
+        // the random seat: n legal labels by ballot and popcount, k = (w * n) >> 23, the k-th by prefix count
+        int64_t n = 0;
+        for (int j0 = 0; j0 < A; j0 += kWave) {
+            const int j = j0 + lane;
+            n += __popcll(__ballot(j < A && lm[j] != 0));
+        }
+        const uint64_t w = philox_word(k0, k1, g0, g1, tw, 0xffffffffu, 0) >> 9;
+        int64_t k = (int64_t)((w * (uint64_t)n) >> 23);   // < n
+        for (int j0 = 0; j0 < A && n > 0; j0 += kWave) {
+            const int j = j0 + lane;
+            const bool ok = j < A && lm[j] != 0;
+            const uint64_t b = __ballot(ok);
+            const int c = __popcll(b);
+            if (k < c) {
+                const bool mine = ok && __popcll(b & ((1ull << lane) - 1ull)) == (int)k;
+                pick = j0 + __ffsll((unsigned long long)__ballot(mine)) - 1;
+                break;
+            }
+            k -= c;
+        }
+    }
+    if (lane == 0) {
+        const int64_t s = g * Tm + t;
+        const int64_t f = forced ? forced[s] : -1;
+        const int64_t a = f >= 0 ? f : pick;
+        action[e] = a;
+        if (tr.action) {
+            tr.action[s] = a;
+            tr.picked[s] = pick;
+            tr.model_ply[s] = model ? 1 : 0;
+        }
+    }
+}
+
+// One workgroup; thread k owns the slots [k * chunk, (k + 1) * chunk).  Every store is a plain vector store.
+constexpr int kFinishThreads = 256;
+__global__ __launch_bounds__(kFinishThreads) void eval_finish_kernel(
+    const uint8_t *__restrict__ terminal, const float *__restrict__ outcome, int64_t E, int64_t Tm, int P, int64_t G,
+    uint8_t *__restrict__ active, int64_t *__restrict__ ply, int64_t *__restrict__ game, int64_t *__restrict__ seat,
+    uint8_t *__restrict__ pending, int64_t *__restrict__ state, float *__restrict__ outcome_out,
+    int64_t *__restrict__ length_out) {
+    __shared__ int s_wave[kFinishThreads / kWave];
+    const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
+    const int64_t chunk = (E + kFinishThreads - 1) / kFinishThreads;
+    const int64_t lo = threadIdx.x * chunk < E ? threadIdx.x * chunk : E, hi = lo + chunk < E ? lo + chunk : E;
+    int cnt = 0;
+    for (int64_t i = lo; i < hi; ++i) {
+        if (!active[i]) continue;
+        const int64_t t = ply[i] + 1;
+        ply[i] = t;
+        if (terminal[i] || t >= Tm) {
+            const int64_t g = game[i];
+            if (g >= 0 && g < G) {
+                for (int q = 0; q < P; ++q) outcome_out[g * P + q] = outcome[i * P + q];
+                length_out[g] = t;
+            }
+            ++cnt;
+        }
+    }
+    int incl = cnt;   // inclusive scan over the wave's lanes, then over the waves
+    for (int off = 1; off < kWave; off <<= 1) {
+        const int v = __shfl_up(incl, off);
+        if (lane >= off) incl += v;
+    }
+    if (lane == kWave - 1) s_wave[wave] = incl;
+    const int64_t finished = state[0], next = state[1];
+    __syncthreads();
+    int64_t pre = incl - cnt, total = 0;
+    for (int w = 0; w < kFinishThreads / kWave; ++w) {
+        pre += w < wave ? s_wave[w] : 0;
+        total += s_wave[w];
+    }
+    for (int64_t i = lo; i < hi; ++i) {
+        if (!active[i] || !(terminal[i] || ply[i] >= Tm)) continue;   // ply[i] is this thread's own store
+        const int64_t g = next + pre++;
+        const bool again = g < G;
+        active[i] = 0;
+        ply[i] = 0;
+        game[i] = again ? g : G;
+        seat[i] = again ? g % P : 0;
+        pending[i] = again ? 1 : 0;
+    }
+    if (threadIdx.x == 0 && total > 0) {
+        state[0] = finished + total;
+        state[1] = next + total < G ? next + total : G;
+    }
+}
+
+constexpr int kMaxRowLeaves = 16;
+struct FillLeaves {
+    float *dst[kMaxRowLeaves];
+    int64_t dst_stride[kMaxRowLeaves], F[kMaxRowLeaves];
+};
+
+__global__ __launch_bounds__(256) void masked_rows_fill_kernel(const uint8_t *__restrict__ mask, FillLeaves L) {
+    const int64_t e = blockIdx.x;
+    const int l = blockIdx.y;
+    if (!mask[e]) return;
+    float *d = L.dst[l] + e * L.dst_stride[l];
+    for (int64_t f = threadIdx.x; f < L.F[l]; f += blockDim.x) d[f] = 0.0f;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hrl_eval_act(const float *logits, int64_t logit_stride, const uint8_t *legal, uint64_t seed, double temperature,
+                 const int64_t *game, const int64_t *ply, const uint8_t *active, const int64_t *seat, int64_t mover,
+                 const int64_t *forced, int64_t E, int64_t A, int64_t Tm, int64_t P, int64_t G, int64_t *action,
+                 int64_t *trace_action, int64_t *trace_picked, float *trace_policy, uint8_t *trace_model_ply,
+                 void *stream) {
+    const int ntrace = (trace_action != nullptr) + (trace_picked != nullptr) + (trace_policy != nullptr) +
+                       (trace_model_ply != nullptr);
+    if (!logits || !legal || !game || !ply || !active || !seat || !action || E < 0 || E > 0x7fffffff || A < 1 ||
+        A > (1 << 20) || Tm < 1 || P < 1 || G < 0 || logit_stride < A || mover < 0 || mover >= P ||
+        !(temperature >= 0.0) || (ntrace != 0 && ntrace != 4))
+        return HRL_EINVAL;
+    if (E == 0) return HRL_OK;
+    const float inv_t = temperature > 0.0 ? (float)(1.0 / temperature) : 0.0f;
+    EvalTrace tr{trace_action, trace_picked, trace_policy, trace_model_ply};
+    const int blocks = (int)((E + kSlotsPerBlock - 1) / kSlotsPerBlock);
+    hipLaunchKernelGGL(eval_act_kernel, dim3(blocks), dim3(kWave * kSlotsPerBlock), 0,
+                       static_cast<hipStream_t>(stream), logits, logit_stride, legal, (uint32_t)seed,
+                       (uint32_t)(seed >> 32), inv_t, game, ply, active, seat, mover, forced, E, (int)A, Tm, G, action,
+                       tr);
+    const hipError_t err = hipGetLastError();
+    return err == hipSuccess ? HRL_OK : HRL_ELAUNCH_BASE - (int)err;
+}
+
+int hrl_eval_finish(const uint8_t *terminal, const float *outcome, int64_t E, int64_t Tm, int64_t P, int64_t G,
+                    uint8_t *active, int64_t *ply, int64_t *game, int64_t *seat, uint8_t *pending, int64_t *state,
+                    float *outcome_out, int64_t *length_out, void *stream) {
+    if (!terminal || !outcome || !active || !ply || !game || !seat || !pending || !state || !outcome_out ||
+        !length_out || E < 0 || E > 0x7fffffff || Tm < 1 || P < 1 || P > 0x7fffffff || G < 0)
+        return HRL_EINVAL;
+    if (E == 0) return HRL_OK;
+    hipLaunchKernelGGL(eval_finish_kernel, dim3(1), dim3(kFinishThreads), 0, static_cast<hipStream_t>(stream),
+                       terminal, outcome, E, Tm, (int)P, G, active, ply, game, seat, pending, state, outcome_out,
+                       length_out);
+    const hipError_t err = hipGetLastError();
+    return err == hipSuccess ? HRL_OK : HRL_ELAUNCH_BASE - (int)err;
+}
+
+int hrl_masked_rows_fill(int nleaves, float *const *dst, const int64_t *dst_stride, const int64_t *F,
+                         const uint8_t *mask, int64_t E, void *stream) {
+    if (nleaves < 1 || nleaves > kMaxRowLeaves || !dst || !dst_stride || !F || !mask || E < 0 || E > 0x7fffffff)
+        return HRL_EINVAL;
+    FillLeaves L{};
+    for (int l = 0; l < nleaves; ++l) {
+        if (!dst[l] || F[l] < 1 || dst_stride[l] < F[l]) return HRL_EINVAL;
+        L.dst[l] = dst[l];
+        L.dst_stride[l] = dst_stride[l];
+        L.F[l] = F[l];
+    }
+    if (E == 0) return HRL_OK;
+    hipLaunchKernelGGL(masked_rows_fill_kernel, dim3((unsigned)E, nleaves), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), mask, L);
+    const hipError_t err = hipGetLastError();
+    return err == hipSuccess ? HRL_OK : HRL_ELAUNCH_BASE - (int)err;
+}
+
+}  // extern "C"

@@ -25,18 +25,11 @@
 
 #include "../../include/hrl_env.h"
 #include "../../include/hrl_targets.h"
+#include "hrl_pick.h"
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kGamesPerBlock = 4;
-
-// torch.argmax's order: NaN beats everything, then larger values, ties to the lower index
-__device__ __forceinline__ bool better(float a, int ia, float b, int ib) {
-    const bool na = a != a, nb = b != b;
-    if (na || nb) return na && (!nb || ia < ib);
-    return a > b || (a == b && ia < ib);
-}
 
 __global__ __launch_bounds__(kWave *kGamesPerBlock) void sample_record_kernel(
     const float *__restrict__ logits, int64_t lstride, const uint8_t *__restrict__ legal,
@@ -88,23 +81,8 @@ __global__ __launch_bounds__(kWave *kGamesPerBlock) void sample_record_kernel(
 }
 
 // ---- the streaming generator's tail: per-game ply index, uniforms from a counter-based generator ----
-// Philox4x32-10 (Salmon et al., SC'11).  The rule (key, counter, word, uniform) is public: include/hrl_env.h and
+// Philox4x32-10 (hrl_pick.h).  The rule (key, counter, word, uniform) is public: include/hrl_env.h and
 // rollout.stream_uniforms, which this reproduces bit for bit.
-__device__ __forceinline__ uint32_t philox_word(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2,
-                                                uint32_t c3, int word) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return word == 0 ? c0 : word == 1 ? c1 : word == 2 ? c2 : c3;
-}
 
 // sample_record_kernel with the slot (e, ply[e]) and u computed here; an inactive game stores no record.
 __global__ __launch_bounds__(kWave *kGamesPerBlock) void sample_record_stream_kernel(

@@ -1,6 +1,7 @@
 """Config-driven learner entry point: the reference's ``main.py --train`` on one GPU node.
 
     python -m handyrl_amd.main --train [config.yaml]
+    python -m handyrl_amd.main --eval MODEL_PATH [NUM_GAMES] [SLOTS]
     python -m torch.distributed.run --nproc-per-node N -m handyrl_amd.main --train [config.yaml]
 
 Reads the reference's ``config.yaml`` (main.py:13-15; config.yaml:1-35;
@@ -45,8 +46,13 @@ written) with the actors and the learner on the GPU:
 * data parallel under torchrun: every rank generates and trains its own
   shard, the gradients are SUMmed over RCCL (distributed.py), rank 0 saves.
 
-The worker/server network plane, evaluation servers and the other CLI modes
-are not rebuilt.
+* evaluation: ``eval_rate`` > 0 in train_args makes rank 0 play the reference's per-epoch evaluation after each
+  epoch's training -- the greedy model against random agents on the device (``evaluation.DeviceEvaluator``,
+  ``eval_slots`` slots, ``eval_temperature``) -- and append its win rate to the epoch's log line;
+  ``--eval MODEL_PATH [NUM_GAMES] [SLOTS]`` evaluates a checkpoint (evaluation.py:291-312).
+
+The worker/server network plane, the network match server and client and the other CLI modes are not rebuilt
+(DESIGN.md §6).
 """
 
 import math
@@ -154,6 +160,16 @@ def train_main(args, device=None, loss_fn=None, model_dir='models', log=print):
         raise ValueError("train_args['self_play']: 'stream' plays the mover-only ply of an alternating env with a "
                          "batched (device) form (turn_based_training without observation); this configuration is "
                          "played by the lockstep generator (self_play: lockstep)")
+    evaluator = None
+    if float(targs.get('eval_rate') or 0) > 0:
+        # the reference's per-epoch evaluation (train.py:519-526); an env it cannot play raises here, at start-up
+        from .evaluation import DeviceEvaluator, batched_env, eval_games
+        eval_cls = batched_env(module)
+        eval_n = eval_games(targs['eval_rate'], targs['update_episodes'])
+        if rank == 0:
+            eval_slots = max(1, min(int(targs.get('eval_slots') or eval_n), eval_n))
+            evaluator = DeviceEvaluator(eval_cls(eval_slots, device), net, observation=observe,
+                                        temperature=float(targs.get('eval_temperature', 0.0)), seed=seed)
     played = None   # a generator that reports what it emitted (stream): episodes of the last play()
     if use_device and self_play == 'stream':
         slots = int(targs.get('stream_slots') or games)
@@ -226,15 +242,25 @@ def train_main(args, device=None, loss_fn=None, model_dir='models', log=print):
         if rank == 0:
             os.makedirs(model_dir, exist_ok=True)
             torch.save(model.state_dict(), os.path.join(model_dir, '%d.pth' % epoch))
-            log('epoch %d: episodes %d, steps %d, lr %.3e (%.1fs)' % (epoch, episodes * world, trainer.steps,
-                                                                     trainer.lr, time.perf_counter() - t0))
+            line = 'epoch %d: episodes %d, steps %d, lr %.3e (%.1fs)' % (epoch, episodes * world, trainer.steps,
+                                                                         trainer.lr, time.perf_counter() - t0)
+            if evaluator is not None:
+                res = evaluator.evaluate(eval_n)
+                line += ', win rate %.3f (%.1f / %d)' % (res['win_rate'], res['win_rate'] * eval_n, eval_n)
+            log(line)
     return model
 
 
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
+    if argv and argv[0] in ('--eval', '-e'):
+        from .evaluation import eval_main
+        args = load_config('config.yaml')
+        print(args)
+        eval_main(args, argv[1:])
+        return 0
     if not argv or argv[0] not in ('--train', '-t'):
-        print('usage: python -m handyrl_amd.main --train [config.yaml]  (the learner side of main.py)')
+        print('usage: python -m handyrl_amd.main --train [config.yaml] | --eval MODEL_PATH [NUM_GAMES] [SLOTS]')
         return 1
     args = load_config(argv[1] if len(argv) > 1 else 'config.yaml')
     print(args)

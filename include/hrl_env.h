@@ -1,6 +1,6 @@
 /*
- * hrl_env.h — C ABI of the batched Geister rules, of the self-play ply tail and of the streaming
- * generator's harvest (libhrl.so).
+ * hrl_env.h — C ABI of the batched Geister rules, of the self-play ply tail, of the streaming
+ * generator's harvest and of the device evaluator's ply (libhrl.so).
  *
  * Replaces the per-game rules of handyrl/envs/geister.py (Environment.legal_actions :460-487,
  * Environment.observation :495-535, Environment.play :359-394), which generation.py:20-88 calls
@@ -143,6 +143,67 @@ int hrl_selfplay_harvest(const uint8_t *done, const hrl_selfplay_slots *slots, i
  * One launch for every state tensor, exactly torch.where(mask, src, dst). */
 int hrl_masked_rows_copy(int nleaves, float *const *dst, const int64_t *dst_stride, const float *const *src,
                          const int64_t *src_stride, const int64_t *F, const uint8_t *mask, int64_t E, void *stream);
+
+/* ---- The device evaluator (evaluation.DeviceEvaluator): the model on one seat, uniform random agents on the others
+ * (handyrl/evaluation.py:64-87, agent.py:13-19, 55-110).  E slots play exactly G games and restart in place.
+ *
+ * Public rules (pure-Python twins in handyrl_amd/evaluation.py):
+ *   Games are counted by NUMBER, never by finishing order: numbers 0 .. G-1 are each played exactly once.  Slot e
+ *     starts game e when e < G and is retired otherwise; a finished slot takes next_game + r, r = the number of done
+ *     slots below it in slot order (no atomics, tickets or spin-waits); a slot whose new number would be >= G is
+ *     retired and stays inactive.  (Counting the first G games to FINISH would favour short games.)
+ *   Seat: the model plays seat(g) = g mod P, the other seats are random agents.
+ *   Mover: the mover of global step s is s mod P in every live game, so a slot restarts only at a step with
+ *     s mod P == 0 (`pending` marks a slot that waits for it).
+ *   Random seat, eval_pick(seed, game, ply, legal): n = the number of legal labels, x = output word 0 of
+ *     Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter (game & 0xffffffff, game >> 32, ply,
+ *     0xffffffff) -- the last word is disjoint from the sampling rule's a / 4 above --, w = x >> 9,
+ *     k = (w * n) >> 23 in integer arithmetic, so 0 <= k < n always (an fp32 floor(u * n) can round up to n); the
+ *     action is the k-th legal label in ascending order.
+ *   Model seat, temperature == 0 (agent.py:92-96): p = logits - (legal ? 0 : 1e32), action = argmax p, ties to the
+ *     lowest label, NaN first (torch.argmax's order).  The one difference from the reference: it breaks an exact tie
+ *     by legal_actions() order, which for Geister is by piece, not by label.
+ *   Model seat, temperature > 0 (agent.py:97-100 as Gumbel-max): argmax of p * r - log(-log(u)) in fp32 with
+ *     r = (float)(1.0 / temperature) and u of the streaming rule above for (seed, game, ply, label).
+ *   Forced moves: forced (G, Tm) int64 or NULL; forced[g][t] >= 0 is played at ply t of game g whichever seat moves,
+ *     -1 leaves the decision to the evaluator.
+ *   Trace (tests; all four buffers or none): action, picked (G, Tm) int64, policy (G, Tm, A) fp32, model_ply (G, Tm)
+ *     bytes.  At ply t of game g: action = the move played, picked = the evaluator's own decision even where a move
+ *     was forced, model_ply = 1 and policy = p at a model ply (policy is not stored at a random-seat ply).
+ *
+ * All three entries are asynchronous on `stream`, allocate nothing, read nothing on the host (graph-capturable) and
+ * validate before any HIP call: HRL_EINVAL for a NULL required pointer, E < 0, A < 1, Tm < 1, P < 1, G < 0,
+ * logit_stride < A (and: mover outside [0, P), temperature < 0 or NaN, some but not all trace buffers); E == 0:
+ * HRL_OK, no launch. */
+
+/* One launch per ply, one wave per slot, lanes over the A labels.  A slot with active[e] == 0 (retired or waiting
+ * to restart; also one whose ply[e] is outside [0, Tm) or game[e] outside [0, G)) gets action[e] = 0 and NO other
+ * store.  An active slot plays the model's move where seat[e] == mover and the random agent's elsewhere.
+ * logits (E, >= A) rows of stride logit_stride, legal (E, A) bytes, game / ply / seat (E,) int64, active (E,) bytes;
+ * action (E,) int64 is written for every slot and nothing else outside the trace. */
+int hrl_eval_act(const float *logits, int64_t logit_stride, const uint8_t *legal, uint64_t seed, double temperature,
+                 const int64_t *game, const int64_t *ply, const uint8_t *active, const int64_t *seat, int64_t mover,
+                 const int64_t *forced, int64_t E, int64_t A, int64_t Tm, int64_t P, int64_t G, int64_t *action,
+                 int64_t *trace_action, int64_t *trace_picked, float *trace_policy, uint8_t *trace_model_ply,
+                 void *stream);
+
+/* After the env's step, one launch of one workgroup.  For every active slot: ply += 1 and
+ * done = terminal[e] != 0 || ply >= Tm.  A done slot stores outcome_out[game] = outcome[e] ((G, P) and (E, P) fp32)
+ * and length_out[game] = ply ((G,) int64), indexed by game number, then restarts or retires by the rule above with
+ * {finished, next_game} = state (2 int64 in device memory, plain stores):
+ *   n = next_game + r;  n < G: game = n, seat = n mod P, ply = 0, pending = 1;  else game = G, seat = 0, ply = 0,
+ *   pending = 0;  active = 0 either way (the evaluator sets active where pending at the next step with mover 0);
+ *   state = {finished + c, min(next_game + c, G)}, c = the number of done slots.
+ * Slots that are not active are not touched. */
+int hrl_eval_finish(const uint8_t *terminal, const float *outcome, int64_t E, int64_t Tm, int64_t P, int64_t G,
+                    uint8_t *active, int64_t *ply, int64_t *game, int64_t *seat, uint8_t *pending, int64_t *state,
+                    float *outcome_out, int64_t *length_out, void *stream);
+
+/* The zeroing twin of hrl_masked_rows_copy: rows e with mask[e] != 0 of nleaves (<= 16) fp32 tensors (E rows of F[l]
+ * contiguous floats, row stride dst_stride[l] elements) become 0; other rows are untouched.  One launch (a restarting
+ * slot's recurrent state, by row). */
+int hrl_masked_rows_fill(int nleaves, float *const *dst, const int64_t *dst_stride, const int64_t *F,
+                         const uint8_t *mask, int64_t E, void *stream);
 
 #ifdef __cplusplus
 }
