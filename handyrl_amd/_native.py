@@ -275,6 +275,10 @@ SIGNATURES = {
                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _i64, ctypes.c_void_p, _i64, _i64,
                                     _i64, _i64, _i64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _f32p,
                                     ctypes.c_void_p, ctypes.c_void_p]),
+    'hrl_match_act': (ctypes.c_int, [_f32p, _i64, _f32p, _i64, ctypes.c_void_p, ctypes.c_uint64, _dbl, _dbl, _i64,
+                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _i64,
+                                     ctypes.c_void_p, _i64, _i64, _i64, _i64, _i64, ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_void_p, _f32p, ctypes.c_void_p, ctypes.c_void_p]),
     'hrl_eval_finish': (ctypes.c_int, [ctypes.c_void_p, _f32p, _i64, _i64, _i64, _i64, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_void_p, _f32p, ctypes.c_void_p, ctypes.c_void_p]),

@@ -4,6 +4,8 @@
 // evaluation.DeviceEvaluator runs, per global step, the env's observation and the net's forward, then
 //   eval_act_kernel      one wave per slot, lanes over the A labels: the model seat's argmax (or Gumbel-max at a
 //                        temperature) of the masked logits, the random seat's k-th legal label (eval_pick);
+//   (match_act_kernel    the same launch for a match against a second net: the other seats play that net's move at
+//                        its own temperature, and the first `opening` plies of a game are eval_pick on every seat;)
 //   the env's step;
 //   eval_finish_kernel   one workgroup: ply += 1, the finished games' outcome and length stored BY GAME NUMBER, the
 //                        slots restarted with the next game numbers in slot order or retired, the state advanced.
@@ -29,6 +31,77 @@ struct EvalTrace {   // all four or none (action NULL: no trace)
     uint8_t *model_ply;
 };
 
+// A net's move for one slot (the whole wave): p = logits - (legal ? 0 : 1e32) goes to pol when pol is given; the
+// argmax of p, or at inv_t > 0 the Gumbel-max over p * inv_t, under better().
+__device__ __forceinline__ int net_pick(const float *__restrict__ lg, const uint8_t *__restrict__ lm, float *pol,
+                                        int A, float inv_t, uint32_t k0, uint32_t k1, uint32_t g0, uint32_t g1,
+                                        uint32_t tw, int lane) {
+    float best = 0.0f;
+    int ib = A;   // no label yet
+    for (int j = lane; j < A; j += kWave) {
+        const float m = lm[j] ? 0.0f : 1e32f;
+        const float p = lg[j] - m;
+        float v = p;
+        if (inv_t > 0.0f) {   // Gumbel-max over p / temperature: the fp32 operations of the streaming tail
+            const uint32_t x = philox_word(k0, k1, g0, g1, tw, (uint32_t)(j >> 2), j & 3);
+            const float u = ((float)(x >> 9) + 0.5f) * 0x1p-23f;
+            v = p * inv_t - logf(-logf(u));
+        }
+        if (ib == A || better(v, j, best, ib)) {
+            best = v;
+            ib = j;
+        }
+        if (pol) pol[j] = p;
+    }
+    for (int off = kWave / 2; off > 0; off >>= 1) {
+        const float ob = __shfl_xor(best, off);
+        const int oi = __shfl_xor(ib, off);
+        if (oi != A && (ib == A || better(ob, oi, best, ib))) {
+            best = ob;
+            ib = oi;
+        }
+    }
+    return ib;
+}
+
+// eval_pick for one slot (the whole wave): n legal labels by ballot and popcount, k = (w * n) >> 23, the k-th by
+// prefix count; 0 for a row without a legal label.
+__device__ __forceinline__ int random_pick(const uint8_t *__restrict__ lm, int A, uint32_t k0, uint32_t k1,
+                                           uint32_t g0, uint32_t g1, uint32_t tw, int lane) {
+    int64_t n = 0;
+    for (int j0 = 0; j0 < A; j0 += kWave) {
+        const int j = j0 + lane;
+        n += __popcll(__ballot(j < A && lm[j] != 0));
+    }
+    const uint64_t w = philox_word(k0, k1, g0, g1, tw, 0xffffffffu, 0) >> 9;
+    int64_t k = (int64_t)((w * (uint64_t)n) >> 23);   // < n
+    for (int j0 = 0; j0 < A && n > 0; j0 += kWave) {
+        const int j = j0 + lane;
+        const bool ok = j < A && lm[j] != 0;
+        const uint64_t b = __ballot(ok);
+        const int c = __popcll(b);
+        if (k < c) {
+            const bool mine = ok && __popcll(b & ((1ull << lane) - 1ull)) == (int)k;
+            return j0 + __ffsll((unsigned long long)__ballot(mine)) - 1;
+        }
+        k -= c;
+    }
+    return 0;
+}
+
+// The slot's last stores (lane 0): the move played, forced or picked, and the trace's three scalar records.
+__device__ __forceinline__ void store_move(const int64_t *__restrict__ forced, int64_t s, int pick, bool model,
+                                           int64_t *__restrict__ action, const EvalTrace &tr) {
+    const int64_t f = forced ? forced[s] : -1;
+    const int64_t a = f >= 0 ? f : pick;
+    *action = a;
+    if (tr.action) {
+        tr.action[s] = a;
+        tr.picked[s] = pick;
+        tr.model_ply[s] = model ? 1 : 0;
+    }
+}
+
 __global__ __launch_bounds__(kWave *kSlotsPerBlock) void eval_act_kernel(
     const float *__restrict__ logits, int64_t lstride, const uint8_t *__restrict__ legal, uint32_t k0, uint32_t k1,
     float inv_t, const int64_t *__restrict__ game, const int64_t *__restrict__ ply,
@@ -46,69 +119,45 @@ __global__ __launch_bounds__(kWave *kSlotsPerBlock) void eval_act_kernel(
     const uint32_t g0 = (uint32_t)(uint64_t)g, g1 = (uint32_t)((uint64_t)g >> 32), tw = (uint32_t)t;
     const uint8_t *lm = legal + e * A;
     const bool model = seat[e] == mover;   // wave-uniform
-    int pick = 0;
+    int pick;
     if (model) {
-        const float *lg = logits + e * lstride;
         float *pol = tr.action ? tr.policy + (g * Tm + t) * A : nullptr;
-        float best = 0.0f;
-        int ib = A;   // no label yet
-        for (int j = lane; j < A; j += kWave) {
-            const float m = lm[j] ? 0.0f : 1e32f;
-            const float p = lg[j] - m;
-            float v = p;
-            if (inv_t > 0.0f) {   // Gumbel-max over p / temperature: the fp32 operations of the streaming tail
-                const uint32_t x = philox_word(k0, k1, g0, g1, tw, (uint32_t)(j >> 2), j & 3);
-                const float u = ((float)(x >> 9) + 0.5f) * 0x1p-23f;
-                v = p * inv_t - logf(-logf(u));
-            }
-            if (ib == A || better(v, j, best, ib)) {
-                best = v;
-                ib = j;
-            }
-            if (pol) pol[j] = p;
-        }
-        for (int off = kWave / 2; off > 0; off >>= 1) {
-            const float ob = __shfl_xor(best, off);
-            const int oi = __shfl_xor(ib, off);
-            if (oi != A && (ib == A || better(ob, oi, best, ib))) {
-                best = ob;
-                ib = oi;
-            }
-        }
-        pick = ib;
+        pick = net_pick(logits + e * lstride, lm, pol, A, inv_t, k0, k1, g0, g1, tw, lane);
     } else {
-        // the random seat: n legal labels by ballot and popcount, k = (w * n) >> 23, the k-th by prefix count
-        int64_t n = 0;
-        for (int j0 = 0; j0 < A; j0 += kWave) {
-            const int j = j0 + lane;
-            n += __popcll(__ballot(j < A && lm[j] != 0));
-        }
-        const uint64_t w = philox_word(k0, k1, g0, g1, tw, 0xffffffffu, 0) >> 9;
-        int64_t k = (int64_t)((w * (uint64_t)n) >> 23);   // < n
-        for (int j0 = 0; j0 < A && n > 0; j0 += kWave) {
-            const int j = j0 + lane;
-            const bool ok = j < A && lm[j] != 0;
-            const uint64_t b = __ballot(ok);
-            const int c = __popcll(b);
-            if (k < c) {
-                const bool mine = ok && __popcll(b & ((1ull << lane) - 1ull)) == (int)k;
-                pick = j0 + __ffsll((unsigned long long)__ballot(mine)) - 1;
-                break;
-            }
-            k -= c;
-        }
+        pick = random_pick(lm, A, k0, k1, g0, g1, tw, lane);
     }
-    if (lane == 0) {
-        const int64_t s = g * Tm + t;
-        const int64_t f = forced ? forced[s] : -1;
-        const int64_t a = f >= 0 ? f : pick;
-        action[e] = a;
-        if (tr.action) {
-            tr.action[s] = a;
-            tr.picked[s] = pick;
-            tr.model_ply[s] = model ? 1 : 0;
-        }
+    if (lane == 0) store_move(forced, g * Tm + t, pick, model, action + e, tr);
+}
+
+// The match ply: a second net on the other seats and `opening` random plies.  Per slot: the mover's net is home
+// where seat == mover, else opp (or none: opp NULL); its masked logits go to the trace whenever there is one; the
+// move is eval_pick at an opening ply or without a net, else that net's argmax / Gumbel-max at its own temperature.
+__global__ __launch_bounds__(kWave *kSlotsPerBlock) void match_act_kernel(
+    const float *__restrict__ home, int64_t hstride, const float *__restrict__ opp, int64_t ostride,
+    const uint8_t *__restrict__ legal, uint32_t k0, uint32_t k1, float inv_t_home, float inv_t_opp, int64_t opening,
+    const int64_t *__restrict__ game, const int64_t *__restrict__ ply, const uint8_t *__restrict__ active,
+    const int64_t *__restrict__ seat, int64_t mover, const int64_t *__restrict__ forced, int64_t E, int A, int64_t Tm,
+    int64_t G, int64_t *__restrict__ action, EvalTrace tr) {
+    const int lane = threadIdx.x % kWave;
+    const int64_t e = (int64_t)blockIdx.x * kSlotsPerBlock + threadIdx.x / kWave;
+    if (e >= E) return;
+    const int64_t t = ply[e], g = game[e];
+    if (!active[e] || t < 0 || t >= Tm || g < 0 || g >= G) {   // wave-uniform
+        if (lane == 0) action[e] = 0;
+        return;
     }
+    const uint32_t g0 = (uint32_t)(uint64_t)g, g1 = (uint32_t)((uint64_t)g >> 32), tw = (uint32_t)t;
+    const uint8_t *lm = legal + e * A;
+    const bool model = seat[e] == mover;   // wave-uniform, as is everything below
+    const float *lg = model ? home + e * hstride : opp ? opp + e * ostride : nullptr;
+    int pick = 0;
+    if (lg) {
+        float *pol = tr.action ? tr.policy + (g * Tm + t) * A : nullptr;
+        if (t >= opening || pol)
+            pick = net_pick(lg, lm, pol, A, model ? inv_t_home : inv_t_opp, k0, k1, g0, g1, tw, lane);
+    }
+    if (!lg || t < opening) pick = random_pick(lm, A, k0, k1, g0, g1, tw, lane);
+    if (lane == 0) store_move(forced, g * Tm + t, pick, model, action + e, tr);
 }
 
 // One workgroup; thread k owns the slots [k * chunk, (k + 1) * chunk).  Every store is a plain vector store.
@@ -202,6 +251,32 @@ int hrl_eval_act(const float *logits, int64_t logit_stride, const uint8_t *legal
                        static_cast<hipStream_t>(stream), logits, logit_stride, legal, (uint32_t)seed,
                        (uint32_t)(seed >> 32), inv_t, game, ply, active, seat, mover, forced, E, (int)A, Tm, G, action,
                        tr);
+    const hipError_t err = hipGetLastError();
+    return err == hipSuccess ? HRL_OK : HRL_ELAUNCH_BASE - (int)err;
+}
+
+int hrl_match_act(const float *logits_home, int64_t stride_home, const float *logits_opp, int64_t stride_opp,
+                  const uint8_t *legal, uint64_t seed, double temperature_home, double temperature_opp,
+                  int64_t opening, const int64_t *game, const int64_t *ply, const uint8_t *active,
+                  const int64_t *seat, int64_t mover, const int64_t *forced, int64_t E, int64_t A, int64_t Tm,
+                  int64_t P, int64_t G, int64_t *action, int64_t *trace_action, int64_t *trace_picked,
+                  float *trace_policy, uint8_t *trace_model_ply, void *stream) {
+    const int ntrace = (trace_action != nullptr) + (trace_picked != nullptr) + (trace_policy != nullptr) +
+                       (trace_model_ply != nullptr);
+    if (!logits_home || !legal || !game || !ply || !active || !seat || !action || E < 0 || E > 0x7fffffff || A < 1 ||
+        A > (1 << 20) || Tm < 1 || P < 1 || G < 0 || stride_home < A || (logits_opp && stride_opp < A) || mover < 0 ||
+        mover >= P || !(temperature_home >= 0.0) || !(temperature_opp >= 0.0) || opening < 0 ||
+        (ntrace != 0 && ntrace != 4))
+        return HRL_EINVAL;
+    if (E == 0) return HRL_OK;
+    const float inv_home = temperature_home > 0.0 ? (float)(1.0 / temperature_home) : 0.0f;
+    const float inv_opp = temperature_opp > 0.0 ? (float)(1.0 / temperature_opp) : 0.0f;
+    EvalTrace tr{trace_action, trace_picked, trace_policy, trace_model_ply};
+    const int blocks = (int)((E + kSlotsPerBlock - 1) / kSlotsPerBlock);
+    hipLaunchKernelGGL(match_act_kernel, dim3(blocks), dim3(kWave * kSlotsPerBlock), 0,
+                       static_cast<hipStream_t>(stream), logits_home, stride_home, logits_opp, stride_opp, legal,
+                       (uint32_t)seed, (uint32_t)(seed >> 32), inv_home, inv_opp, opening, game, ply, active, seat,
+                       mover, forced, E, (int)A, Tm, G, action, tr);
     const hipError_t err = hipGetLastError();
     return err == hipSuccess ? HRL_OK : HRL_ELAUNCH_BASE - (int)err;
 }

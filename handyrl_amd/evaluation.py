@@ -18,9 +18,14 @@ The rules are public (include/hrl_env.h spells them out; the kernels reproduce t
 * the model seat plays the argmax of its masked logits (ties to the lowest label) or, at a temperature, Gumbel-max
   over ``p / temperature`` with ``rollout.stream_uniforms(seed, game, ply, A)``.
 
-``FUSED_EVAL``: on a GPU the ply's decision and bookkeeping are the launches of hrl_eval_act, hrl_eval_finish and
-hrl_masked_rows_fill (csrc/hrl_eval.hip); the torch formulation below is the CPU path and the form the kernels are
-tested against.
+A match of two nets (``DeviceEvaluator(..., opponent=)``, ``main.py --eval-match A B``, ``eval_opponent`` in
+train_args) seats a second net on the other seats, as the reference's ``exec_match`` seats one ``Agent`` per model
+(evaluation.py:64-116); the vs-random win rate saturates within a few epochs, a match against a checkpoint does not.
+Each agent has its own temperature, and the first ``opening_plies`` plies of a game are ``eval_pick`` on every seat.
+
+``FUSED_EVAL``: on a GPU the ply's decision and bookkeeping are the launches of hrl_eval_act (hrl_match_act in a
+match), hrl_eval_finish and hrl_masked_rows_fill (csrc/hrl_eval.hip); the torch formulation below is the CPU path and
+the form the kernels are tested against.
 """
 
 import contextlib
@@ -33,7 +38,8 @@ import torch
 from .rollout import _M32, _PHILOX_M, _PHILOX_W, _leaves, philox4x32, stream_uniforms_torch
 from .util import map_r
 
-__all__ = ['DeviceEvaluator', 'eval_pick', 'eval_pick_torch', 'eval_main', 'wp_func', 'eval_games', 'batched_env']
+__all__ = ['DeviceEvaluator', 'eval_pick', 'eval_pick_torch', 'eval_main', 'eval_match_main', 'wp_func', 'eval_games',
+           'batched_env']
 
 # True: on a GPU the three steps are HIP launches; False (or a CPU env): the torch ops below, bit-identical.
 FUSED_EVAL = True
@@ -170,6 +176,89 @@ def act_hip(st, logits, legal, mover, seed, temperature, G, forced=None, trace=N
     return a
 
 
+def match_act_torch(st, logits_home, logits_opp, legal, mover, seed, temperature_home, temperature_opp, opening, G,
+                    forced=None, trace=None):
+    """hrl_match_act: ``act_torch`` with a second net on the other seats (``logits_opp`` None: they play
+    ``eval_pick``) and ``opening`` random plies on every seat.  With ``logits_opp`` None and ``opening`` 0 these are
+    ``act_torch``'s operations."""
+    game, ply, active, seat = st['game'], st['ply'], st['active'], st['seat']
+    E, A = legal.shape
+    Tm = st['Tm']
+    ok = active & (ply >= 0) & (ply < Tm) & (game >= 0) & (game < G)
+    m = torch.where(legal, 0.0, 1e32)
+    u = None
+    if temperature_home > 0 or (logits_opp is not None and temperature_opp > 0):
+        u = stream_uniforms_torch(seed, game, ply, A)   # one agent moves at (game, ply): one stream for both
+
+    def net(logits, temperature):
+        p = logits[:, :A].float() - m
+        v = p
+        if temperature > 0:
+            v = p * float(np.float32(1.0 / temperature)) - torch.log(-torch.log(u))
+        return p, torch.argmax(v, dim=-1)
+
+    home = seat == mover
+    rand = eval_pick_torch(seed, game, ply, legal)
+    p, pick = net(logits_home, temperature_home)
+    has_net = home
+    if logits_opp is not None:
+        po, ao = net(logits_opp, temperature_opp)
+        p, pick = torch.where(home.view(-1, 1), p, po), torch.where(home, pick, ao)
+        has_net = torch.ones_like(home)
+    pick = torch.where(has_net & (ply >= opening), pick, rand)
+    g = torch.where(ok, game, G)
+    t = torch.where(ok, ply, 0)
+    a = pick
+    if forced is not None:
+        f = forced[g, t]
+        a = torch.where(f >= 0, f, pick)
+    a = torch.where(ok, a, 0)
+    if trace is not None:
+        trace['action'][g, t] = a
+        trace['picked'][g, t] = pick
+        trace['model_ply'][g, t] = home
+        trace['policy'][torch.where(has_net, g, G), t] = p
+    return a
+
+
+def match_act_hip(st, logits_home, logits_opp, legal, mover, seed, temperature_home, temperature_opp, opening, G,
+                  forced=None, trace=None):
+    """match_act_torch as ONE launch (hrl_match_act, one wave per slot)."""
+    from . import _native
+    E, A = legal.shape
+    legal = legal.contiguous()
+    assert legal.dtype == torch.bool
+    rows = []
+    for logits in (logits_home, logits_opp):
+        if logits is not None:
+            logits = logits.float()
+            if logits.stride(1) != 1:
+                logits = logits.contiguous()
+            assert logits.shape[0] == E and logits.shape[1] >= A
+        rows.append(logits)
+    for k in ('game', 'ply', 'seat'):
+        assert st[k].shape == (E,) and st[k].dtype == torch.long and st[k].is_contiguous()
+    assert st['active'].shape == (E,) and st['active'].dtype == torch.bool
+    Tm = st['Tm']
+    if forced is not None:
+        assert forced.dtype == torch.long and forced.is_contiguous() and forced.shape[0] >= G
+        assert forced.shape[1] == Tm
+    tr = [None] * 4
+    if trace is not None:
+        tr = [trace[k] for k in ('action', 'picked', 'policy', 'model_ply')]
+        assert all(x.is_contiguous() and x.shape[0] >= G and x.shape[1] == Tm for x in tr)
+        assert tr[0].dtype == tr[1].dtype == torch.long and tr[2].dtype == torch.float32 and tr[2].shape[2] == A
+        assert tr[3].dtype == torch.bool
+    a = torch.empty(E, dtype=torch.long, device=legal.device)
+    _native.check(_native.load().hrl_match_act(
+        _native.ptr(rows[0]), rows[0].stride(0), _native.ptr(rows[1]), 0 if rows[1] is None else rows[1].stride(0),
+        _native.ptr(legal), int(seed) & 0xffffffffffffffff, float(temperature_home), float(temperature_opp),
+        int(opening), _native.ptr(st['game']), _native.ptr(st['ply']), _native.ptr(st['active']),
+        _native.ptr(st['seat']), int(mover), _native.ptr(forced), E, A, Tm, st['P'], G, _native.ptr(a),
+        *[_native.ptr(x) for x in tr], _native.stream_of(legal.device)), 'hrl_match_act')
+    return a
+
+
 def finish_torch(st, terminal, outcome, G, outcome_out, length_out):
     """hrl_eval_finish: plies counted, finished games' results stored by game number, slots restarted or retired."""
     game, ply, active, seat, pending, state = (st[k] for k in ('game', 'ply', 'active', 'seat', 'pending', 'state'))
@@ -242,13 +331,34 @@ class DeviceEvaluator:
     ``inference_session`` in eval mode; the training mode is put back.  No torch generator is drawn from and no
     training state is touched.  The host reads the two-word device state every ``check_every`` steps; that read is
     the only synchronisation.
+
+    A match (``exec_match`` with one ``Agent`` per model, evaluation.py:64-116): ``opponent`` is a second net (another
+    module object than ``net``) that plays every other seat greedily or at ``opponent_temperature`` (None: the same
+    as ``temperature``), and the first ``opening_plies`` plies of every game are ``eval_pick`` moves on every seat:
+    two greedy agents on a deterministic env would otherwise play the same two games over and over.  Each ply then
+    runs both nets over the E slots (the home net views the board from ``seat``, the opponent from the other seat;
+    include/hrl_env.h has the rule for P > 2) and ONE launch of hrl_match_act decides.  There is one recurrent state
+    per net per slot; the opponent's advances where the home seat does not move, or with ``observation`` on every
+    active row.  The result gains ``opponent_results`` (the {outcome: count} table over every non-home seat) and
+    ``opponent_win_rate``.  With the three arguments at their defaults nothing changes.
     """
 
-    def __init__(self, env_batch, net, observation=False, temperature=0.0, seed=0, check_every=16, graph=None):
+    def __init__(self, env_batch, net, observation=False, temperature=0.0, seed=0, check_every=16, graph=None,
+                 opponent=None, opponent_temperature=None, opening_plies=0):
         _check_env(type(env_batch))
         if not temperature >= 0:
             raise ValueError('temperature must be >= 0, not %r' % (temperature,))
+        if opponent_temperature is None:
+            opponent_temperature = temperature
+        if not opponent_temperature >= 0:
+            raise ValueError('opponent_temperature must be >= 0, not %r' % (opponent_temperature,))
+        if int(opening_plies) < 0:
+            raise ValueError('opening_plies must be >= 0, not %r' % (opening_plies,))
+        if opponent is net:
+            raise ValueError('the opponent must be a module of its own (a copy of the net plays a self-match)')
         self.env, self.net = env_batch, net
+        self.opponent, self.opponent_temperature = opponent, float(opponent_temperature)
+        self.opening_plies = int(opening_plies)
         self.observation, self.temperature = bool(observation), float(temperature)
         self.seed = int(seed) & 0xffffffffffffffff
         self.check_every = max(1, int(check_every or 1))
@@ -270,12 +380,13 @@ class DeviceEvaluator:
               'active': torch.zeros(E, dtype=torch.bool, device=dev),
               'pending': torch.zeros(E, dtype=torch.bool, device=dev),
               'state': torch.zeros(2, dtype=torch.long, device=dev), 'rows': torch.arange(E, device=dev),
-              'hidden': None}
-        if hasattr(self.net, 'inference_hidden') and st['cuda']:
-            # the net's stacked layout for one "player": leaf (1, E, ...) -> the slot-major view (E, ...)
-            st['hidden'] = map_r(self.net.inference_hidden(E, 1, dev), lambda h: h[0])
-        elif hasattr(self.net, 'init_hidden'):
-            st['hidden'] = map_r(self.net.init_hidden([E]), lambda h: h.to(dev).contiguous())
+              'hidden': None, 'hidden_opp': None}
+        for key, net in (('hidden', self.net), ('hidden_opp', self.opponent)):
+            if hasattr(net, 'inference_hidden') and st['cuda']:
+                # the net's stacked layout for one "player": leaf (1, E, ...) -> the slot-major view (E, ...)
+                st[key] = map_r(net.inference_hidden(E, 1, dev), lambda h: h[0])
+            elif hasattr(net, 'init_hidden'):
+                st[key] = map_r(net.init_hidden([E]), lambda h: h.to(dev).contiguous())
         self._st = st
         return st
 
@@ -290,8 +401,9 @@ class DeviceEvaluator:
         st['ply'].zero_()
         st['pending'].zero_()
         st['state'].copy_(torch.tensor([0, min(E, G)], dtype=torch.long))
-        if st['hidden'] is not None:
-            map_r(st['hidden'], lambda h: h.zero_())
+        for key in ('hidden', 'hidden_opp'):
+            if st[key] is not None:
+                map_r(st[key], lambda h: h.zero_())
         run['outcome'].zero_()
         run['length'].zero_()
         if run['trace'] is not None:
@@ -302,30 +414,45 @@ class DeviceEvaluator:
 
     def _ply(self, st, run, mover):
         """One global step with mover ``mover`` = s % P."""
-        env, hidden = self.env, st['hidden']
+        env, hidden, hidden_opp = self.env, st['hidden'], st['hidden_opp']
         fused = FUSED_EVAL and st['cuda']
         active, seat, pending = st['active'], st['seat'], st['pending']
         if mover == 0:
             # finished games restart here only, so that s % P is the mover of every live game
             env.reset_where(pending)
-            if hidden is not None:
-                (rows_fill_hip if fused else rows_fill_torch)(_leaves(hidden), pending)
+            for h in (hidden, hidden_opp):
+                if h is not None:
+                    (rows_fill_hip if fused else rows_fill_torch)(_leaves(h), pending)
             active.logical_or_(pending)
             pending.zero_()
         out = self.net(env.observation(seat), hidden)
-        act = act_hip if fused else act_torch
-        a = act(st, out['policy'], env.legal(), mover, self.seed, self.temperature, run['G'], run['forced'],
-                run['trace'])
-        if hidden is not None:
-            # the model's state moves where it played, or (observation) wherever a game is running
-            adv = active.clone() if self.observation else active & (seat == mover)
-            dst, src = _leaves(hidden), _leaves(out['hidden'])
+        out_opp = None
+        if self.opponent is not None:
+            # the opponent's view: the mover's seat where it moves, else the seat after the home seat
+            other = (seat + 1) % st['P']
+            opp_seat = other if st['P'] == 2 else torch.where(seat != mover, torch.full_like(seat, mover), other)
+            out_opp = self.opponent(env.observation(opp_seat), hidden_opp)
+        if out_opp is None and self.opening_plies == 0:
+            act = act_hip if fused else act_torch
+            a = act(st, out['policy'], env.legal(), mover, self.seed, self.temperature, run['G'], run['forced'],
+                    run['trace'])
+        else:
+            act = match_act_hip if fused else match_act_torch
+            a = act(st, out['policy'], None if out_opp is None else out_opp['policy'], env.legal(), mover, self.seed,
+                    self.temperature, self.opponent_temperature, self.opening_plies, run['G'], run['forced'],
+                    run['trace'])
+        # a net's state moves where it played, or (observation) wherever a game is running
+        for h, o, mine in ((hidden, out, True), (hidden_opp, out_opp, False)):
+            if h is None:
+                continue
+            adv = active.clone() if self.observation else active & ((seat == mover) == mine)
+            dst, src = _leaves(h), _leaves(o['hidden'])
             if fused:
                 from .nn import masked_rows_copy_
                 masked_rows_copy_(dst, src, adv)
             else:
-                for h, nh in zip(dst, src):
-                    h.copy_(torch.where(adv.view(-1, *([1] * (nh.dim() - 1))), nh, h))
+                for x, nx in zip(dst, src):
+                    x.copy_(torch.where(adv.view(-1, *([1] * (nx.dim() - 1))), nx, x))
         env.step(a, active)
         finish = finish_hip if fused else finish_torch
         finish(st, env.terminal(), env.outcome(), run['G'], run['outcome'], run['length'])
@@ -355,8 +482,9 @@ class DeviceEvaluator:
         """The buffers that depend on G (a captured ply addresses them) and the graphs, kept for the next call with
         the same G, forced / trace choice and parameter addresses."""
         dev = self.env.device
-        key = (G, forced is not None, bool(trace), FUSED_EVAL, self._use_graph()) + tuple(
-            t.data_ptr() for t in list(self.net.parameters()) + list(self.net.buffers()))
+        nets = [self.net] + ([] if self.opponent is None else [self.opponent])
+        key = (G, forced is not None, bool(trace), FUSED_EVAL, self._use_graph(), self.opponent is not None,
+               self.opening_plies) + tuple(t.data_ptr() for n in nets for t in list(n.parameters()) + list(n.buffers()))
         if self._run is None or self._run['key'] != key:
             Tm, P, A = st['Tm'], st['P'], self.env.A
             run = {'key': key, 'G': G, 'graphs': None, 'forced': None, 'trace': None,
@@ -391,15 +519,19 @@ class DeviceEvaluator:
         if G < 0:
             raise ValueError('games must be >= 0')
         st = self._state()
-        was_training = self.net.training
-        self.net.eval()
-        session = getattr(self.net, 'inference_session', None)
+        nets = [self.net] + ([] if self.opponent is None else [self.opponent])
+        was_training = [n.training for n in nets]
         try:
-            with session() if session is not None else contextlib.nullcontext():
+            with contextlib.ExitStack() as stack:
+                for n in nets:
+                    n.eval()
+                    if hasattr(n, 'inference_session'):
+                        stack.enter_context(n.inference_session())
                 run = self._prepare(st, G, forced, trace)
                 plies = self._play(st, run)
         finally:
-            self.net.train(was_training)
+            for n, mode in zip(nets, was_training):
+                n.train(mode)
         dev = self.env.device
         P = st['P']
         outcome, length = run['outcome'][:G].clone(), run['length'][:G].clone()
@@ -412,9 +544,22 @@ class DeviceEvaluator:
         results = {k: results[k] for k in sorted(results, reverse=True)}
         res = {'outcome': outcome, 'length': length, 'seat': seat, 'results': results, 'win_rate': wp_func(results),
                'games': G, 'plies': plies, 'env_steps': int(length.sum())}
+        if self.opponent is not None:
+            others = outcome[(torch.arange(P, device=dev) != seat.view(-1, 1))].tolist() if G else []
+            table = {}
+            for o in others:
+                table[o + 0.0] = table.get(o + 0.0, 0) + 1
+            res['opponent_results'] = {k: table[k] for k in sorted(table, reverse=True)}
+            res['opponent_win_rate'] = wp_func(res['opponent_results'])
         if run['trace'] is not None:
             res['trace'] = {k: v[:G].clone() for k, v in run['trace'].items()}
         return res
+
+    @torch.no_grad()
+    def set_opponent_state(self, state_dict):
+        """Copy weights and buffers into the opponent IN PLACE (no tensor is replaced), so the captured graphs, which
+        address them, stay valid."""
+        self.opponent.load_state_dict(state_dict)
 
     def _play(self, st, run):
         G, P = run['G'], st['P']
@@ -454,16 +599,76 @@ def eval_main(args, argv, device=None, log=print):
         if not torch.cuda.is_available():
             raise RuntimeError('handyrl_amd.main evaluates on the GPU (HIP kernels); no GPU is visible')
         device = torch.device('cuda', 0)
-    net = env.net()()
-    net.load_state_dict(torch.load(model_path, map_location='cpu', weights_only=True))
-    net = net.to(device)
-    if device.type == 'cuda':
-        from .nn import accelerate
-        accelerate(net)
+    net = load_net(env, model_path, device)
     E = max(1, min(slots, games))
     log('%d slots, %d games' % (E, games))
     ev = DeviceEvaluator(cls(E, device), net, observation=bool(targs.get('observation', False)),
                          temperature=float(targs.get('eval_temperature', 0.0)), seed=int(targs.get('seed', 0)))
     res = ev.evaluate(games)
     log('total %s %s' % (res['results'], res['win_rate']))
+    return res
+
+
+def load_net(env, model_path, device):
+    """The checkpoint ``model_path`` in ``env.net()()`` on ``device``, HIP-backed on a GPU."""
+    net = env.net()()
+    net.load_state_dict(torch.load(model_path, map_location='cpu', weights_only=True))
+    net = net.to(device)
+    if device.type == 'cuda':
+        from .nn import accelerate
+        accelerate(net)
+    return net
+
+
+def opening_plies(targs):
+    """``eval_opening_plies`` of a match (default 2).  Two greedy agents on a deterministic env play the same game
+    every time: 0 with ``eval_temperature`` 0 replays two games, one per seating."""
+    n = targs.get('eval_opening_plies')
+    return 2 if n is None else int(n)
+
+
+def eval_match_main(args, argv, device=None, log=print):
+    """``main.py --eval-match MODEL_A MODEL_B [NUM_GAMES=100] [SLOTS]``: two checkpoints in ``env.net()`` against
+    each other (the reference's match of one ``Agent`` per model, evaluation.py:64-116), agent 0 = MODEL_A on seat
+    ``g mod 2`` of game g.  train_args gives ``observation``, ``eval_temperature`` (both agents), ``eval_opening_plies``
+    and ``seed``.  Logs the reference's ``evaluate_mp`` tables (evaluation.py:233-248) -- per agent the games where
+    agent 0 moves first (``default-F``: the even game numbers, (NUM_GAMES + 1) // 2 of them), those where it moves
+    second (``default-S``) and the total, each with its win rate -- and returns the evaluator's result."""
+    from .environment import make_env, prepare_env
+    env_args = args['env_args']
+    prepare_env(env_args)
+    env = make_env(env_args)
+    cls = batched_env(type(env).__module__)
+    if cls.P != 2:
+        raise ValueError('--eval-match seats two models: %s has %d players' % (cls.__name__, cls.P))
+    targs = args.get('train_args') or {}
+    if len(argv) < 2:
+        raise ValueError('--eval-match needs two checkpoints: MODEL_A MODEL_B [NUM_GAMES] [SLOTS]')
+    games = int(argv[2]) if len(argv) >= 3 else 100
+    slots = int(argv[3]) if len(argv) >= 4 else int(targs.get('eval_slots') or 1024)
+    if device is None:
+        if not torch.cuda.is_available():
+            raise RuntimeError('handyrl_amd.main evaluates on the GPU (HIP kernels); no GPU is visible')
+        device = torch.device('cuda', 0)
+    nets = [load_net(env, path, device) for path in argv[:2]]
+    E = max(1, min(slots, games))
+    log('%d slots, %d games' % (E, games))
+    ev = DeviceEvaluator(cls(E, device), nets[0], observation=bool(targs.get('observation', False)),
+                         temperature=float(targs.get('eval_temperature', 0.0)), seed=int(targs.get('seed', 0)),
+                         opponent=nets[1], opening_plies=opening_plies(targs))
+    res = ev.evaluate(games)
+    outcome, seat = res['outcome'].tolist(), res['seat'].tolist()
+    for agent in (0, 1):
+        log('---agent %d---' % agent)
+        total = {}
+        for tag, first in (('default-F', 0), ('default-S', 1)):     # agent 0 moves first / second
+            table = {}
+            for g in range(games):
+                if seat[g] == first:
+                    o = outcome[g][seat[g] if agent == 0 else 1 - seat[g]] + 0.0
+                    table[o] = table.get(o, 0) + 1
+                    total[o] = total.get(o, 0) + 1
+            if table:
+                log('%s %s %s' % (tag, {k: table[k] for k in sorted(table, reverse=True)}, wp_func(table)))
+        log('total %s %s' % ({k: total[k] for k in sorted(total, reverse=True)}, wp_func(total)))
     return res

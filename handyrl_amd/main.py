@@ -2,6 +2,7 @@
 
     python -m handyrl_amd.main --train [config.yaml]
     python -m handyrl_amd.main --eval MODEL_PATH [NUM_GAMES] [SLOTS]
+    python -m handyrl_amd.main --eval-match MODEL_A MODEL_B [NUM_GAMES] [SLOTS]
     python -m torch.distributed.run --nproc-per-node N -m handyrl_amd.main --train [config.yaml]
 
 Reads the reference's ``config.yaml`` (main.py:13-15; config.yaml:1-35;
@@ -49,10 +50,20 @@ written) with the actors and the learner on the GPU:
 * evaluation: ``eval_rate`` > 0 in train_args makes rank 0 play the reference's per-epoch evaluation after each
   epoch's training -- the greedy model against random agents on the device (``evaluation.DeviceEvaluator``,
   ``eval_slots`` slots, ``eval_temperature``) -- and append its win rate to the epoch's log line;
-  ``--eval MODEL_PATH [NUM_GAMES] [SLOTS]`` evaluates a checkpoint (evaluation.py:291-312).
+  ``--eval MODEL_PATH [NUM_GAMES] [SLOTS]`` evaluates a checkpoint (evaluation.py:291-312);
+* matches: the win rate against random agents saturates within a few epochs, so ``eval_opponent`` in train_args
+  seats a second net on the other seats of the per-epoch evaluation instead (the reference's match of one ``Agent``
+  per model, evaluation.py:64-116): a path to a ``.pth`` is a fixed anchor loaded once, ``previous`` is the model
+  as it was at the end of the previous epoch (at the first epoch: as training started), absent or ``random`` is the
+  evaluation above.  The first ``eval_opening_plies`` plies (default 2) of every game are uniform random moves on
+  both seats: two greedy agents on a deterministic env play the same game every time, so 0 with
+  ``eval_temperature`` 0 replays two games, one per seating.  The epoch line then ends ``vs previous`` or
+  ``vs <path>``.  ``--eval-match MODEL_A MODEL_B [NUM_GAMES] [SLOTS]`` plays two checkpoints against each other
+  and prints the reference's per-agent tables (evaluation.py:233-248).  Training is bit-identical with and
+  without the key.
 
-The worker/server network plane, the network match server and client and the other CLI modes are not rebuilt
-(DESIGN.md §6).
+The worker/server network plane, the network match server and client (their match itself is ``--eval-match``) and
+the other CLI modes are not rebuilt.
 """
 
 import math
@@ -117,6 +128,27 @@ def _per_rank(n, world):
     return max(1, -(-int(n) // world))
 
 
+def _eval_opponent(env, net, spec, device):
+    """The opponent module of ``eval_opponent``: ``env.net()()`` holding ``net``'s weights (``previous``) or the
+    checkpoint ``spec``.  Constructing a net draws initial weights, so the torch RNG state is put back: training
+    draws what it draws without the key."""
+    cpu_state = torch.get_rng_state()
+    dev_state = torch.cuda.get_rng_state(device) if device.type == 'cuda' else None
+    try:
+        opponent = env.net()()
+    finally:
+        torch.set_rng_state(cpu_state)
+        if dev_state is not None:
+            torch.cuda.set_rng_state(dev_state, device)
+    opponent.load_state_dict(net.state_dict() if spec == 'previous'
+                             else torch.load(spec, map_location='cpu', weights_only=True))
+    opponent = opponent.to(device)
+    if device.type == 'cuda':
+        from .nn import accelerate
+        accelerate(opponent)
+    return opponent
+
+
 def train_main(args, device=None, loss_fn=None, model_dir='models', log=print):
     """The learner cycle of train.py:425-560 on the device; returns the trained model (CPU copy)."""
     env_args, targs = args['env_args'], {**TRAIN_DEFAULTS, **args['train_args']}
@@ -161,15 +193,23 @@ def train_main(args, device=None, loss_fn=None, model_dir='models', log=print):
                          "batched (device) form (turn_based_training without observation); this configuration is "
                          "played by the lockstep generator (self_play: lockstep)")
     evaluator = None
+    eval_vs = targs.get('eval_opponent')
     if float(targs.get('eval_rate') or 0) > 0:
         # the reference's per-epoch evaluation (train.py:519-526); an env it cannot play raises here, at start-up
-        from .evaluation import DeviceEvaluator, batched_env, eval_games
+        from .evaluation import DeviceEvaluator, batched_env, eval_games, opening_plies
         eval_cls = batched_env(module)
         eval_n = eval_games(targs['eval_rate'], targs['update_episodes'])
+        # a second net on the other seats: a checkpoint (a fixed anchor) or `previous`; a bad path raises here
+        if eval_vs not in (None, 'random', 'previous') and not os.path.isfile(str(eval_vs)):
+            raise FileNotFoundError("train_args['eval_opponent'] is random, previous or a checkpoint: no file %r"
+                                    % (eval_vs,))
         if rank == 0:
             eval_slots = max(1, min(int(targs.get('eval_slots') or eval_n), eval_n))
+            match = {}
+            if eval_vs not in (None, 'random'):
+                match = {'opponent': _eval_opponent(env, net, eval_vs, device), 'opening_plies': opening_plies(targs)}
             evaluator = DeviceEvaluator(eval_cls(eval_slots, device), net, observation=observe,
-                                        temperature=float(targs.get('eval_temperature', 0.0)), seed=seed)
+                                        temperature=float(targs.get('eval_temperature', 0.0)), seed=seed, **match)
     played = None   # a generator that reports what it emitted (stream): episodes of the last play()
     if use_device and self_play == 'stream':
         slots = int(targs.get('stream_slots') or games)
@@ -247,6 +287,10 @@ def train_main(args, device=None, loss_fn=None, model_dir='models', log=print):
             if evaluator is not None:
                 res = evaluator.evaluate(eval_n)
                 line += ', win rate %.3f (%.1f / %d)' % (res['win_rate'], res['win_rate'] * eval_n, eval_n)
+                if evaluator.opponent is not None:
+                    line += ' vs %s' % (eval_vs,)
+                    if eval_vs == 'previous':     # the next epoch's opponent: the model as it is now, in place
+                        evaluator.set_opponent_state(model.state_dict())
             log(line)
     return model
 
@@ -259,8 +303,15 @@ def main(argv=None):
         print(args)
         eval_main(args, argv[1:])
         return 0
+    if argv and argv[0] == '--eval-match':
+        from .evaluation import eval_match_main
+        args = load_config('config.yaml')
+        print(args)
+        eval_match_main(args, argv[1:])
+        return 0
     if not argv or argv[0] not in ('--train', '-t'):
-        print('usage: python -m handyrl_amd.main --train [config.yaml] | --eval MODEL_PATH [NUM_GAMES] [SLOTS]')
+        print('usage: python -m handyrl_amd.main --train [config.yaml] | --eval MODEL_PATH [NUM_GAMES] [SLOTS] | '
+              '--eval-match MODEL_A MODEL_B [NUM_GAMES] [SLOTS]')
         return 1
     args = load_config(argv[1] if len(argv) > 1 else 'config.yaml')
     print(args)

@@ -171,7 +171,7 @@ int hrl_masked_rows_copy(int nleaves, float *const *dst, const int64_t *dst_stri
  *     bytes.  At ply t of game g: action = the move played, picked = the evaluator's own decision even where a move
  *     was forced, model_ply = 1 and policy = p at a model ply (policy is not stored at a random-seat ply).
  *
- * All three entries are asynchronous on `stream`, allocate nothing, read nothing on the host (graph-capturable) and
+ * All entries are asynchronous on `stream`, allocate nothing, read nothing on the host (graph-capturable) and
  * validate before any HIP call: HRL_EINVAL for a NULL required pointer, E < 0, A < 1, Tm < 1, P < 1, G < 0,
  * logit_stride < A (and: mover outside [0, P), temperature < 0 or NaN, some but not all trace buffers); E == 0:
  * HRL_OK, no launch. */
@@ -186,6 +186,30 @@ int hrl_eval_act(const float *logits, int64_t logit_stride, const uint8_t *legal
                  const int64_t *forced, int64_t E, int64_t A, int64_t Tm, int64_t P, int64_t G, int64_t *action,
                  int64_t *trace_action, int64_t *trace_picked, float *trace_policy, uint8_t *trace_model_ply,
                  void *stream);
+
+/* hrl_eval_act for a match of two nets (evaluation.DeviceEvaluator with an opponent; the reference seats one Agent per
+ * model in exec_match, handyrl/evaluation.py:64-116).  One launch per ply of the same form; logits_home / logits_opp
+ * (E, >= A) fp32 rows of stride stride_home / stride_opp.  For an active slot with game g and ply t in range:
+ *   The mover's net is home where seat[e] == mover, otherwise opp, or no net when logits_opp is NULL.
+ *   Where t < opening, or where the mover has no net, pick = eval_pick(seed, g, t, legal): the rule above, bit for bit.
+ *   Otherwise pick comes from that net's own row and that net's own temperature: at temperature 0 the argmax of
+ *     p = logits - (legal ? 0 : 1e32), ties to the lowest label, NaN first; at temperature > 0 the argmax of
+ *     p * (float)(1.0 / temperature) - log(-log(u)) with u of the streaming rule for (seed, g, t, label).  Only one
+ *     agent moves at a given (g, t), so both agents share the one stream.
+ *   forced[g][t] >= 0 overrides the move played, not `picked`.
+ *   Trace: policy[g][t] = p whenever the mover has a net, opening plies included; model_ply[g][t] = (seat == mover);
+ *     action and picked as for hrl_eval_act.
+ *   Which rows the evaluator feeds: the home net sees the board from `seat`; the opponent sees it from the mover's seat
+ *     where the mover is not home and from seat (seat + 1) mod P otherwise (for P == 2: always the other seat).
+ * An inactive, retired or out-of-range slot gets action[e] = 0 and no other store.  With logits_opp == NULL and
+ * opening == 0 every output equals hrl_eval_act's bit for bit.  HRL_EINVAL as for hrl_eval_act, and for
+ * stride_home < A, stride_opp < A when logits_opp is given, either temperature < 0 or NaN, opening < 0. */
+int hrl_match_act(const float *logits_home, int64_t stride_home, const float *logits_opp, int64_t stride_opp,
+                  const uint8_t *legal, uint64_t seed, double temperature_home, double temperature_opp,
+                  int64_t opening, const int64_t *game, const int64_t *ply, const uint8_t *active,
+                  const int64_t *seat, int64_t mover, const int64_t *forced, int64_t E, int64_t A, int64_t Tm,
+                  int64_t P, int64_t G, int64_t *action, int64_t *trace_action, int64_t *trace_picked,
+                  float *trace_policy, uint8_t *trace_model_ply, void *stream);
 
 /* After the env's step, one launch of one workgroup.  For every active slot: ply += 1 and
  * done = terminal[e] != 0 || ply >= Tm.  A done slot stores outcome_out[game] = outcome[e] ((G, P) and (E, P) fp32)

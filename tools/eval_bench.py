@@ -4,11 +4,18 @@
     python tools/eval_bench.py --profile --config geister --calls 2
                   (the program of a separate `rocprofv3 --kernel-trace --stats -- python ...` run: a fixed number of
                    evaluate() calls after warm-up, no timing; prints the plies it ran)
+    python tools/eval_bench.py --match [--config ...] [--seconds 3] [--repeats 3] [--out FILE]
+                  (a match of the net against a copy of itself with two opening plies, the unchanged evaluator against
+                   random agents and one eval-mode forward of the net at E rows, alternating in one call; --profile
+                   --match is the match's kernel-trace program)
     python tools/eval_bench.py --reference PATH [--games 20]
                   (context, on the CPU: the rate of the reference's one-process exec_match, greedy Agent against
                    RandomAgent, from the HandyRL tree at PATH)
 
   eval      ``DeviceEvaluator(E slots).evaluate(G)``: TicTacToe E = 4096, G = 16384; Geister E = 2048, G = 4096
+  match     ``DeviceEvaluator(E slots, opponent=copy of the net, opening_plies=2).evaluate(G)``, same E and G; its
+            yardstick is the ``eval`` ply plus one ``forward`` (the match adds the opponent's forward and, for a
+            recurrent net, one state advance); ``forward`` reports ms per forward as its ms per ply
   baseline  TicTacToe: ``loop.evaluate_vs_random(games=4096)`` (the lockstep torch loop, nine plies per call);
             Geister: the lockstep ``DeviceGenerator.generate()`` ply at E = 2048, which runs the same forward
 
@@ -20,6 +27,7 @@ the ``--profile`` run's kernel trace: every kernel's call count over the plies o
 """
 
 import argparse
+import contextlib
 import json
 import os
 import statistics
@@ -32,7 +40,8 @@ sys.path.insert(0, ROOT)
 CONFIGS = {'tictactoe': (4096, 16384), 'geister': (2048, 4096)}   # env: slots E, games G
 
 
-def build(env, dev):
+def build(env, dev, match=False):
+    import copy
     import torch
     from handyrl_amd.evaluation import DeviceEvaluator
     from handyrl_amd.nn import accelerate
@@ -62,7 +71,29 @@ def build(env, dev):
     def evaluate():
         res = ev.evaluate(G)
         return G, res['plies']
-    return {'eval': evaluate, 'baseline': baseline}, cls, net
+    if not match:
+        return {'eval': evaluate, 'baseline': baseline}, cls, net
+    mv = DeviceEvaluator(cls(E, dev), net, seed=1, opponent=copy.deepcopy(net), opening_plies=2)
+
+    def play_match():
+        res = mv.evaluate(G)
+        return G, res['plies']
+    board = cls(E, dev)
+    board.reset()
+    obs = board.observation(torch.arange(E, device=dev) % cls.P)
+    hidden = None
+    if hasattr(net, 'inference_hidden'):
+        hidden = tuple([x[0] for x in leaf] for leaf in net.inference_hidden(E, 1, dev))
+    elif hasattr(net, 'init_hidden'):
+        hidden = net.init_hidden([E])
+
+    def forward(n=64):
+        with torch.no_grad(), net.inference_session() if hasattr(net, 'inference_session') \
+                else contextlib.nullcontext():
+            for _ in range(n):
+                net(obs, hidden)
+        return 0, n
+    return {'match': play_match, 'eval': evaluate, 'forward': forward}, cls, net
 
 
 def leg(call, seconds, sync):
@@ -79,10 +110,10 @@ def leg(call, seconds, sync):
     return {'games_per_s': sum(games) / dt, 'ms_per_ply': 1e3 * dt / plies, 'calls': len(games), 'seconds': dt}
 
 
-def measure(env, seconds, repeats):
+def measure(env, seconds, repeats, match=False):
     import torch
     dev = torch.device('cuda', 0)
-    calls, cls, net = build(env, dev)
+    calls, cls, net = build(env, dev, match)
     sync = lambda: torch.cuda.synchronize(dev)   # noqa: E731
     for _ in range(2):
         for c in calls.values():
@@ -99,22 +130,28 @@ def measure(env, seconds, repeats):
             v = [l[q] for l in ls]
             out[k][q] = {'median': statistics.median(v), 'min': min(v), 'max': max(v)}
         out[k]['calls'] = [l['calls'] for l in ls]
-    out['ply_eval_over_baseline'] = out['eval']['ms_per_ply']['median'] / out['baseline']['ms_per_ply']['median']
+    if match:
+        yard = out['eval']['ms_per_ply']['median'] + out['forward']['ms_per_ply']['median']
+        out['yardstick_ms_per_ply'] = yard
+        out['ply_match_over_yardstick'] = out['match']['ms_per_ply']['median'] / yard
+    else:
+        out['ply_eval_over_baseline'] = out['eval']['ms_per_ply']['median'] / out['baseline']['ms_per_ply']['median']
     return out
 
 
-def profile_run(env, n):
+def profile_run(env, n, match=False):
     import torch
     dev = torch.device('cuda', 0)
-    calls, _, _ = build(env, dev)
+    calls, _, _ = build(env, dev, match)
+    which = 'match' if match else 'eval'
     for _ in range(2):
-        calls['eval']()
+        calls[which]()
     torch.cuda.synchronize(dev)
     plies = 0
     for _ in range(n):
-        plies += calls['eval']()[1]
+        plies += calls[which]()[1]
     torch.cuda.synchronize(dev)
-    print(json.dumps({'profile': 'eval', 'config': env, 'calls': n, 'plies': plies}))
+    print(json.dumps({'profile': which, 'config': env, 'calls': n, 'plies': plies}))
 
 
 def reference(path, games):
@@ -146,6 +183,7 @@ def main():
     ap.add_argument('--seconds', type=float, default=3.0)
     ap.add_argument('--repeats', type=int, default=3)
     ap.add_argument('--profile', action='store_true')
+    ap.add_argument('--match', action='store_true')
     ap.add_argument('--calls', type=int, default=2)
     ap.add_argument('--reference')
     ap.add_argument('--games', type=int, default=20)
@@ -160,9 +198,9 @@ def main():
     configs = list(CONFIGS) if a.config == 'all' else [a.config]
     for env in configs:
         if a.profile:
-            profile_run(env, a.calls)
+            profile_run(env, a.calls, a.match)
             continue
-        line = json.dumps(measure(env, a.seconds, a.repeats))
+        line = json.dumps(measure(env, a.seconds, a.repeats, a.match))
         print(line, flush=True)
         if a.out:
             with open(a.out, 'a') as f:
