@@ -284,6 +284,12 @@ SIGNATURES = {
                                        ctypes.c_void_p, _f32p, ctypes.c_void_p, ctypes.c_void_p]),
     'hrl_masked_rows_fill': (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                             ctypes.c_void_p, _i64, ctypes.c_void_p]),
+    'hrl_league_finish': (ctypes.c_int, [ctypes.c_void_p, _f32p, _i64, _i64, _i64, _i64, _i64, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _f32p,
+                                         ctypes.c_void_p, ctypes.c_void_p]),
+    'hrl_rows_permute': (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _i64,
+                                        ctypes.c_void_p]),
     'hrl_replay_gather': (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_void_p, _i64, _i64, ctypes.c_void_p, ctypes.c_void_p]),
     'hrl_replay_draw': (ctypes.c_int, [_f32p, _i64, _i64, _i64, _i64, _i64, ctypes.c_void_p, _i64, _i64,

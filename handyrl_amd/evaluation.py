@@ -23,6 +23,10 @@ train_args) seats a second net on the other seats, as the reference's ``exec_mat
 (evaluation.py:64-116); the vs-random win rate saturates within a few epochs, a match against a checkpoint does not.
 Each agent has its own temperature, and the first ``opening_plies`` plies of a game are ``eval_pick`` on every seat.
 
+A league (``LeagueEvaluator``, ``main.py --eval-league``) plays a round robin of K nets, every pairing's games being
+those of the match above, with each net forwarded only over the rows where it moves, and rates the agents with
+``bradley_terry``; include/hrl_env.h has its rules.
+
 ``FUSED_EVAL``: on a GPU the ply's decision and bookkeeping are the launches of hrl_eval_act (hrl_match_act in a
 match), hrl_eval_finish and hrl_masked_rows_fill (csrc/hrl_eval.hip); the torch formulation below is the CPU path and
 the form the kernels are tested against.
@@ -39,10 +43,13 @@ from .rollout import _M32, _PHILOX_M, _PHILOX_W, _leaves, philox4x32, stream_uni
 from .util import map_r
 
 __all__ = ['DeviceEvaluator', 'eval_pick', 'eval_pick_torch', 'eval_main', 'eval_match_main', 'wp_func', 'eval_games',
-           'batched_env']
+           'batched_env', 'LeagueEvaluator', 'bradley_terry', 'eval_league_main']
 
 # True: on a GPU the three steps are HIP launches; False (or a CPU env): the torch ops below, bit-identical.
 FUSED_EVAL = True
+# The league's own two steps (hrl_league_finish, hrl_rows_permute; csrc/hrl_league.hip) and its use of hrl_match_act
+# and hrl_masked_rows_fill: True: HIP launches on a GPU; False (or a CPU env): league_finish_torch, rows_permute_torch.
+FUSED_LEAGUE = True
 
 _PICK_WORD = 0xffffffff   # the counter's last word: disjoint from stream_uniforms' a // 4 (A <= 2**20)
 
@@ -319,6 +326,85 @@ def rows_fill_hip(leaves, mask):
         _native.stream_of(mask.device)), 'hrl_masked_rows_fill')
 
 
+def league_finish_torch(st, terminal, outcome, G, outcome_out, length_out):
+    """hrl_league_finish: ``finish_torch`` with the block rule.  Slot e belongs to block e // S and its next game is
+    game + S; the seat is not touched.  ``outcome_out`` (Q * G + 1, P) and ``length_out`` (Q * G + 1,) are indexed by
+    block * G + game; the last row takes the stores of the slots that store nothing."""
+    game, ply, active, pending, state = (st[k] for k in ('game', 'ply', 'active', 'pending', 'state'))
+    Tm, S = st['Tm'], st['S']
+    E = game.shape[0]
+    ply.add_(active)
+    done = active & (terminal | (ply >= Tm))
+    block = torch.arange(E, device=game.device) // S
+    idx = torch.where(done & (game >= 0) & (game < G), block * G + game, (E // S) * G)
+    outcome_out[idx] = outcome.float()
+    length_out[idx] = ply
+    n = game + S
+    again = done & (n < G)
+    game.copy_(torch.where(done, torch.where(again, n, G), game))
+    ply.masked_fill_(done, 0)
+    pending.copy_(torch.where(done, again, pending))
+    active.logical_and_(~done)
+    state[0:1].add_(done.sum())
+
+
+def league_finish_hip(st, terminal, outcome, G, outcome_out, length_out):
+    """league_finish_torch as ONE launch of one workgroup (hrl_league_finish); the kernel needs no spare row."""
+    from . import _native
+    E, P, S = st['game'].shape[0], st['P'], st['S']
+    terminal, outcome = terminal.contiguous(), outcome.float().contiguous()
+    assert terminal.shape == (E,) and terminal.dtype == torch.bool and outcome.shape == (E, P)
+    assert S >= 2 and S % 2 == 0 and E % S == 0
+    rows = (E // S) * G
+    assert outcome_out.shape[0] >= rows and outcome_out.shape[1] == P and outcome_out.dtype == torch.float32
+    assert length_out.shape[0] >= rows and length_out.dtype == torch.long
+    assert outcome_out.is_contiguous() and length_out.is_contiguous()
+    for k in ('game', 'ply'):
+        assert st[k].shape == (E,) and st[k].dtype == torch.long and st[k].is_contiguous()
+    for k in ('active', 'pending'):
+        assert st[k].shape == (E,) and st[k].dtype == torch.bool
+    assert st['state'].shape == (1,) and st['state'].dtype == torch.long
+    _native.check(_native.load().hrl_league_finish(
+        _native.ptr(terminal), _native.ptr(outcome), E, S, st['Tm'], P, G, _native.ptr(st['active']),
+        _native.ptr(st['ply']), _native.ptr(st['game']), _native.ptr(st['pending']), _native.ptr(st['state']),
+        _native.ptr(outcome_out), _native.ptr(length_out), _native.stream_of(terminal.device)), 'hrl_league_finish')
+
+
+def rows_permute_torch(dst, src, src_index=None, dst_index=None, n=None):
+    """Row dst_index[r] of dst[l] = row src_index[r] of src[l], r < n, for every leaf pair; a None index is the
+    identity.  ``n`` defaults to the index length."""
+    if n is None:
+        n = (src_index if src_index is not None else dst_index).shape[0]
+    for d, s in zip(dst, src):
+        x = s[:n] if src_index is None else s.index_select(0, src_index[:n])
+        if dst_index is None:
+            d[:n].copy_(x)
+        else:
+            d.index_copy_(0, dst_index[:n], x)
+
+
+def rows_permute_hip(dst, src, src_index=None, dst_index=None, n=None):
+    """rows_permute_torch in ONE launch for up to 16 fp32 leaves (hrl_rows_permute); leaves (rows, *shape) with
+    contiguous rows and any row stride.  The indices are not read here: the caller keeps them in range."""
+    from . import _native
+    if n is None:
+        n = (src_index if src_index is not None else dst_index).shape[0]
+    assert len(dst) == len(src)
+    for ix in (src_index, dst_index):
+        assert ix is None or (ix.dtype == torch.long and ix.is_contiguous() and ix.dim() == 1 and ix.shape[0] >= n)
+    F = []
+    for d, s in zip(dst, src):
+        assert d.is_cuda and d.dtype == torch.float32 and s.dtype == torch.float32 and d.shape[1:] == s.shape[1:]
+        assert (src_index is not None or s.shape[0] >= n) and (dst_index is not None or d.shape[0] >= n)
+        assert n == 0 or (d[0].is_contiguous() and s[0].is_contiguous())
+        F.append(max(1, d[0].numel()) if d.shape[0] else 1)
+    _native.check(_native.load().hrl_rows_permute(
+        len(dst), _native.ptr_array(dst), _native.i64_array([max(d.stride(0), f) for d, f in zip(dst, F)]),
+        _native.ptr_array(src), _native.i64_array([max(s.stride(0), f) for s, f in zip(src, F)]),
+        _native.i64_array(F), _native.ptr(src_index), _native.ptr(dst_index), int(n),
+        _native.stream_of(dst[0].device)), 'hrl_rows_permute')
+
+
 class DeviceEvaluator:
     """Plays ``games`` games of ``net`` (``Agent(model, observation, temperature)``, agent.py:55-110) against
     uniform random agents (``RandomAgent``) on the E slots of ``env_batch`` (TicTacToeBatch, GeisterBatch,
@@ -580,6 +666,436 @@ class DeviceEvaluator:
                 return s
             if s > limit:
                 raise RuntimeError('evaluation did not finish %d games in %d steps' % (G, s))
+
+
+def _connected(K, pairs):
+    """Every agent reaches every other over the played pairs."""
+    seen, todo = {0}, [0]
+    while todo:
+        a = todo.pop()
+        for i, j in pairs:
+            for x, y in ((i, j), (j, i)):
+                if x == a and y not in seen:
+                    seen.add(y)
+                    todo.append(y)
+    return len(seen) == K
+
+
+def bradley_terry(score, games):
+    """Ratings of K agents from a cross table, as Elo (400 log10 gamma, mean 0), (K,) fp64.
+
+    ``score[i][j]`` is i's score in its ``games[i][j]`` games against j (a win 1, a draw 1/2).  Every played pair gets
+    one virtual drawn game (0.5 to both scores, 1 to the count), so an agent that won or lost everything keeps a finite
+    rating.  The Bradley-Terry strengths are fitted on the host in fp64 by the MM iteration
+    gamma_i <- W_i / sum_j n_ij / (gamma_i + gamma_j), W_i the agent's total score, every agent updated from the
+    previous sweep's strengths, renormalised to geometric mean 1 after each sweep, until the largest relative change
+    is below 1e-12 (or 10,000 sweeps).  A pairing graph that is not connected has no common scale: ValueError."""
+    s = torch.as_tensor(score, dtype=torch.float64).cpu().clone()
+    n = torch.as_tensor(games, dtype=torch.float64).cpu().clone()
+    K = s.shape[0]
+    if s.shape != (K, K) or n.shape != (K, K):
+        raise ValueError('score and games are (K, K) tables, not %s and %s' % (tuple(s.shape), tuple(n.shape)))
+    n.fill_diagonal_(0)
+    s.fill_diagonal_(0)
+    n = torch.maximum(n, n.t())
+    played = n > 0
+    pairs = [(i, j) for i in range(K) for j in range(i + 1, K) if bool(played[i, j])]
+    if K < 1 or not _connected(K, pairs):
+        raise ValueError('the pairings do not connect every agent to every other: the ratings have no common scale')
+    s = s + 0.5 * played
+    n = n + played
+    W = s.sum(1)
+    gamma = torch.ones(K, dtype=torch.float64)
+    for _ in range(10000):
+        new = W / (n / (gamma.view(-1, 1) + gamma.view(1, -1))).sum(1) if K > 1 else gamma.clone()
+        new = new / torch.exp(torch.log(new).mean())
+        change = float(((new - gamma).abs() / gamma).max())
+        gamma = new
+        if change < 1e-12:
+            break
+    elo = 400.0 * torch.log10(gamma)
+    return elo - elo.mean()
+
+
+class LeagueEvaluator:
+    """A round robin of K nets on the E slots of ``env_batch`` (an alternating env with two players): every pairing
+    (i, j) plays ``games`` games, and game g of the pairing is the game g that
+    ``DeviceEvaluator(env, nets[i], opponent=nets[j], observation=, temperature=, opening_plies=, seed=)`` plays.
+
+    ``pairings``: None is every (i, j) with i < j in lexicographic order, or a list of pairs (i != j, each unordered
+    pair once); the first agent of a pair is its home agent, on seat g mod 2 of game g.  Pairing q owns the S = E / Q
+    slots from q * S; S is even, so slot t of a block always seats the home agent on t mod 2 and plays the game numbers
+    t, t + S, ... below G.  The rows where a net moves at a mover parity are therefore fixed for the run: each ply the
+    observation leaves go into net-major order in one launch (hrl_rows_permute), each net runs once over its own
+    rows only (E rows in all; with ``observation=True`` every net runs over every slot it sits in, from its own seat:
+    2 E rows), the logits return to slot order in one launch and hrl_match_act decides as in a match, both logit
+    pointers at the one buffer.  A net keeps one recurrent-state row per slot it sits in, its rows of one seat
+    contiguous: the rows it moves on are a view that the net advances (GeisterNet in place inside its session), the
+    rows of a restarting slot are zeroed.  On a GPU each mover's ply is one captured graph, the K forwards one after
+    another on one stream.  Eval mode, inference sessions and training modes are put back; no torch generator is drawn
+    from; the host reads the one-word device state every ``check_every`` steps and nothing else.
+    """
+
+    def __init__(self, env_batch, nets, pairings=None, observation=False, temperature=0.0, opening_plies=0, seed=0,
+                 check_every=16, graph=None):
+        _check_env(type(env_batch))
+        if env_batch.P != 2:
+            raise ValueError('a league seats two nets per game: %s has %d players'
+                             % (type(env_batch).__name__, env_batch.P))
+        nets = list(nets)
+        K = len(nets)
+        if K < 2:
+            raise ValueError('a league needs at least two nets, not %d' % K)
+        if len({id(n) for n in nets}) != K:
+            raise ValueError('every agent must be a module of its own (a copy of a net plays against it)')
+        if not temperature >= 0:
+            raise ValueError('temperature must be >= 0, not %r' % (temperature,))
+        if int(opening_plies) < 0:
+            raise ValueError('opening_plies must be >= 0, not %r' % (opening_plies,))
+        if pairings is None:
+            pairings = [(i, j) for i in range(K) for j in range(i + 1, K)]
+        pairings = [(int(i), int(j)) for i, j in pairings]
+        for i, j in pairings:
+            if not (0 <= i < K and 0 <= j < K) or i == j:
+                raise ValueError('a pairing is (i, j) with i != j, both agents in 0 .. %d, not %r' % (K - 1, (i, j)))
+        if len({frozenset(p) for p in pairings}) != len(pairings) or not pairings:
+            raise ValueError('each unordered pair of agents may appear once in the pairings, and one at least')
+        if not _connected(K, pairings):
+            raise ValueError('the pairings do not connect every agent to every other: the ratings have no common '
+                             'scale')
+        Q = len(pairings)
+        if env_batch.E <= 0 or env_batch.E % (2 * Q) != 0:
+            raise ValueError('env_batch.E must be a positive multiple of 2Q = %d (Q = %d pairings, an even number of '
+                             'slots each), not %d' % (2 * Q, Q, env_batch.E))
+        self.env, self.nets, self.pairings = env_batch, nets, pairings
+        self.K, self.Q, self.S = K, Q, env_batch.E // Q
+        self.observation, self.temperature = bool(observation), float(temperature)
+        self.opening_plies = int(opening_plies)
+        self.seed = int(seed) & 0xffffffffffffffff
+        self.check_every = max(1, int(check_every or 1))
+        self.graph = graph
+        self._st = None
+        self._run = None
+
+    def _use_graph(self):
+        dev = torch.device(self.env.device)
+        return dev.type == 'cuda' and (self.graph is None or bool(self.graph))
+
+    def _layout(self):
+        """The fixed routes.  rows[k][s]: the slots where agent k sits on seat s, ascending.  Net-major order is agent
+        by agent; without observation, at mover m, agent k's rows are rows[k][m]; with it, rows[k][0] then rows[k][1]
+        at both movers (the state's own layout)."""
+        K, S, E = self.K, self.S, self.env.E
+        rows = [([], []) for _ in range(K)]
+        for e in range(E):
+            (i, j), t = self.pairings[e // S], e % S
+            rows[i][t % 2].append(e)
+            rows[j][1 - t % 2].append(e)
+        lay = {'rows': rows, 'count': [len(r[0]) + len(r[1]) for r in rows], 'total': E}
+        # the movers' rows at mover m, agent by agent (the order of the logits, in both modes), and its inverse
+        lay['span'], lay['order'], lay['back'] = [[], []], [[], []], [[0] * E, [0] * E]
+        for m in (0, 1):
+            off = 0
+            for k in range(K):
+                lay['span'][m].append((off, off + len(rows[k][m])))
+                for e in rows[k][m]:
+                    lay['order'][m].append(e)
+                    lay['back'][m][e] = off
+                    off += 1
+            assert off == E
+        if self.observation:
+            # one order for both movers: agent k's block is [its seat-0 slots, its seat-1 slots] (its state's layout)
+            lay['span'] = [[], []]
+            lay['seat_src'], lay['seat_dst'] = [[], []], [[], []]
+            off = 0
+            for k in range(K):
+                for m in (0, 1):
+                    lay['span'][m].append((off, off + lay['count'][k]))
+                for s in (0, 1):
+                    for e in rows[k][s]:
+                        lay['seat_src'][s].append(e)
+                        lay['seat_dst'][s].append(off)
+                        off += 1
+            lay['total'] = off
+        return lay
+
+    def _state(self):
+        if self._st is not None:
+            return self._st
+        env, E, dev, S = self.env, self.env.E, self.env.device, self.S
+        cuda = torch.device(dev).type == 'cuda'
+        lay = self._layout()
+
+        def index(values, rows):
+            assert all(0 <= v < rows for v in values)     # hrl_rows_permute does not read its indices: checked here
+            return torch.tensor(values, dtype=torch.long, device=dev)
+        t = torch.arange(E, device=dev) % S
+        st = {'Tm': env.MAX_PLIES, 'P': 2, 'S': S, 'cuda': cuda, 'lay': lay, 'slot': t,
+              'game': torch.zeros(E, dtype=torch.long, device=dev), 'ply': torch.zeros(E, dtype=torch.long, device=dev),
+              'seat': (t % 2).contiguous(), 'active': torch.zeros(E, dtype=torch.bool, device=dev),
+              'pending': torch.zeros(E, dtype=torch.bool, device=dev),
+              'state': torch.zeros(1, dtype=torch.long, device=dev),
+              'views': [torch.full((E,), s, dtype=torch.long, device=dev) for s in (0, 1)],
+              'back': [index(b, E) for b in lay['back']],
+              'logits': torch.zeros(E, env.A, device=dev)}
+        if self.observation:
+            st['seat_src'] = [index(x, E) for x in lay['seat_src']]
+            st['seat_dst'] = [index(x, lay['total']) for x in lay['seat_dst']]
+        else:
+            st['order'] = [index(x, E) for x in lay['order']]
+        # the observation leaves in net-major order, written by the route every ply
+        probe = env.observation(st['views'][0])
+        st['obs'] = map_r(probe, lambda x: torch.zeros(lay['total'], *x.shape[1:], dtype=x.dtype, device=dev))
+        # one state row per net per slot it sits in: [its seat-0 slots, its seat-1 slots]
+        st['hidden'], st['inplace'] = [], []
+        for k, net in enumerate(self.nets):
+            n = lay['count'][k]              # >= S: the pairings connect every agent
+            h, inplace = None, False
+            if hasattr(net, 'inference_hidden') and cuda:
+                h = map_r(net.inference_hidden(n, 1, dev), lambda x: x[0])
+                inplace = hasattr(net, 'inference_session')
+            elif hasattr(net, 'init_hidden'):
+                h = map_r(net.init_hidden([n]), lambda x: x.to(dev).contiguous())
+            st['hidden'].append(h)
+            st['inplace'].append(inplace)
+        # the slot of every state row, all nets one after another: a restarting slot's rows by one index op
+        st['row_slot'] = index([e for k in range(self.K) for s in (0, 1) for e in lay['rows'][k][s]], E)
+        self._st = st
+        return st
+
+    def _begin(self, st, run):
+        """Every buffer as at the start of a call: slot t of every block plays game t (t < G) or is retired."""
+        G = run['G']
+        self.env.reset()
+        st['game'].copy_(torch.clamp(st['slot'], max=G))
+        st['active'].copy_(st['slot'] < G)
+        st['ply'].zero_()
+        st['pending'].zero_()
+        st['state'].zero_()
+        for h in st['hidden']:
+            if h is not None:
+                map_r(h, lambda x: x.zero_())
+        run['outcome'].zero_()
+        run['length'].zero_()
+
+    def _ply(self, st, run, mover):
+        """One global step with mover ``mover`` = s % 2."""
+        env, lay = self.env, st['lay']
+        fused = FUSED_LEAGUE and st['cuda']
+        permute = rows_permute_hip if fused else rows_permute_torch
+        active, pending = st['active'], st['pending']
+        if mover == 0:
+            # finished games restart here only, so that s % 2 is the mover of every live game
+            env.reset_where(pending)
+            if any(h is not None for h in st['hidden']):
+                gone, off = pending.index_select(0, st['row_slot']), 0
+                for k, h in enumerate(st['hidden']):
+                    if h is not None:
+                        (rows_fill_hip if fused else rows_fill_torch)(_leaves(h), gone[off:off + lay['count'][k]])
+                    off += lay['count'][k]
+            active.logical_or_(pending)
+            pending.zero_()
+        # the route in: the observation leaves into net-major order
+        dst = _leaves(st['obs'])
+        if self.observation:
+            for s in (0, 1):
+                permute(dst, _leaves(env.observation(st['views'][s])), st['seat_src'][s], st['seat_dst'][s])
+        else:
+            permute(dst, _leaves(env.observation(st['views'][mover])), st['order'][mover], None)
+        # every net once, over its own rows; its state rows are a view, which it advances
+        policies = []
+        for k, net in enumerate(self.nets):
+            lo, hi = lay['span'][mover][k]
+            h = st['hidden'][k]
+            if h is not None and not self.observation:
+                half = lay['count'][k] // 2
+                h = map_r(h, lambda x: x[mover * half:(mover + 1) * half])
+            out = net(map_r(st['obs'], lambda x: x[lo:hi]), h)
+            if h is not None:
+                for d, x in zip(_leaves(h), _leaves(out['hidden'])):
+                    if not (d.data_ptr() == x.data_ptr() and d.stride() == x.stride()):
+                        d.copy_(x)
+            p = out['policy'][:, :env.A].float()
+            if self.observation:      # the rows it moves on: its seat-`mover` half
+                half = lay['count'][k] // 2
+                p = p[mover * half:(mover + 1) * half]
+            policies.append(p)
+        # the route out: the movers' logits, agent by agent, back into slot order
+        permute([st['logits']], [torch.cat(policies)], st['back'][mover], None)
+        act = match_act_hip if fused else match_act_torch
+        a = act(st, st['logits'], st['logits'], env.legal(), mover, self.seed, self.temperature, self.temperature,
+                self.opening_plies, run['G'])
+        env.step(a, active)
+        finish = league_finish_hip if fused else league_finish_torch
+        finish(st, env.terminal(), env.outcome(), run['G'], run['outcome'], run['length'])
+
+    def _capture(self, st, run):
+        """One graph per mover, the K forwards one after another on the capturing stream (no parallel branches);
+        warm-up plies run first on a side stream.  ``_begin`` then starts the call afresh."""
+        dev = torch.device(self.env.device)
+        self._begin(st, run)
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            for m in range(2):
+                self._ply(st, run, m)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        graphs, pool = {}, None
+        for m in range(2):
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, pool=pool):
+                self._ply(st, run, m)
+            pool = g.pool()
+            graphs[m] = g
+        return graphs
+
+    def _prepare(self, st, G):
+        dev = self.env.device
+        key = (G, FUSED_LEAGUE, self._use_graph()) + tuple(
+            t.data_ptr() for n in self.nets for t in list(n.parameters()) + list(n.buffers()))
+        if self._run is None or self._run['key'] != key:
+            rows = self.Q * G + 1
+            run = {'key': key, 'G': G, 'graphs': None, 'outcome': torch.zeros(rows, 2, device=dev),
+                   'length': torch.zeros(rows, dtype=torch.long, device=dev)}
+            self._run = run
+            if self._use_graph() and G > 0:
+                run['graphs'] = self._capture(st, run)
+        return self._run
+
+    def _play(self, st, run):
+        G = run['G']
+        if G == 0:
+            return 0
+        self._begin(st, run)
+        graphs = run['graphs']
+        s = 0
+        limit = (-(-G // min(self.S, G)) + 1) * (st['Tm'] + 2) + self.check_every
+        while True:
+            for _ in range(self.check_every):
+                if graphs is not None:
+                    graphs[s % 2].replay()
+                else:
+                    self._ply(st, run, s % 2)
+                s += 1
+            if int(st['state'][0]) >= self.Q * G:
+                return s
+            if s > limit:
+                raise RuntimeError('the league did not finish %d games in %d steps' % (self.Q * G, s))
+
+    @torch.no_grad()
+    def evaluate(self, games):
+        """Play game numbers 0 .. games-1 of every pairing.  Returns {'pairings': the pairs played; 'outcome'
+        (Q, G, 2) fp32 and 'length' (Q, G): per pairing and game; 'score' (K, K) fp64: score[i][j] = the sum of
+        (outcome_i + 1) / 2 over i's games against j; 'games' (K, K) counts; 'win_rate' (K,): ``wp_func`` over
+        everything the agent played; 'rating' (K,): ``bradley_terry(score, games)``; 'plies' (global steps run),
+        'env_steps' (the sum of the lengths)}."""
+        G = int(games)
+        if G < 0:
+            raise ValueError('games must be >= 0')
+        st = self._state()
+        was_training = [n.training for n in self.nets]
+        try:
+            with contextlib.ExitStack() as stack:
+                for n, inplace in zip(self.nets, st['inplace']):
+                    n.eval()
+                    if hasattr(n, 'inference_session'):
+                        stack.enter_context(n.inference_session(inplace_state=True) if inplace
+                                            else n.inference_session())
+                run = self._prepare(st, G)
+                plies = self._play(st, run)
+        finally:
+            for n, mode in zip(self.nets, was_training):
+                n.train(mode)
+        K, Q = self.K, self.Q
+        outcome = run['outcome'][:Q * G].view(Q, G, 2).clone()
+        length = run['length'][:Q * G].view(Q, G).clone()
+        o = outcome.cpu().double()
+        home = torch.arange(G) % 2
+        score = torch.zeros(K, K, dtype=torch.float64)
+        count = torch.zeros(K, K, dtype=torch.long)
+        tables = [{} for _ in range(K)]
+        for q, (i, j) in enumerate(self.pairings):
+            mine = o[q].gather(1, home.view(-1, 1)).view(-1)
+            theirs = o[q].gather(1, (1 - home).view(-1, 1)).view(-1)
+            score[i, j] += ((mine + 1) / 2).sum()
+            score[j, i] += ((theirs + 1) / 2).sum()
+            count[i, j] += G
+            count[j, i] += G
+            for k, values in ((i, mine), (j, theirs)):
+                for v in values.tolist():
+                    tables[k][v + 0.0] = tables[k].get(v + 0.0, 0) + 1
+        win_rate = torch.tensor([wp_func(t) for t in tables], dtype=torch.float64)
+        rating = bradley_terry(score, count) if G > 0 else torch.zeros(K, dtype=torch.float64)
+        return {'pairings': list(self.pairings), 'outcome': outcome, 'length': length, 'score': score, 'games': count,
+                'win_rate': win_rate, 'rating': rating, 'plies': plies, 'env_steps': int(length.sum())}
+
+
+def league_paths(argv):
+    """The checkpoints of ``--eval-league``: a directory expands to its ``<integer>.pth`` files in ascending epoch
+    order, a file is itself; anything else raises FileNotFoundError."""
+    paths = []
+    for p in argv:
+        if os.path.isdir(p):
+            epochs = sorted(int(f[:-4]) for f in os.listdir(p) if f.endswith('.pth') and f[:-4].isdigit())
+            paths += [os.path.join(p, '%d.pth' % e) for e in epochs if os.path.isfile(os.path.join(p, '%d.pth' % e))]
+        elif os.path.isfile(p):
+            paths.append(p)
+        else:
+            raise FileNotFoundError('--eval-league takes checkpoints and directories of <epoch>.pth files: no file %r'
+                                    % (p,))
+    return paths
+
+
+def eval_league_main(args, argv, device=None, log=print):
+    """``main.py --eval-league MODEL_OR_DIR [MODEL_OR_DIR ...] [NUM_GAMES=100] [SLOTS]``: a round robin of the
+    checkpoints in ``env.net()`` (the reference's author answers "which checkpoint is strongest" by hand, looping
+    evaluate_best_player.py over saved models one CPU game at a time).  Trailing arguments that are decimal integers
+    and not existing paths are NUM_GAMES (per pairing) and SLOTS (in all; default ``eval_slots`` or 1024, rounded down
+    to a multiple of 2Q and at least 2Q; a pairing gets no more slots than NUM_GAMES rounded up to even).  train_args
+    gives ``observation``, ``eval_temperature``, ``eval_opening_plies`` and ``seed`` as for ``--eval-match``.  Logs one
+    line per agent (path, rating, win rate, games) and the cross table (row i, column j: i's win rate against j) and
+    returns the evaluator's result."""
+    from .environment import make_env, prepare_env
+    env_args = args['env_args']
+    prepare_env(env_args)
+    env = make_env(env_args)
+    cls = batched_env(type(env).__module__)
+    if cls.P != 2:
+        raise ValueError('--eval-league seats two models per game: %s has %d players' % (cls.__name__, cls.P))
+    targs = args.get('train_args') or {}
+    argv, tail = list(argv), []
+    while argv and len(tail) < 2 and argv[-1].isdigit() and not os.path.exists(argv[-1]):
+        tail.insert(0, int(argv.pop()))
+    paths = league_paths(argv)
+    K = len(paths)
+    if K < 2:
+        raise ValueError('--eval-league needs two checkpoints at least: MODEL_OR_DIR [MODEL_OR_DIR ...] [NUM_GAMES] '
+                         '[SLOTS]')
+    games = tail[0] if len(tail) >= 1 else 100
+    slots = tail[1] if len(tail) >= 2 else int(targs.get('eval_slots') or 1024)
+    Q = K * (K - 1) // 2
+    S = max(2, min(slots // (2 * Q) * 2, games + games % 2))
+    if device is None:
+        if not torch.cuda.is_available():
+            raise RuntimeError('handyrl_amd.main evaluates on the GPU (HIP kernels); no GPU is visible')
+        device = torch.device('cuda', 0)
+    nets = [load_net(env, path, device) for path in paths]
+    log('%d agents, %d pairings, %d slots, %d games per pairing' % (K, Q, Q * S, games))
+    ev = LeagueEvaluator(cls(Q * S, device), nets, observation=bool(targs.get('observation', False)),
+                         temperature=float(targs.get('eval_temperature', 0.0)), opening_plies=opening_plies(targs),
+                         seed=int(targs.get('seed', 0)))
+    res = ev.evaluate(games)
+    played = res['games'].sum(1).tolist()
+    for k, path in enumerate(paths):
+        log('agent %d %s rating %+.1f win rate %.3f games %d'
+            % (k, path, float(res['rating'][k]), float(res['win_rate'][k]), played[k]))
+    log('cross table: row i, column j = the win rate of agent i against agent j')
+    log('      ' + ' '.join('%5d' % j for j in range(K)))
+    for i in range(K):
+        cells = ['    -' if i == j or int(res['games'][i, j]) == 0
+                 else '%5.3f' % (float(res['score'][i, j]) / int(res['games'][i, j])) for j in range(K)]
+        log('%5d ' % i + ' '.join(cells))
+    return res
 
 
 def eval_main(args, argv, device=None, log=print):

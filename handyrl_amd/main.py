@@ -3,6 +3,7 @@
     python -m handyrl_amd.main --train [config.yaml]
     python -m handyrl_amd.main --eval MODEL_PATH [NUM_GAMES] [SLOTS]
     python -m handyrl_amd.main --eval-match MODEL_A MODEL_B [NUM_GAMES] [SLOTS]
+    python -m handyrl_amd.main --eval-league MODEL_OR_DIR [MODEL_OR_DIR ...] [NUM_GAMES] [SLOTS]
     python -m torch.distributed.run --nproc-per-node N -m handyrl_amd.main --train [config.yaml]
 
 Reads the reference's ``config.yaml`` (main.py:13-15; config.yaml:1-35;
@@ -61,6 +62,11 @@ written) with the actors and the learner on the GPU:
   ``vs <path>``.  ``--eval-match MODEL_A MODEL_B [NUM_GAMES] [SLOTS]`` plays two checkpoints against each other
   and prints the reference's per-agent tables (evaluation.py:233-248).  Training is bit-identical with and
   without the key.
+* leagues: ``--eval-league MODEL_OR_DIR [MODEL_OR_DIR ...] [NUM_GAMES] [SLOTS]`` plays a round robin of checkpoints
+  (a directory expands to its ``<epoch>.pth`` files in epoch order) in one run on the device
+  (``evaluation.LeagueEvaluator``): NUM_GAMES games per pairing, each game the one ``--eval-match`` would play, every
+  net forwarded only over the rows where it moves.  It prints one line per agent with its Bradley-Terry rating (Elo,
+  mean 0), win rate and game count, and the cross table of win rates.
 
 The worker/server network plane, the network match server and client (their match itself is ``--eval-match``) and
 the other CLI modes are not rebuilt.
@@ -309,9 +315,16 @@ def main(argv=None):
         print(args)
         eval_match_main(args, argv[1:])
         return 0
+    if argv and argv[0] == '--eval-league':
+        from .evaluation import eval_league_main
+        args = load_config('config.yaml')
+        print(args)
+        eval_league_main(args, argv[1:])
+        return 0
     if not argv or argv[0] not in ('--train', '-t'):
         print('usage: python -m handyrl_amd.main --train [config.yaml] | --eval MODEL_PATH [NUM_GAMES] [SLOTS] | '
-              '--eval-match MODEL_A MODEL_B [NUM_GAMES] [SLOTS]')
+              '--eval-match MODEL_A MODEL_B [NUM_GAMES] [SLOTS] | '
+              '--eval-league MODEL_OR_DIR [MODEL_OR_DIR ...] [NUM_GAMES] [SLOTS]')
         return 1
     args = load_config(argv[1] if len(argv) > 1 else 'config.yaml')
     print(args)

@@ -229,6 +229,54 @@ int hrl_eval_finish(const uint8_t *terminal, const float *outcome, int64_t E, in
 int hrl_masked_rows_fill(int nleaves, float *const *dst, const int64_t *dst_stride, const int64_t *F,
                          const uint8_t *mask, int64_t E, void *stream);
 
+/* ---- The league evaluator (evaluation.LeagueEvaluator): a round robin of K >= 2 nets on the device.
+ *
+ * Public rules (torch twins in handyrl_amd/evaluation.py):
+ *   Agents: K nets, agents 0 .. K-1, each a module object of its own, on an alternating env with P == 2.
+ *   Pairings: by default every (i, j) with i < j in lexicographic order, Q = K (K - 1) / 2 of them; or an explicit
+ *     list of pairs with i != j in which each unordered pair appears at most once.  The first agent of a pair is its
+ *     HOME agent.  A ladder of the newest agent against all others is [(K-1, 0), ..., (K-1, K-2)].
+ *   Games: every pairing plays G games, numbers 0 .. G-1; in game g the home agent sits on seat g mod 2.
+ *   Contract: every ply is decided by the match rules above, unchanged -- the mover's own net at the one shared
+ *     temperature, eval_pick on the first `opening` plies, Philox keyed by (seed, g, ply) -- so game g of pairing
+ *     (i, j) IS game g of the match of net i (home) against net j with the same arguments.
+ *   Slots: E = Q * S; pairing q owns slots q * S .. q * S + S - 1; S is even and >= 2.  Slot t of a block plays games
+ *     t, t + S, t + 2 S, ... while the number is below G, then retires.  A slot restarts only at a step with
+ *     s mod 2 == 0.  Because S is even a slot's seating never changes (seat = t mod 2 for the whole run), so the set of
+ *     rows on which a given net moves at a given mover parity is fixed: shapes are static and one captured graph per
+ *     mover serves the run.  This is NOT hrl_eval_finish's next_game + r rule; every game number is still played
+ *     exactly once, whichever game finishes first, so short games are not favoured.
+ *   Forwards: without `observation` each net runs once per ply over the rows where it is the mover (the view is the
+ *     mover's seat): E rows over all nets.  With it each net runs over every slot it sits in, from its own seat: 2 E.
+ *   Recurrent state: one row per net per slot it sits in, zero when a game starts, advanced where the net moved (with
+ *     `observation`: on every row); a net's rows of one seat are contiguous.
+ * Both entries are asynchronous on `stream`, allocate nothing, read nothing on the host (graph-capturable) and
+ * validate before any HIP call. */
+
+/* hrl_eval_finish with the block rule; after the env's step, one launch of one workgroup.  For every active slot:
+ * ply += 1 and done = terminal[e] != 0 || ply >= Tm.  A done slot e of block q = e / S with game number g:
+ *   0 <= g < G: outcome_out[q][g] = outcome[e] and length_out[q][g] = ply  (outcome_out (Q, G, P) fp32, length_out
+ *   (Q, G) int64, Q = E / S; outcome (E, P) fp32);
+ *   n = g + S;  n < G: game = n, ply = 0, pending = 1;  else (retired) game = G, ply = 0, pending = 0;
+ *   active = 0 either way.  The seat is not touched.
+ * state[0] (one int64 in device memory, `finished`) grows by the number of done slots; the host stops at Q * G.
+ * Plain stores only: no atomics, tickets or spin-waits.  Slots that are not active are not touched.
+ * HRL_EINVAL for a NULL pointer, E < 0, S < 2 or odd, E not a multiple of S, Tm < 1, P < 1, G < 0; E == 0: HRL_OK, no
+ * launch. */
+int hrl_league_finish(const uint8_t *terminal, const float *outcome, int64_t E, int64_t S, int64_t Tm, int64_t P,
+                      int64_t G, uint8_t *active, int64_t *ply, int64_t *game, uint8_t *pending, int64_t *state,
+                      float *outcome_out, int64_t *length_out, void *stream);
+
+/* The ply's route: for each of nleaves (<= 16) fp32 tensors in ONE launch, row dst_index[r] of dst[l] becomes row
+ * src_index[r] of src[l] for r < n (rows of F[l] contiguous floats, row strides dst_stride[l] / src_stride[l] elements
+ * as in hrl_masked_rows_copy).  src_index / dst_index (n,) int64 device arrays; NULL is the identity.  Every index
+ * must be a row of its tensor, and the dst rows distinct; other rows of dst are untouched.  The observation leaves go
+ * into net-major order in one launch and the nets' logits return to slot order in one launch, whatever K is.
+ * HRL_EINVAL for nleaves outside [1, 16], a NULL array or leaf, F < 1, a stride < F, n < 0; n == 0: HRL_OK, no launch. */
+int hrl_rows_permute(int nleaves, float *const *dst, const int64_t *dst_stride, const float *const *src,
+                     const int64_t *src_stride, const int64_t *F, const int64_t *src_index, const int64_t *dst_index,
+                     int64_t n, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
