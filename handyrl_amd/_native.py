@@ -290,6 +290,12 @@ SIGNATURES = {
     'hrl_rows_permute': (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _i64,
                                         ctypes.c_void_p]),
+    'hrl_board_infer_pack_bytes': (ctypes.c_int64, [_i64]),
+    'hrl_board_infer_pack': (ctypes.c_int, [_f32p, _f32p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _i64, _f32p, _f32p,
+                                            _f32p, _f32p, _f32p, _f32p, ctypes.c_void_p, ctypes.c_void_p]),
+    'hrl_board_infer': (ctypes.c_int, [ctypes.c_void_p, _i64, _i64, ctypes.c_void_p, _f32p, _i64, _i64, _f32p,
+                                       _f32p, ctypes.c_void_p]),
     'hrl_replay_gather': (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_void_p, _i64, _i64, ctypes.c_void_p, ctypes.c_void_p]),
     'hrl_replay_draw': (ctypes.c_int, [_f32p, _i64, _i64, _i64, _i64, _i64, ctypes.c_void_p, _i64, _i64,

@@ -858,6 +858,15 @@ class LeagueEvaluator:
                 h = map_r(net.init_hidden([n]), lambda x: x.to(dev).contiguous())
             st['hidden'].append(h)
             st['inplace'].append(inplace)
+        # nets that are the members of one nn.board_inference_group, in its order, without observation: one grouped
+        # forward per ply over the spans of the movers' rows (anything else: the loop over the nets)
+        group = getattr(self.nets[0], '_group', None)
+        st['group'] = None
+        if (group is not None and cuda and not self.observation and len(group) == self.K
+                and all(n is m for n, m in zip(self.nets, group)) and env.A == 9
+                and not isinstance(st['obs'], (dict, list, tuple))):
+            st['group'] = group
+            st['group_span'] = [[0] + [hi for _, hi in lay['span'][m]] for m in (0, 1)]
         # the slot of every state row, all nets one after another: a restarting slot's rows by one index op
         st['row_slot'] = index([e for k in range(self.K) for s in (0, 1) for e in lay['rows'][k][s]], E)
         self._st = st
@@ -902,9 +911,15 @@ class LeagueEvaluator:
                 permute(dst, _leaves(env.observation(st['views'][s])), st['seat_src'][s], st['seat_dst'][s])
         else:
             permute(dst, _leaves(env.observation(st['views'][mover])), st['order'][mover], None)
+        group = st['group']
+        if group is not None:
+            # every net a member of one board_inference_group: the K forwards as one launch over the net-major rows,
+            # its logits straight into the route out
+            out = group.forward(st['obs'], st['group_span'][mover])
+            permute([st['logits']], [out['policy']], st['back'][mover], None)
         # every net once, over its own rows; its state rows are a view, which it advances
         policies = []
-        for k, net in enumerate(self.nets):
+        for k, net in enumerate(self.nets if group is None else ()):
             lo, hi = lay['span'][mover][k]
             h = st['hidden'][k]
             if h is not None and not self.observation:
@@ -921,7 +936,8 @@ class LeagueEvaluator:
                 p = p[mover * half:(mover + 1) * half]
             policies.append(p)
         # the route out: the movers' logits, agent by agent, back into slot order
-        permute([st['logits']], [torch.cat(policies)], st['back'][mover], None)
+        if group is None:
+            permute([st['logits']], [torch.cat(policies)], st['back'][mover], None)
         act = match_act_hip if fused else match_act_torch
         a = act(st, st['logits'], st['logits'], env.legal(), mover, self.seed, self.temperature, self.temperature,
                 self.opening_plies, run['G'])
@@ -1079,7 +1095,9 @@ def eval_league_main(args, argv, device=None, log=print):
         if not torch.cuda.is_available():
             raise RuntimeError('handyrl_amd.main evaluates on the GPU (HIP kernels); no GPU is visible')
         device = torch.device('cuda', 0)
-    nets = [load_net(env, path, device) for path in paths]
+    from .nn import configured_inference
+    # train_args['inference']: fused -- the nets as one board_inference_group (one launch per ply for all of them)
+    nets = configured_inference(targs.get('inference'), [load_net(env, path, device) for path in paths], device)
     log('%d agents, %d pairings, %d slots, %d games per pairing' % (K, Q, Q * S, games))
     ev = LeagueEvaluator(cls(Q * S, device), nets, observation=bool(targs.get('observation', False)),
                          temperature=float(targs.get('eval_temperature', 0.0)), opening_plies=opening_plies(targs),
@@ -1115,7 +1133,8 @@ def eval_main(args, argv, device=None, log=print):
         if not torch.cuda.is_available():
             raise RuntimeError('handyrl_amd.main evaluates on the GPU (HIP kernels); no GPU is visible')
         device = torch.device('cuda', 0)
-    net = load_net(env, model_path, device)
+    from .nn import configured_inference
+    net = configured_inference(targs.get('inference'), [load_net(env, model_path, device)], device)[0]
     E = max(1, min(slots, games))
     log('%d slots, %d games' % (E, games))
     ev = DeviceEvaluator(cls(E, device), net, observation=bool(targs.get('observation', False)),
@@ -1166,7 +1185,10 @@ def eval_match_main(args, argv, device=None, log=print):
         if not torch.cuda.is_available():
             raise RuntimeError('handyrl_amd.main evaluates on the GPU (HIP kernels); no GPU is visible')
         device = torch.device('cuda', 0)
-    nets = [load_net(env, path, device) for path in argv[:2]]
+    from .nn import configured_inference
+    # train_args['inference']: fused -- each agent its one-launch forward (the members of a group, used one by one)
+    nets = list(configured_inference(targs.get('inference'), [load_net(env, path, device) for path in argv[:2]],
+                                     device))
     E = max(1, min(slots, games))
     log('%d slots, %d games' % (E, games))
     ev = DeviceEvaluator(cls(E, device), nets[0], observation=bool(targs.get('observation', False)),

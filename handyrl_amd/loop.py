@@ -13,10 +13,12 @@ and ``LearnerStep`` trains on windows gathered from it.
 evaluation against a random agent (evaluation.py:64-87, agent.py:55-110).
 """
 
+import contextlib
 import time
 
 import torch
 
+from .nn import BoardInference
 from .rollout import DeviceGenerator, DeviceReplay, StreamGenerator, TicTacToeBatch
 from .trainer import LearnerStep
 from .util import map_r
@@ -28,20 +30,24 @@ class SelfPlayTrainer:
     """``env_cls``: a batched env (TicTacToeBatch, envs.geister.GeisterBatch); recurrent nets
     train from a zero hidden state at every window start (train.py:375).  ``stream``: play with
     ``rollout.StreamGenerator`` (``games_per_round`` slots that restart in place; a round plays until that many
-    more games are in the ring) instead of the lockstep ``DeviceGenerator``."""
+    more games are in the ring) instead of the lockstep ``DeviceGenerator``.  ``fused_inference``: self-play runs
+    ``nn.BoardInference(net)`` (``play_net``, also the net to hand to ``evaluate_vs_random``); the learner trains
+    ``net`` itself."""
 
     def __init__(self, net, args, device, games_per_round=4096, capacity=65536, graph=False, seed=0,
-                 env_cls=TicTacToeBatch, obs_dtype=torch.uint8, stream=False):
+                 env_cls=TicTacToeBatch, obs_dtype=torch.uint8, stream=False, fused_inference=False):
         self.args = args
         self.device = device
         self.env = env_cls(games_per_round, device)
         self.replay = DeviceReplay(capacity, env_cls.MAX_PLIES, env_cls.OBS_SHAPE, env_cls.A, env_cls.P, device,
                                    maximum_episodes=args.get('maximum_episodes', capacity), obs_dtype=obs_dtype)
         self.stream = bool(stream)
+        # the net as self-play runs it: itself, or its one-launch eval forward (the learner trains `net` itself)
+        self.play_net = BoardInference(net) if fused_inference else net
         if self.stream:
-            self.gen = StreamGenerator(self.env, net, self.replay, gamma=args['gamma'], seed=seed)
+            self.gen = StreamGenerator(self.env, self.play_net, self.replay, gamma=args['gamma'], seed=seed)
         else:
-            self.gen = DeviceGenerator(self.env, net, gamma=args['gamma'])
+            self.gen = DeviceGenerator(self.env, self.play_net, gamma=args['gamma'])
         self.learner = LearnerStep(net, args, device, graph=graph)
         self.hidden = None
         if hasattr(net, 'init_hidden'):
@@ -99,17 +105,20 @@ def evaluate_vs_random(net, device, games=4096, seed=0):
     model_side = (torch.arange(games, device=device) >= games // 2).long()   # 0 = black
     was = net.training
     net.eval()
-    for _ in range(TicTacToeBatch.MAX_PLIES):
-        active = ~env.terminal()
-        player = env.turn()
-        legal = env.legal()
-        logits = net(env.observation(player), None)['policy']
-        mine = player == model_side
-        rand_logits = torch.zeros_like(logits)
-        p = torch.where(mine.view(-1, 1), logits, rand_logits) - torch.where(legal, 0.0, 1e32)
-        u = torch.rand(p.shape, device=device, generator=g).clamp_(1e-20, 1.0)
-        a = torch.argmax(p - torch.log(-torch.log(u)), dim=-1)
-        env.step(a, active)
+    # a wrapper that prepares its weights per call (nn.BoardInference) is entered; a plain net has no session
+    session = getattr(net, 'inference_session', None) if getattr(net, 'stateless_session', False) else None
+    with session() if session is not None else contextlib.nullcontext():
+        for _ in range(TicTacToeBatch.MAX_PLIES):
+            active = ~env.terminal()
+            player = env.turn()
+            legal = env.legal()
+            logits = net(env.observation(player), None)['policy']
+            mine = player == model_side
+            rand_logits = torch.zeros_like(logits)
+            p = torch.where(mine.view(-1, 1), logits, rand_logits) - torch.where(legal, 0.0, 1e32)
+            u = torch.rand(p.shape, device=device, generator=g).clamp_(1e-20, 1.0)
+            a = torch.argmax(p - torch.log(-torch.log(u)), dim=-1)
+            env.step(a, active)
     net.train(was)
     oc = env.outcome()[torch.arange(games, device=device), model_side]
     return {'win': float((oc > 0).float().mean()), 'draw': float((oc == 0).float().mean()),

@@ -186,6 +186,11 @@ def train_main(args, device=None, loss_fn=None, model_dir='models', log=print):
         net.load_state_dict(torch.load(os.path.join(model_dir, '%d.pth' % restart), map_location='cpu',
                                        weights_only=True))
     net = net.to(device)
+    # train_args['inference']: fused -- self-play and the per-epoch evaluation run the net's one-launch eval forward
+    # (nn.BoardInference, which refers to `net`); the learner trains `net` itself.  Absent: `net` plays as it is
+    from .nn import configured_inference
+    infer_mode = targs.get('inference')
+    play_net = configured_inference(infer_mode, [net], device)[0]
     # the episode counts are global (train.py:480-503, 549-552): each rank plays and keeps 1/world of them
     games = _per_rank(targs['update_episodes'], world)
     minimum = _per_rank(targs['minimum_episodes'], world)
@@ -213,8 +218,10 @@ def train_main(args, device=None, loss_fn=None, model_dir='models', log=print):
             eval_slots = max(1, min(int(targs.get('eval_slots') or eval_n), eval_n))
             match = {}
             if eval_vs not in (None, 'random'):
-                match = {'opponent': _eval_opponent(env, net, eval_vs, device), 'opening_plies': opening_plies(targs)}
-            evaluator = DeviceEvaluator(eval_cls(eval_slots, device), net, observation=observe,
+                opponent = _eval_opponent(env, net, eval_vs, device)
+                match = {'opponent': configured_inference(infer_mode, [opponent], device)[0],
+                         'opening_plies': opening_plies(targs)}
+            evaluator = DeviceEvaluator(eval_cls(eval_slots, device), play_net, observation=observe,
                                         temperature=float(targs.get('eval_temperature', 0.0)), seed=seed, **match)
     played = None   # a generator that reports what it emitted (stream): episodes of the last play()
     if use_device and self_play == 'stream':
@@ -222,7 +229,7 @@ def train_main(args, device=None, loss_fn=None, model_dir='models', log=print):
         replay = DeviceReplay(maximum, batched.MAX_PLIES, batched.OBS_SHAPE, batched.A, batched.P, device,
                               maximum_episodes=maximum, obs_dtype=torch.uint8,
                               draw=targs.get('window_draw', 'multinomial'))
-        gen = StreamGenerator(batched(slots, device), net, replay, gamma=targs['gamma'], seed=seed)
+        gen = StreamGenerator(batched(slots, device), play_net, replay, gamma=targs['gamma'], seed=seed)
         played = [0]
 
         def play():
@@ -230,7 +237,7 @@ def train_main(args, device=None, loss_fn=None, model_dir='models', log=print):
             played[0] = out['episodes']
             return float(out['env_steps'])
     elif use_device:
-        gen = DeviceGenerator(batched(games, device), net, gamma=targs['gamma'], observation=observe,
+        gen = DeviceGenerator(batched(games, device), play_net, gamma=targs['gamma'], observation=observe,
                               per_player=per_player)
         # binary observation planes live in HBM as uint8 (widened by the gather)
         if per_player:
@@ -248,7 +255,7 @@ def train_main(args, device=None, loss_fn=None, model_dir='models', log=print):
             return float(ep['length'].float().sum())
     else:
         slots = min(games, int(targs.get('host_envs', 256)))
-        gen = HostBatchGenerator(lambda: make_env(env_args), net, targs, E=slots, seed=seed)
+        gen = HostBatchGenerator(lambda: make_env(env_args), play_net, targs, E=slots, seed=seed)
         replay = MomentReplay({**targs, 'maximum_episodes': maximum}, device, maximum_episodes=maximum)
 
         def play():

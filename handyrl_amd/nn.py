@@ -25,6 +25,7 @@ The HIP path is taken whenever the input is a CUDA tensor in training mode;
 if libhrl.so is missing that raises (no silent fallback).
 """
 
+import contextlib
 import ctypes
 import operator
 
@@ -37,7 +38,8 @@ import torch.nn.functional as F
 
 from . import _native
 
-__all__ = ['BatchNorm2d', 'BoardConv2d', 'Linear', 'accelerate', 'batch_norm_train', 'fuse_bn_relu', 'unfuse']
+__all__ = ['BatchNorm2d', 'BoardConv2d', 'Linear', 'accelerate', 'batch_norm_train', 'fuse_bn_relu', 'unfuse',
+           'BoardInference', 'board_inference_group', 'board_inference_ok']
 
 _MAX_ROW = 3072        # float4 path (row width a multiple of 4)
 _MAX_ROW_SCALAR = 1024  # scalar path
@@ -2600,3 +2602,220 @@ def unfuse(model):
         if isinstance(m, BatchNorm2d):
             m.fused_relu = False
     return model
+
+
+# ---------------------------------------------------------------- one-launch inference for the TicTacToe net
+def _board_infer_parts(net):
+    """The modules of a SimpleConv2dModel-shaped net (envs/tictactoe.py) that csrc/hrl_infer.hip forwards, or
+    None: stem Conv2d(3,32,3,padding=1) with bias, 1..8 blocks of bias-free Conv2d(32,32,3,padding=1) + affine,
+    stat-tracking BatchNorm2d(32), two heads (1x1 conv with bias to 2 / 1 channels, LeakyReLU(0.1), bias-free
+    linear to 9 / 1).  The same before and after ``accelerate`` / ``fuse_bn_relu`` (subclasses, same parameters)."""
+    def conv_ok(c, cin, cout, k, bias):
+        return (isinstance(c, nn.Conv2d) and c.in_channels == cin and c.out_channels == cout
+                and tuple(c.kernel_size) == (k, k) and tuple(c.stride) == (1, 1) and tuple(c.dilation) == (1, 1)
+                and c.groups == 1 and c.padding_mode == 'zeros' and isinstance(c.padding, tuple)
+                and tuple(c.padding) == (k // 2, k // 2) and (c.bias is not None) == bias)
+
+    stem, blocks = getattr(net, 'conv', None), getattr(net, 'blocks', None)
+    heads = (getattr(net, 'head_p', None), getattr(net, 'head_v', None))
+    if hasattr(net, 'init_hidden') or not conv_ok(stem, 3, 32, 3, True):
+        return None
+    if not isinstance(blocks, nn.ModuleList) or not 1 <= len(blocks) <= 8:
+        return None
+    for blk in blocks:
+        bn = getattr(blk, 'bn', None)
+        if not (conv_ok(getattr(blk, 'conv', None), 32, 32, 3, False) and isinstance(bn, nn.BatchNorm2d)
+                and bn.num_features == 32 and bn.affine and bn.track_running_stats
+                and bn.running_mean is not None and bn.running_var is not None):
+            return None
+    for head, cmid, nout in zip(heads, (2, 1), (9, 1)):
+        unit, fc = getattr(head, 'conv', None), getattr(head, 'fc', None)
+        if not (conv_ok(getattr(unit, 'conv', None), 32, cmid, 1, True) and getattr(unit, 'bn', None) is None
+                and isinstance(fc, nn.Linear) and fc.in_features == 9 * cmid and fc.out_features == nout
+                and fc.bias is None and getattr(head, 'LEAKY_SLOPE', None) == 0.1):
+            return None
+    return stem, list(blocks), heads
+
+
+def board_inference_ok(net):
+    """True for a net ``BoardInference`` can forward (a SimpleConv2dModel-shaped module with 32 filters)."""
+    return _board_infer_parts(net) is not None
+
+
+class BoardInference:
+    """The TicTacToe net as the generators and evaluators use one, its eval forward ONE launch (hrl_board_infer).
+
+    ``net`` is referred to, not registered: ``training``, ``eval``, ``train``, ``parameters``, ``buffers``,
+    ``state_dict``, ``load_state_dict`` and ``to`` are its own.  ``inference_session`` packs the net's current
+    tensors (one hrl_board_infer_pack launch) into a buffer that keeps its address, so a captured ply stays valid
+    and a later session refreshes the weights in place.  Inside a session a CUDA fp32 observation batch is one
+    launch; a CPU batch runs ``net``'s own forward.  Training mode, or the GPU outside a session, raises: there is
+    no other GPU path.
+    """
+
+    stateless_session = True   # nothing to advance in place: generators may enter the session in any mode
+
+    def __init__(self, net):
+        if not board_inference_ok(net):
+            raise ValueError('BoardInference: not a SimpleConv2dModel-shaped net (board_inference_ok)')
+        self.net = net
+        self.layers = len(net.blocks)
+        self._buf = None          # own pack; a group member's is a row of the group's buffer
+        self._group, self._index = None, 0
+        self._live = 0
+
+    training = property(lambda self: self.net.training)
+
+    def eval(self):
+        self.net.eval()
+        return self
+
+    def train(self, mode=True):
+        self.net.train(mode)
+        return self
+
+    def parameters(self, *args, **kwargs):
+        return self.net.parameters(*args, **kwargs)
+
+    def buffers(self, *args, **kwargs):
+        return self.net.buffers(*args, **kwargs)
+
+    def state_dict(self, *args, **kwargs):
+        return self.net.state_dict(*args, **kwargs)
+
+    def load_state_dict(self, *args, **kwargs):
+        return self.net.load_state_dict(*args, **kwargs)
+
+    def to(self, *args, **kwargs):
+        self.net = self.net.to(*args, **kwargs)
+        return self
+
+    def pack(self, device=None):
+        """The pack buffer (pack_bytes uint8) on ``device``: allocated once, the same storage ever after."""
+        if self._group is not None:
+            return self._group.buffer(device)[self._index]
+        if self._buf is None or (device is not None and self._buf.device != torch.device(device)):
+            nbytes = _native.load().hrl_board_infer_pack_bytes(self.layers)
+            self._buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        return self._buf
+
+    def _refresh(self, dev, out=None):
+        """hrl_board_infer_pack from the net's tensors into the pack (``out``: another buffer of pack_bytes)."""
+        stem, blocks, (hp, hv) = _board_infer_parts(self.net)
+        tensors = [stem.weight, stem.bias, hp.conv.conv.weight, hp.conv.conv.bias, hv.conv.conv.weight,
+                   hv.conv.conv.bias, hp.fc.weight, hv.fc.weight]
+        per = [[b.conv.weight for b in blocks], [b.bn.weight for b in blocks], [b.bn.bias for b in blocks],
+               [b.bn.running_mean for b in blocks], [b.bn.running_var for b in blocks]]
+        for t in tensors + [t for ts in per for t in ts]:
+            if not (t.device == dev and t.dtype == torch.float32 and t.is_contiguous()):
+                raise ValueError('BoardInference: the net\'s tensors must be contiguous fp32 on one device')
+        eps = (ctypes.c_double * len(blocks))(*[float(b.bn.eps) for b in blocks])
+        sw, sb, w1p, b1p, w1v, b1v, fcp, fcv = tensors
+        _native.check(_native.load().hrl_board_infer_pack(
+            _native.ptr(sw), _native.ptr(sb), *[_native.ptr_array(ts) for ts in per], eps, len(blocks),
+            _native.ptr(w1p), _native.ptr(b1p), _native.ptr(w1v), _native.ptr(b1v), _native.ptr(fcp),
+            _native.ptr(fcv), _native.ptr(self.pack(dev) if out is None else out), _native.stream_of(dev)),
+            'hrl_board_infer_pack')
+
+    @contextlib.contextmanager
+    def inference_session(self, inplace_state=False):
+        """Pack the net's current weights (one launch, in place); ``inplace_state`` is accepted and ignored (the
+        net has no state).  On a CPU net there is nothing to prepare."""
+        dev = next(self.net.parameters()).device
+        if dev.type == 'cuda':
+            with torch.no_grad():
+                self._refresh(dev)
+        self._live += 1
+        try:
+            yield self
+        finally:
+            self._live -= 1
+
+    def __call__(self, obs, hidden=None):
+        if self.net.training:
+            raise RuntimeError('BoardInference is the eval forward: the net is in training mode')
+        if not obs.is_cuda:
+            return self.net(obs, hidden)
+        if not self._live:
+            raise RuntimeError('BoardInference on the GPU runs inside inference_session()')
+        pack = self.pack(obs.device)
+        return _board_infer_launch(pack, pack.numel(), 1, [0, obs.shape[0]], obs, self.layers)
+
+
+def _board_infer_launch(pack, stride, K, span, obs, layers):
+    N = obs.shape[0]
+    if obs.dtype != torch.float32 or obs.numel() != N * 27:
+        raise ValueError('BoardInference: observations are (N, 3, 3, 3) fp32, not %s %s' % (tuple(obs.shape),
+                                                                                          obs.dtype))
+    o = obs.reshape(N, 27)
+    if not o.is_contiguous():
+        o = o.contiguous()
+    policy = torch.empty(N, 9, device=obs.device)
+    value = torch.empty(N, 1, device=obs.device)
+    if N == 0:
+        return {'policy': policy, 'value': value}
+    _native.check(_native.load().hrl_board_infer(
+        _native.ptr(pack), stride, K, _native.i64_array([int(s) for s in span]), _native.ptr(o), N, layers,
+        _native.ptr(policy), _native.ptr(value), _native.stream_of(obs.device)), 'hrl_board_infer')
+    return {'policy': policy, 'value': value}
+
+
+class BoardInferenceGroup(list):
+    """K ``BoardInference`` wrappers whose packs are the rows of one (K, pack_bytes) buffer (board_inference_group);
+    ``forward`` runs all K nets in one launch."""
+
+    def __init__(self, nets):
+        super().__init__(BoardInference(n) for n in nets)
+        if not self:
+            raise ValueError('board_inference_group: no nets')
+        self.layers = self[0].layers
+        if any(m.layers != self.layers for m in self):
+            raise ValueError('board_inference_group: the nets must have the same number of blocks')
+        for k, m in enumerate(self):
+            m._group, m._index = self, k
+        self._buf = None
+
+    def buffer(self, device=None):
+        if self._buf is None or (device is not None and self._buf.device != torch.device(device)):
+            nbytes = _native.load().hrl_board_infer_pack_bytes(self.layers)
+            self._buf = torch.empty(len(self), nbytes, dtype=torch.uint8, device=device)
+        return self._buf
+
+    def forward(self, obs, span):
+        """Rows [span[k], span[k+1]) of ``obs`` through net k (span: K+1 ascending row offsets, a Python list):
+        {'policy' (N, 9), 'value' (N, 1)} in row order, one launch.  Every member must be inside its session."""
+        if len(span) != len(self) + 1:
+            raise ValueError('board_inference_group.forward: span has K + 1 = %d offsets' % (len(self) + 1))
+        if any(m.net.training for m in self):
+            raise RuntimeError('BoardInference is the eval forward: a net is in training mode')
+        if not obs.is_cuda:
+            outs = [m.net(obs[span[k]:span[k + 1]], None) for k, m in enumerate(self)]
+            return {key: torch.cat([o[key] for o in outs]) for key in ('policy', 'value')}
+        if not all(m._live for m in self):
+            raise RuntimeError('board_inference_group.forward runs inside every member\'s inference_session()')
+        buf = self.buffer(obs.device)
+        return _board_infer_launch(buf, buf.shape[1], len(self), span, obs, self.layers)
+
+
+def board_inference_group(nets):
+    """``BoardInference`` wrappers of same-depth nets sharing one pack buffer: a list of the K wrappers (each
+    usable on its own) with ``forward(obs, span)``, all K nets in one launch."""
+    return BoardInferenceGroup(nets)
+
+
+def configured_inference(mode, nets, device):
+    """``train_args['inference']`` applied to the nets that play: absent / None leaves them as they are; ``fused``
+    wraps each in ``BoardInference`` (several: one ``board_inference_group``).  Anything the fused forward cannot
+    run raises here, at start-up, by the key's name."""
+    if mode is None:
+        return nets
+    if mode != 'fused':
+        raise ValueError("train_args['inference'] must be fused (or absent), not %r" % (mode,))
+    if torch.device(device).type != 'cuda':
+        raise ValueError("train_args['inference']: 'fused' is the one-launch forward on the GPU; the device is %s"
+                         % (device,))
+    for net in nets:
+        if not board_inference_ok(net):
+            raise ValueError("train_args['inference']: 'fused' forwards the TicTacToe net (SimpleConv2dModel with 32 "
+                             "filters and 1..8 blocks); %s is not one (board_inference_ok)" % type(net).__name__)
+    return board_inference_group(nets) if len(nets) > 1 else [BoardInference(nets[0])]

@@ -564,9 +564,11 @@ class DeviceGenerator:
         was_training = self.net.training
         self.net.eval()
         # per-call weight preparation (GeisterNet); its own stacked state is advanced in place by the net (the
-        # per-player ply too when every player infers; otherwise it runs the net's ordinary forward)
+        # per-player ply too when every player infers; otherwise it runs the net's ordinary forward).  A wrapper
+        # without state (nn.BoardInference) is entered in every mode
         session = (getattr(self.net, 'inference_session', None)
-                   if (not self.per_player or st.get('flat_state')) else None)
+                   if (not self.per_player or st.get('flat_state') or getattr(self.net, 'stateless_session', False))
+                   else None)
         with session(inplace_state=st['pmajor']) if session is not None else contextlib.nullcontext():
             out = self._generate(st, generator, alternating, reference)
         self.net.train(was_training)

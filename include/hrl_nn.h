@@ -609,6 +609,34 @@ int64_t hrl_clip_workspace_bytes(int64_t n);
 int hrl_clip_grad_norm_ws(float *grads, int64_t n, double max_norm, float *total_norm, void *workspace,
                           int64_t workspace_bytes, void *stream);
 
+/* One-launch inference for the TicTacToe net (envs/tictactoe.py SimpleConv2dModel: stem conv 3->32 + ReLU, `layers`
+ * x [conv 32->32 3x3 -> BatchNorm (running statistics) -> ReLU], policy / value heads), grouped over checkpoints
+ * (csrc/hrl_infer.hip).  Filters 32, board 3x3, A = 9; layers in 1..8.  Every entry is asynchronous, allocates
+ * nothing, never synchronises and is capturable; arguments are validated (HRL_EINVAL) before any HIP call.
+ * hrl_board_infer_pack_bytes: the bytes of one packed net (a multiple of 16; 0 for layers outside 1..8).
+ * hrl_board_infer_pack: ONE launch that reads the net's tensors where they lie -- stem weight (32,3,3,3) and bias;
+ *   per block l (host arrays of `layers` device pointers) conv weight (32,32,3,3), BatchNorm weight, bias,
+ *   running_mean, running_var, and bn_eps[l] (host doubles); head 1x1 conv weights w1p (2,32) / w1v (1,32) and
+ *   biases b1p (2) / b1v (1); the bias-free fc weights fcp (9,18) and fcv (1,9) -- and writes the pack
+ *   (16-byte aligned): the conv weights as the exact three-way bf16 split fragments the forward's MFMAs read, the
+ *   BatchNorm coefficients invstd = (float)(1/sqrt((double)var + eps)), a = invstd*w, b = bias - mean*a as
+ *   hrl_bn_forward_eval forms them.
+ * hrl_board_infer: ONE launch.  Rows [span[k], span[k+1]) of obs (N x 27 fp32, contiguous) are forwarded with the
+ *   pack at pack + k*pack_stride_bytes (k < K <= 64; span: K+1 ascending host offsets, span[0] = 0, span[K] = N;
+ *   read during the call only: a captured graph replays with the spans of its capture; empty spans are legal);
+ *   policy (N x 9 fp32) gets the raw logits, value (N x 1 fp32) the tanh.  K = 1 with span {0, N} is the
+ *   single-net forward; N = 0 returns HRL_OK with no launch.  Arithmetic: six partial products of the exact bf16
+ *   split on v_mfma_f32_16x16x32_bf16 with fp32 accumulation (fp32-accurate; exact on data whose products and sums
+ *   are exact in fp32); a row's result does not depend on N, K or the row's place in its span.  Deterministic. */
+int64_t hrl_board_infer_pack_bytes(int64_t layers);
+int hrl_board_infer_pack(const float *stem_w, const float *stem_b, const float *const *conv_w,
+                         const float *const *bn_w, const float *const *bn_b, const float *const *bn_mean,
+                         const float *const *bn_var, const double *bn_eps, int64_t layers, const float *w1p,
+                         const float *b1p, const float *w1v, const float *b1v, const float *fcp, const float *fcv,
+                         void *pack, void *stream);
+int hrl_board_infer(const void *pack, int64_t pack_stride_bytes, int64_t K, const int64_t *span, const float *obs,
+                    int64_t N, int64_t layers, float *policy, float *value, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
