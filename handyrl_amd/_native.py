@@ -296,6 +296,9 @@ SIGNATURES = {
                                             _f32p, _f32p, _f32p, _f32p, ctypes.c_void_p, ctypes.c_void_p]),
     'hrl_board_infer': (ctypes.c_int, [ctypes.c_void_p, _i64, _i64, ctypes.c_void_p, _f32p, _i64, _i64, _f32p,
                                        _f32p, ctypes.c_void_p]),
+    'hrl_board_selfplay': (ctypes.c_int, [ctypes.c_void_p, _i64, _i64, _i64, _i64, _i64, _f32p, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _f32p, _f32p, _f32p,
+                                          ctypes.c_void_p, _f32p, ctypes.c_void_p, ctypes.c_void_p]),
     'hrl_replay_gather': (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_void_p, _i64, _i64, ctypes.c_void_p, ctypes.c_void_p]),
     'hrl_replay_draw': (ctypes.c_int, [_f32p, _i64, _i64, _i64, _i64, _i64, ctypes.c_void_p, _i64, _i64,

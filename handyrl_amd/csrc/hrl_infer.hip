@@ -19,45 +19,19 @@
 //   * arithmetic: six partial products on v_mfma_f32_16x16x32_bf16, smallest terms first, fp32 accumulation;
 //     BN + ReLU as y*a + b, v < 0 ? 0 : v; the heads on the VALU.
 //   LDS 78,464 B per workgroup: two workgroups per CU; N = 4096 is 256 tiles, one per CU.
+// The tile's forward itself (pack layout constants, stem, chain, heads) is hrl_board_fwd.h, shared with the
+// whole-game self-play kernel (hrl_boardplay.hip).
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/hrl_nn.h"
 #include "../../include/hrl_targets.h"
-#include "hrl_split.h"
+#include "hrl_board_fwd.h"
 
 namespace {
 
-using hrl_split::f32x4;
-using hrl_split::mfma_bf16;
-using hrl_split::mfma_split;
-using hrl_split::split8;
-using hrl_split::split_part;
-
-constexpr int kCells = 9;
-constexpr int kC = 32;
-constexpr int kRow = kC * kCells;          // 288 floats per sample
-constexpr int kStride = kRow + 2;          // LDS row stride, == 2 (mod 32)
-constexpr int kTile = 16;                  // rows per workgroup
-constexpr int kThreads = 256;
-constexpr int kObs = 27;                   // 3 planes x 9 cells
-constexpr int kA = 9;
-constexpr int kMaxLayers = 8;
 constexpr int kMaxNets = 64;               // nets per launch (the span table is a kernel argument)
-
-// the pack, in 32-bit words
-constexpr int kStemFragWords = 2 * 3 * 64 * 4;                 // 1536
-constexpr int kStemBiasWords = kC;                             // 32
-constexpr int kHeadFloats = 270;   // w1p[2][32] | b1p[2] | w1v[32] | b1v | fcp[9][18] | fcv[9]
-constexpr int kHeadWords = 272;
-constexpr int kHW1p = 0, kHB1p = 64, kHW1v = 66, kHB1v = 98, kHFcp = 99, kHFcv = 261;
-constexpr int kLayerFragWords = 9 * 2 * 3 * 64 * 4;            // 13824 (54 KB)
-constexpr int kLayerWords = kLayerFragWords + 2 * kC;
-constexpr int kHeadOff = kStemFragWords + kStemBiasWords;      // words
-constexpr int kLayer0Off = kHeadOff + kHeadWords;              // 1840 words = 7360 B
-constexpr int kFragVec = kLayerFragWords / 4;                  // 3456 uint4
-constexpr int kStage = (kFragVec + kThreads - 1) / kThreads;   // 14 per thread
 
 struct PackArgs {
     const float *stem_w, *stem_b;
@@ -116,26 +90,9 @@ __global__ __launch_bounds__(kThreads) void board_infer_pack_kernel(PackArgs a) 
     a.out[w] = v;
 }
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 struct Spans {
     int32_t off[kMaxNets + 1];
 };
-
-// cells of wave w: {4,0}, {1,3}, {5,7}, {2,6,8}
-__device__ __forceinline__ int wave_cell(int wave, int s) {
-    const int packed = wave == 0 ? 0x004 : wave == 1 ? 0x031 : wave == 2 ? 0x075 : 0x862;
-    return (packed >> (4 * s)) & 15;
-}
-
-// a layer's B fragments, global -> registers (thread tid's share of the 3456 uint4)
-__device__ __forceinline__ void prefetch(u32x4 (&wst)[kStage], const uint32_t *pack, int layer, int tid) {
-    const u32x4 *src = reinterpret_cast<const u32x4 *>(pack + kLayer0Off + (int64_t)layer * kLayerWords);
-#pragma unroll
-    for (int i = 0; i < kStage; ++i) {
-        const int idx = tid + i * kThreads;
-        wst[i] = src[idx < kFragVec ? idx : kFragVec - 1];
-    }
-}
 
 __global__ __launch_bounds__(kThreads) void board_infer_kernel(const uint8_t *__restrict__ packs,
                                                                int64_t pack_stride, int K, Spans sp,
@@ -146,7 +103,7 @@ __global__ __launch_bounds__(kThreads) void board_infer_kernel(const uint8_t *__
     __shared__ float act[kTile * kStride];                                       // 18.1 KB
     __shared__ float obs_lds[kTile * kObs];
     __shared__ float head_w[kHeadWords];
-    __shared__ float h_lds[kTile * 28];
+    __shared__ float h_lds[kTile * kHMid];
 
     // the tile's net and rows: tiles are laid out span by span
     int b = blockIdx.x, net = 0, row0 = 0, valid = 0;
@@ -165,166 +122,23 @@ __global__ __launch_bounds__(kThreads) void board_infer_kernel(const uint8_t *__
     if (valid > kTile) valid = kTile;
 
     const uint32_t *pack = reinterpret_cast<const uint32_t *>(packs + (int64_t)net * pack_stride);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int ar = lane & 15, ak = lane >> 4;
-    const int nq = wave == 3 ? 3 : 2;
+    const int tid = threadIdx.x;
 
-    // observation tile and head weights -> LDS; rows past the span read as zeros
-    for (int i = tid; i < kTile * kObs; i += kThreads) {
-        const int r = i / kObs;
-        obs_lds[i] = r < valid ? obs[(int64_t)row0 * kObs + i] : 0.f;
-    }
-    for (int i = tid; i < kHeadWords; i += kThreads) head_w[i] = __uint_as_float(pack[kHeadOff + i]);
-
-    // layer 0's B fragments: global -> registers now, -> LDS after the stem
-    u32x4 wst[kStage];
-    prefetch(wst, pack, 0, tid);
-
-    // ---- stem: out[q][co] = relu(sum_k A_q[row][k] W[k][co] + bias[co]), k = ci*9 + tap over the cell's neighbourhood
-    {
-        const uint4 *sf = reinterpret_cast<const uint4 *>(pack) + lane;
-        uint4 B[2][3];
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-            for (int part = 0; part < 3; ++part) B[ct][part] = sf[(ct * 3 + part) * 64];
-        const float sb0 = __uint_as_float(pack[kStemFragWords + ar]);
-        const float sb1 = __uint_as_float(pack[kStemFragWords + 16 + ar]);
-        __syncthreads();   // obs_lds
-#pragma unroll
-        for (int s = 0; s < 3; ++s) {
-            if (s >= nq) break;
-            const int q = wave_cell(wave, s), qy = q / 3, qx = q - 3 * qy;
-            float av[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const int k = 8 * ak + e;
-                const int ci = k / 9, t = k - 9 * ci;
-                const int py = qy + t / 3 - 1, px = qx + t % 3 - 1;
-                const bool ok = k < kObs && py >= 0 && py < 3 && px >= 0 && px < 3;
-                const float x = obs_lds[ar * kObs + (ok ? ci * 9 + py * 3 + px : 0)];
-                av[e] = ok ? x : 0.f;
-            }
-            uint4 Ah, Am, Al;
-            split8(av, Ah, Am, Al);
-#pragma unroll
-            for (int ct = 0; ct < 2; ++ct) {
-                f32x4 c = (f32x4){0.f, 0.f, 0.f, 0.f};
-                c = mfma_split(Ah, Am, Al, B[ct][0], B[ct][1], B[ct][2], c);
-                const float bias = ct == 0 ? sb0 : sb1;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int row = ak * 4 + r, co = ct * 16 + ar;      // C/D: row = (lane>>4)*4 + reg, col = lane & 15
-                    const float v = c[r] + bias;
-                    act[row * kStride + co * kCells + q] = v < 0.f ? 0.f : v;
-                }
-            }
+    // hrl_board_fwd.h; the observation tile: rows past the span read as zeros
+    board_forward_tile(pack, layers, obs_lds, act, w_lds_u, head_w, h_lds, tid, [&] {
+        for (int i = tid; i < kTile * kObs; i += kThreads) {
+            const int r = i / kObs;
+            obs_lds[i] = r < valid ? obs[(int64_t)row0 * kObs + i] : 0.f;
         }
-    }
+    });
 
-    // ---- the chain: conv -> BN -> ReLU per layer
-    for (int layer = 0; layer < layers; ++layer) {
-        {
-            u32x4 *dst = reinterpret_cast<u32x4 *>(w_lds_u);
-#pragma unroll
-            for (int i = 0; i < kStage; ++i) {
-                const int idx = tid + i * kThreads;
-                if (idx < kFragVec) dst[idx] = wst[i];
-            }
-        }
-        const uint32_t *coef = pack + kLayer0Off + (int64_t)layer * kLayerWords + kLayerFragWords;
-        float ca[2], cb[2];
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct) {
-            ca[ct] = __uint_as_float(coef[ct * 16 + ar]);
-            cb[ct] = __uint_as_float(coef[kC + ct * 16 + ar]);
-        }
-        __syncthreads();   // this layer's weights and its input tile are in LDS
-        if (layer + 1 < layers) prefetch(wst, pack, layer + 1, tid);
-
-        f32x4 acc[3][2];
-#pragma unroll
-        for (int s = 0; s < 3; ++s) acc[s][0] = acc[s][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        const float *acol = act + ar * kStride + 8 * ak * kCells;
-        const uint4 *wb = reinterpret_cast<const uint4 *>(w_lds_u) + lane;
-        float an[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) an[e] = acol[e * kCells];
-#pragma unroll 1
-        for (int p = 0; p < kCells; ++p) {
-            float av[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) av[e] = an[e];
-            if (p + 1 < kCells) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) an[e] = acol[e * kCells + p + 1];
-            }
-            uint4 Ah, Am, Al;
-            split8(av, Ah, Am, Al);
-            const int py = p / 3, px = p - 3 * py;
-#pragma unroll
-            for (int s = 0; s < 3; ++s) {
-                if (s >= nq) break;
-                const int q = wave_cell(wave, s);
-                const int dy = py - q / 3 + 1, dx = px - q % 3 + 1;    // wave-uniform: scalar branches
-                if (dy < 0 || dy > 2 || dx < 0 || dx > 2) continue;
-                const int tap = dy * 3 + dx;
-#pragma unroll
-                for (int ct = 0; ct < 2; ++ct) {
-                    const uint4 *wf = wb + (tap * 2 + ct) * 3 * 64;
-                    const uint4 Bh = wf[0], Bm = wf[64], Bl = wf[128];
-                    acc[s][ct] = mfma_split(Ah, Am, Al, Bh, Bm, Bl, acc[s][ct]);
-                }
-            }
-        }
-        __syncthreads();   // every wave has read the tile and the weights: both may be overwritten
-#pragma unroll
-        for (int s = 0; s < 3; ++s) {
-            if (s >= nq) break;
-            const int q = wave_cell(wave, s);
-#pragma unroll
-            for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int row = ak * 4 + r, co = ct * 16 + ar;
-                    const float v = acc[s][ct][r] * ca[ct] + cb[ct];
-                    act[row * kStride + co * kCells + q] = v < 0.f ? 0.f : v;
-                }
-        }
-    }
-    __syncthreads();   // the last layer's tile is whole
-
-    // ---- heads: 1x1 conv + bias, LeakyReLU(0.1); the 27 mid values of a row are [policy c0 | policy c1 | value]
-    const float *as = act;
-    for (int i = tid; i < kTile * 27; i += kThreads) {
-        const int row = i / 27, j = i - row * 27;
-        const int c = j / 9, q = j - 9 * c;
-        const float *w1 = head_w + (c < 2 ? kHW1p + c * kC : kHW1v);
-        const float *x = as + row * kStride + q;
-        float sum = 0.f;
-#pragma unroll 8
-        for (int ci = 0; ci < kC; ++ci) sum += x[ci * kCells] * w1[ci];
-        sum += c < 2 ? head_w[kHB1p + c] : head_w[kHB1v];
-        h_lds[row * 28 + j] = sum > 0.f ? sum : sum * 0.1f;
-    }
-    __syncthreads();
     if (tid < kTile * 10) {
         const int row = tid / 10, o = tid - row * 10;
         if (row < valid) {
-            const float *h = h_lds + row * 28;
-            if (o < kA) {
-                const float *w = head_w + kHFcp + o * 18;
-                float sum = 0.f;
-#pragma unroll
-                for (int j = 0; j < 18; ++j) sum += h[j] * w[j];
-                policy[(int64_t)(row0 + row) * kA + o] = sum;
-            } else {
-                const float *w = head_w + kHFcv;
-                float sum = 0.f;
-#pragma unroll
-                for (int j = 0; j < 9; ++j) sum += h[18 + j] * w[j];
-                value[row0 + row] = tanhf(sum);
-            }
+            if (o < kA)
+                policy[(int64_t)(row0 + row) * kA + o] = board_policy_out(h_lds, head_w, row, o);
+            else
+                value[row0 + row] = board_value_out(h_lds, head_w, row);
         }
     }
 }

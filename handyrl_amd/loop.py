@@ -32,10 +32,16 @@ class SelfPlayTrainer:
     ``rollout.StreamGenerator`` (``games_per_round`` slots that restart in place; a round plays until that many
     more games are in the ring) instead of the lockstep ``DeviceGenerator``.  ``fused_inference``: self-play runs
     ``nn.BoardInference(net)`` (``play_net``, also the net to hand to ``evaluate_vs_random``); the learner trains
-    ``net`` itself."""
+    ``net`` itself.  ``fused_game`` (with ``fused_inference``, without ``stream``): the lockstep generator plays a whole
+    round in one launch (``DeviceGenerator(fused_game=True)``), the same episodes bit for bit."""
 
     def __init__(self, net, args, device, games_per_round=4096, capacity=65536, graph=False, seed=0,
-                 env_cls=TicTacToeBatch, obs_dtype=torch.uint8, stream=False, fused_inference=False):
+                 env_cls=TicTacToeBatch, obs_dtype=torch.uint8, stream=False, fused_inference=False,
+                 fused_game=False):
+        if fused_game and not fused_inference:
+            raise ValueError('fused_game requires fused_inference=True (the one-launch game runs nn.BoardInference)')
+        if fused_game and stream:
+            raise ValueError('fused_game is the lockstep generator\'s option: it cannot be combined with stream=True')
         self.args = args
         self.device = device
         self.env = env_cls(games_per_round, device)
@@ -47,7 +53,7 @@ class SelfPlayTrainer:
         if self.stream:
             self.gen = StreamGenerator(self.env, self.play_net, self.replay, gamma=args['gamma'], seed=seed)
         else:
-            self.gen = DeviceGenerator(self.env, self.play_net, gamma=args['gamma'])
+            self.gen = DeviceGenerator(self.env, self.play_net, gamma=args['gamma'], fused_game=bool(fused_game))
         self.learner = LearnerStep(net, args, device, graph=graph)
         self.hidden = None
         if hasattr(net, 'init_hidden'):

@@ -33,6 +33,8 @@ written) with the actors and the learner on the GPU:
   waits for the longest game of a batch.  Every call plays until ``update_episodes`` more games are in the ring
   (it may overshoot by less than one check interval) and the episode counts follow what was actually emitted;
   any other mode with ``stream`` raises at start-up;
+* ``self_play: fused`` is the lockstep generator with ``fused_game=True``: every ``generate`` call is one launch that
+  plays all the games to the end (TicTacToe's stock mode on a CUDA device with ``inference: fused``; else it raises);
 * ``update_episodes`` games per epoch with the current weights (the
   reference's workers hold the latest published model), recency-weighted
   replay of ``maximum_episodes``; training starts once ``minimum_episodes``
@@ -197,8 +199,13 @@ def train_main(args, device=None, loss_fn=None, model_dir='models', log=print):
     maximum = _per_rank(targs['maximum_episodes'], world)
     rng = torch.Generator(device=device).manual_seed(seed)
     self_play = targs.get('self_play', 'lockstep')
-    if self_play not in ('lockstep', 'stream'):
-        raise ValueError("train_args['self_play'] must be lockstep or stream, not %r" % (self_play,))
+    if self_play not in ('lockstep', 'stream', 'fused'):
+        raise ValueError("train_args['self_play'] must be lockstep, stream or fused, not %r" % (self_play,))
+    if self_play == 'fused' and (device.type != 'cuda' or not use_device or per_player or batched is not TicTacToeBatch
+                                 or infer_mode != 'fused'):
+        raise ValueError("train_args['self_play']: 'fused' plays whole TicTacToe games in one launch: it needs a CUDA "
+                         "device, the stock mode (turn_based_training without observation) of the TicTacToe batched "
+                         "env and inference: fused; this configuration is played by self_play: lockstep")
     if self_play == 'stream' and (not use_device or per_player or not getattr(batched, 'ALTERNATING', False)):
         raise ValueError("train_args['self_play']: 'stream' plays the mover-only ply of an alternating env with a "
                          "batched (device) form (turn_based_training without observation); this configuration is "
@@ -238,7 +245,7 @@ def train_main(args, device=None, loss_fn=None, model_dir='models', log=print):
             return float(out['env_steps'])
     elif use_device:
         gen = DeviceGenerator(batched(games, device), play_net, gamma=targs['gamma'], observation=observe,
-                              per_player=per_player)
+                              per_player=per_player, fused_game=self_play == 'fused')
         # binary observation planes live in HBM as uint8 (widened by the gather)
         if per_player:
             replay = PlayerReplay(maximum, batched.MAX_PLIES, batched.OBS_SHAPE, batched.A, batched.P, device,

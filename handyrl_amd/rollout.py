@@ -287,9 +287,18 @@ class DeviceGenerator:
     turn player's ``random.choices`` draws and sel (E, Tm) the simultaneous
     env's played-player uniforms (``reference_uniforms``), so seeded reference
     games replay move for move.
+
+    ``fused_game=True`` (opt-in; TicTacToe with a ``nn.BoardInference`` net): on a CUDA env a call is ONE
+    ``hrl_board_selfplay`` launch (csrc/hrl_boardplay.hip) for all nine plies of all E games -- observation,
+    forward, sampling, records and rules, the games resident in LDS -- on the same buffers, the env's own state
+    tensors and the same uniforms instead of the ply loop; no graph is captured and the episodes are the ply loop's
+    bit for bit.  The env must be exactly a ``TicTacToeBatch`` in the mover-only mode and the net a
+    ``BoardInference``; a member of a ``board_inference_group`` is accepted and plays from its row of the group's
+    buffer.  Anything else raises ``ValueError`` here.  On a CPU env the option runs the ordinary ply loop.
     """
 
-    def __init__(self, env_batch, net, gamma=0.8, check_every=16, graph=None, observation=False, per_player=None):
+    def __init__(self, env_batch, net, gamma=0.8, check_every=16, graph=None, observation=False, per_player=None,
+                 fused_game=False):
         self.env = env_batch
         self.net = net
         self.gamma = gamma
@@ -299,6 +308,18 @@ class DeviceGenerator:
         # per_player=True also for a mover-only alternating game whose batches need per-player records (solo)
         self.per_player = (self.observation or getattr(env_batch, 'SIMULTANEOUS', False) if per_player is None
                            else bool(per_player) or self.observation or getattr(env_batch, 'SIMULTANEOUS', False))
+        self.fused_game = bool(fused_game)
+        if self.fused_game:
+            from .nn import BoardInference
+            if type(env_batch) is not TicTacToeBatch:
+                raise ValueError('fused_game: the one-launch game plays the rules of TicTacToeBatch itself, not %s'
+                                 % type(env_batch).__name__)
+            if self.per_player:
+                raise ValueError('fused_game: the one-launch game is the mover-only ply (no observation, no '
+                                 'per-player records)')
+            if not isinstance(net, BoardInference):
+                raise ValueError('fused_game: the one-launch game runs the forward of nn.BoardInference, not %s'
+                                 % type(net).__name__)
         self._st = None
 
     def _use_graph(self):
@@ -570,8 +591,38 @@ class DeviceGenerator:
                    if (not self.per_player or st.get('flat_state') or getattr(self.net, 'stateless_session', False))
                    else None)
         with session(inplace_state=st['pmajor']) if session is not None else contextlib.nullcontext():
-            out = self._generate(st, generator, alternating, reference)
+            if self.fused_game and st['obs_dev'] == 'cuda':
+                out = self._generate_fused(st, generator)
+            else:
+                out = self._generate(st, generator, alternating, reference)
         self.net.train(was_training)
+        return out
+
+    def _generate_fused(self, st, generator):
+        """``_generate`` with the ply loop as one launch (``fused_game``), inside the net's inference session.  The
+        kernel stores every slot of every record, so of ``_reset`` only the env's and the draw of the uniforms run
+        (reward / ret stay the zeros they were allocated as: TicTacToe has no per-ply reward)."""
+        from . import _native
+        env, net = self.env, self.net
+        E, Tm = env.E, env.MAX_PLIES
+        env.reset()
+        torch.rand(st['U'].shape, out=st['U'], generator=generator, device=st['U'].device)
+        st['U'].clamp_(1e-20, 1.0)
+        dev = st['U'].device
+        for x in env.state_tensors() + [st['obs'], st['policy'], st['amask'], st['action'], st['value'], st['turn']]:
+            assert x.is_contiguous() and x.device == dev
+        assert (env.board.dtype, env.color.dtype, env.nmoves.dtype, env.winner.dtype) == \
+            (torch.int8, torch.int8, torch.int32, torch.int8) and env.board.shape == (E, 9)
+        _native.check(_native.load().hrl_board_selfplay(
+            _native.ptr(net.pack(dev)), net.layers, E, Tm, 0, Tm, _native.ptr(st['U']), _native.ptr(env.board),
+            _native.ptr(env.color), _native.ptr(env.nmoves), _native.ptr(env.winner), _native.ptr(st['obs']),
+            _native.ptr(st['policy']), _native.ptr(st['amask']), _native.ptr(st['action']), _native.ptr(st['value']),
+            _native.ptr(st['turn']), _native.stream_of(dev)), 'hrl_board_selfplay')
+        out = {'observation': st['obs'].clone()}
+        for key, k in (('policy', 'policy'), ('action_mask', 'amask'), ('action', 'action'), ('value', 'value'),
+                       ('turn', 'turn'), ('return', 'ret')):
+            out[key] = st[k].clone()
+        out.update(length=env.plies().long(), outcome=env.outcome(), reward=st['reward'].float())
         return out
 
     def _generate(self, st, generator, alternating, reference=None):

@@ -94,6 +94,25 @@ int hrl_selfplay_sample_record_stream(const float *logits, int64_t logit_stride,
                                       float *amask_buf, int64_t *action_buf, float *value_buf, int64_t *turn_buf,
                                       double *reward_buf, void *stream);
 
+/* Whole TicTacToe self-play games in ONE launch (csrc/hrl_boardplay.hip): plies t0 <= t < t1 <= Tm <= 9 of
+ * rollout.DeviceGenerator's mover-only ply on a TicTacToeBatch with a nn.BoardInference net, for E games, 16 per
+ * workgroup.  pack: one hrl_board_infer_pack pack (include/hrl_nn.h; 16-byte aligned) of a net of `layers` blocks.
+ * U (Tm, E, 9) uniforms in (0, 1].  board (E, 9) int8, color (E,) int8, nmoves (E,) int32, winner (E,) int8: the
+ * env's state, advanced in place.  Per game and ply, in DeviceGenerator._ply's order: active = winner == 0 &&
+ * nmoves < 9, player = nmoves % 2; the mover's view [1, board == color, board == -color]; hrl_board_infer's forward
+ * (the same device code: the same bits); hrl_selfplay_sample_record's sampling (m = legal ? 0 : 1e32, p = logit - m,
+ * argmax(p - log(-log(u))), torch.argmax's tie order); slot (e, t) of obs (E, Tm, 27), policy / amask (E, Tm, 9)
+ * fp32 and action / value / turn (E, Tm) int64 / fp32 / int64 gets the live value of an active game, else 0, 0, 1e32,
+ * 0, 0, 0 -- every slot of plies [t0, t1) is written for every game, whatever the buffers held; then
+ * TicTacToeBatch.step for the active games (the cell takes color; winner = color on a line of three; color flips;
+ * nmoves + 1).  Calls over [t0, tm) and [tm, t1) equal one over [t0, t1).  Asynchronous, allocates nothing,
+ * capturable.  HRL_EINVAL (before any HIP call) for a NULL pointer, layers outside 1..8, a pack that is not 16-byte
+ * aligned, E < 0 (or E > 2^31 - 17), Tm outside 1..9, t0 < 0, t1 > Tm, t0 > t1; E == 0 or t0 == t1: HRL_OK, no
+ * launch. */
+int hrl_board_selfplay(const void *pack, int64_t layers, int64_t E, int64_t Tm, int64_t t0, int64_t t1, const float *U,
+                       int8_t *board, int8_t *color, int32_t *nmoves, int8_t *winner, float *obs, float *policy,
+                       float *amask, int64_t *action, float *value, int64_t *turn, void *stream);
+
 /* The slot records of the streaming generator (DeviceGenerator's mover-only layout), DEVICE pointers to
  * C-contiguous fp32 / int64 / fp64 tensors; the struct itself is HOST memory read before the call returns:
  *   obs[l] (E, Tm, obs_width[l]) fp32, l < nleaves <= 8      policy, amask (E, Tm, A) fp32
