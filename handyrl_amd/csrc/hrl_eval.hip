@@ -2,10 +2,12 @@
 // seat of every game, a uniform random agent on the others, E slots that restart in place until G games are played.
 //
 // evaluation.DeviceEvaluator runs, per global step, the env's observation and the net's forward, then
-//   eval_act_kernel      one wave per slot, lanes over the A labels: the model seat's argmax (or Gumbel-max at a
-//                        temperature) of the masked logits, the random seat's k-th legal label (eval_pick);
-//   (match_act_kernel    the same launch for a match against a second net: the other seats play that net's move at
-//                        its own temperature, and the first `opening` plies of a game are eval_pick on every seat;)
+//   match_act_kernel     one wave per slot, lanes over the A labels: the model seat's argmax (or Gumbel-max at a
+//                        temperature) of the masked logits, the random seat's k-th legal label (eval_pick); in a match
+//                        against a second net the other seats play that net's move at its own temperature, and the
+//                        first `opening` plies of a game are eval_pick on every seat.  It is the ONE decision kernel
+//                        (one source body, two instantiations: with and without the second net's pointer pair):
+//                        hrl_eval_act is hrl_match_act without an opponent and without opening plies;
 //   the env's step;
 //   eval_finish_kernel   one workgroup: ply += 1, the finished games' outcome and length stored BY GAME NUMBER, the
 //                        slots restarted with the next game numbers in slot order or retired, the state advanced.
@@ -102,36 +104,11 @@ __device__ __forceinline__ void store_move(const int64_t *__restrict__ forced, i
     }
 }
 
-__global__ __launch_bounds__(kWave *kSlotsPerBlock) void eval_act_kernel(
-    const float *__restrict__ logits, int64_t lstride, const uint8_t *__restrict__ legal, uint32_t k0, uint32_t k1,
-    float inv_t, const int64_t *__restrict__ game, const int64_t *__restrict__ ply,
-    const uint8_t *__restrict__ active, const int64_t *__restrict__ seat, int64_t mover,
-    const int64_t *__restrict__ forced, int64_t E, int A, int64_t Tm, int64_t G, int64_t *__restrict__ action,
-    EvalTrace tr) {
-    const int lane = threadIdx.x % kWave;
-    const int64_t e = (int64_t)blockIdx.x * kSlotsPerBlock + threadIdx.x / kWave;
-    if (e >= E) return;
-    const int64_t t = ply[e], g = game[e];
-    if (!active[e] || t < 0 || t >= Tm || g < 0 || g >= G) {   // wave-uniform
-        if (lane == 0) action[e] = 0;
-        return;
-    }
-    const uint32_t g0 = (uint32_t)(uint64_t)g, g1 = (uint32_t)((uint64_t)g >> 32), tw = (uint32_t)t;
-    const uint8_t *lm = legal + e * A;
-    const bool model = seat[e] == mover;   // wave-uniform
-    int pick;
-    if (model) {
-        float *pol = tr.action ? tr.policy + (g * Tm + t) * A : nullptr;
-        pick = net_pick(logits + e * lstride, lm, pol, A, inv_t, k0, k1, g0, g1, tw, lane);
-    } else {
-        pick = random_pick(lm, A, k0, k1, g0, g1, tw, lane);
-    }
-    if (lane == 0) store_move(forced, g * Tm + t, pick, model, action + e, tr);
-}
-
-// The match ply: a second net on the other seats and `opening` random plies.  Per slot: the mover's net is home
-// where seat == mover, else opp (or none: opp NULL); its masked logits go to the trace whenever there is one; the
-// move is eval_pick at an opening ply or without a net, else that net's argmax / Gumbel-max at its own temperature.
+// The ply's decision, against random agents (opp NULL, opening 0), in a match and in a league.  Per slot: the mover's
+// net is home where seat == mover, else opp (or none: opp NULL); its masked logits go to the trace whenever there is
+// one; the move is eval_pick at an opening ply or without a net, else that net's argmax / Gumbel-max at its own
+// temperature.  kOpp false is the form without a second net (hrl_eval_act): the opp pointer pair is compiled out.
+template <bool kOpp>
 __global__ __launch_bounds__(kWave *kSlotsPerBlock) void match_act_kernel(
     const float *__restrict__ home, int64_t hstride, const float *__restrict__ opp, int64_t ostride,
     const uint8_t *__restrict__ legal, uint32_t k0, uint32_t k1, float inv_t_home, float inv_t_opp, int64_t opening,
@@ -149,7 +126,7 @@ __global__ __launch_bounds__(kWave *kSlotsPerBlock) void match_act_kernel(
     const uint32_t g0 = (uint32_t)(uint64_t)g, g1 = (uint32_t)((uint64_t)g >> 32), tw = (uint32_t)t;
     const uint8_t *lm = legal + e * A;
     const bool model = seat[e] == mover;   // wave-uniform, as is everything below
-    const float *lg = model ? home + e * hstride : opp ? opp + e * ostride : nullptr;
+    const float *lg = model ? home + e * hstride : kOpp && opp ? opp + e * ostride : nullptr;
     int pick = 0;
     if (lg) {
         float *pol = tr.action ? tr.policy + (g * Tm + t) * A : nullptr;
@@ -237,22 +214,10 @@ int hrl_eval_act(const float *logits, int64_t logit_stride, const uint8_t *legal
                  const int64_t *forced, int64_t E, int64_t A, int64_t Tm, int64_t P, int64_t G, int64_t *action,
                  int64_t *trace_action, int64_t *trace_picked, float *trace_policy, uint8_t *trace_model_ply,
                  void *stream) {
-    const int ntrace = (trace_action != nullptr) + (trace_picked != nullptr) + (trace_policy != nullptr) +
-                       (trace_model_ply != nullptr);
-    if (!logits || !legal || !game || !ply || !active || !seat || !action || E < 0 || E > 0x7fffffff || A < 1 ||
-        A > (1 << 20) || Tm < 1 || P < 1 || G < 0 || logit_stride < A || mover < 0 || mover >= P ||
-        !(temperature >= 0.0) || (ntrace != 0 && ntrace != 4))
-        return HRL_EINVAL;
-    if (E == 0) return HRL_OK;
-    const float inv_t = temperature > 0.0 ? (float)(1.0 / temperature) : 0.0f;
-    EvalTrace tr{trace_action, trace_picked, trace_policy, trace_model_ply};
-    const int blocks = (int)((E + kSlotsPerBlock - 1) / kSlotsPerBlock);
-    hipLaunchKernelGGL(eval_act_kernel, dim3(blocks), dim3(kWave * kSlotsPerBlock), 0,
-                       static_cast<hipStream_t>(stream), logits, logit_stride, legal, (uint32_t)seed,
-                       (uint32_t)(seed >> 32), inv_t, game, ply, active, seat, mover, forced, E, (int)A, Tm, G, action,
-                       tr);
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? HRL_OK : HRL_ELAUNCH_BASE - (int)err;
+    // no opponent, no opening plies: the same kernel, and for these arguments the same argument checks
+    return hrl_match_act(logits, logit_stride, nullptr, 0, legal, seed, temperature, 0.0, 0, game, ply, active, seat,
+                         mover, forced, E, A, Tm, P, G, action, trace_action, trace_picked, trace_policy,
+                         trace_model_ply, stream);
 }
 
 int hrl_match_act(const float *logits_home, int64_t stride_home, const float *logits_opp, int64_t stride_opp,
@@ -273,7 +238,8 @@ int hrl_match_act(const float *logits_home, int64_t stride_home, const float *lo
     const float inv_opp = temperature_opp > 0.0 ? (float)(1.0 / temperature_opp) : 0.0f;
     EvalTrace tr{trace_action, trace_picked, trace_policy, trace_model_ply};
     const int blocks = (int)((E + kSlotsPerBlock - 1) / kSlotsPerBlock);
-    hipLaunchKernelGGL(match_act_kernel, dim3(blocks), dim3(kWave * kSlotsPerBlock), 0,
+    const auto kernel = logits_opp ? match_act_kernel<true> : match_act_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kWave * kSlotsPerBlock), 0,
                        static_cast<hipStream_t>(stream), logits_home, stride_home, logits_opp, stride_opp, legal,
                        (uint32_t)seed, (uint32_t)(seed >> 32), inv_home, inv_opp, opening, game, ply, active, seat,
                        mover, forced, E, (int)A, Tm, G, action, tr);

@@ -5,7 +5,8 @@
 //   rows_permute_kernel    the observation leaves from slot order into net-major order (every net's rows adjacent);
 //   each net's forward over its own rows only;
 //   rows_permute_kernel    the nets' logits back into slot order;
-//   match_act_kernel       (hrl_eval.hip, unchanged) both logit pointers at the slot-ordered buffer;
+//   match_act_kernel       (hrl_eval.hip: the one decision kernel of every evaluator) both logit pointers at the
+//                          slot-ordered buffer;
 //   the env's step;
 //   league_finish_kernel   one workgroup: ply += 1, a finished game's outcome and length stored at [block][game], the
 //                          slot restarted with game + S or retired.  A slot's seat never changes (S is even), so no

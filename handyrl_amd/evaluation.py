@@ -27,19 +27,21 @@ A league (``LeagueEvaluator``, ``main.py --eval-league``) plays a round robin of
 those of the match above, with each net forwarded only over the rows where it moves, and rates the agents with
 ``bradley_terry``; include/hrl_env.h has its rules.
 
-``FUSED_EVAL``: on a GPU the ply's decision and bookkeeping are the launches of hrl_eval_act (hrl_match_act in a
-match), hrl_eval_finish and hrl_masked_rows_fill (csrc/hrl_eval.hip); the torch formulation below is the CPU path and
-the form the kernels are tested against.
+``FUSED_EVAL``: on a GPU the ply's decision and bookkeeping are the launches of hrl_match_act (the one decision
+kernel; hrl_eval_act is its form without an opponent and opening plies), hrl_eval_finish and hrl_masked_rows_fill
+(csrc/hrl_eval.hip); the torch formulation below is the CPU path and the form the kernels are tested against.
 """
 
 import contextlib
+import functools
 import math
 import os
 
 import numpy as np
 import torch
 
-from .rollout import _M32, _PHILOX_M, _PHILOX_W, _leaves, philox4x32, stream_uniforms_torch
+from .rollout import (_M32, _PHILOX_M, _PHILOX_W, _leaves, capture_graphs, eval_mode, graph_wanted, params_key,
+                      philox4x32, stream_uniforms_torch)
 from .util import map_r
 
 __all__ = ['DeviceEvaluator', 'eval_pick', 'eval_pick_torch', 'eval_main', 'eval_match_main', 'wp_func', 'eval_games',
@@ -125,42 +127,24 @@ def _check_env(cls, name=None):
 
 def act_torch(st, logits, legal, mover, seed, temperature, G, forced=None, trace=None):
     """hrl_eval_act: the action of every slot, 0 for an inactive one; ``trace`` (dict or None) gets the records."""
-    game, ply, active, seat = st['game'], st['ply'], st['active'], st['seat']
-    E, A = legal.shape
-    Tm = st['Tm']
-    ok = active & (ply >= 0) & (ply < Tm) & (game >= 0) & (game < G)
-    m = torch.where(legal, 0.0, 1e32)
-    p = logits[:, :A].float() - m
-    v = p
-    if temperature > 0:
-        u = stream_uniforms_torch(seed, game, ply, A)
-        v = p * float(np.float32(1.0 / temperature)) - torch.log(-torch.log(u))
-    model = seat == mover
-    pick = torch.where(model, torch.argmax(v, dim=-1), eval_pick_torch(seed, game, ply, legal))
-    g = torch.where(ok, game, G)
-    t = torch.where(ok, ply, 0)
-    a = pick
-    if forced is not None:
-        f = forced[g, t]
-        a = torch.where(f >= 0, f, pick)
-    a = torch.where(ok, a, 0)
-    if trace is not None:
-        trace['action'][g, t] = a
-        trace['picked'][g, t] = pick
-        trace['model_ply'][g, t] = model
-        trace['policy'][torch.where(model, g, G), t] = p
-    return a
+    return match_act_torch(st, logits, None, legal, mover, seed, temperature, 0.0, 0, G, forced, trace)
 
 
-def act_hip(st, logits, legal, mover, seed, temperature, G, forced=None, trace=None):
-    """act_torch as ONE launch (hrl_eval_act, one wave per slot)."""
+def _act_operands(st, rows, legal, mover, G, forced, trace):
+    """What hrl_eval_act and hrl_match_act both take, checked: the logits of ``rows`` (None stays None) as fp32 with
+    unit inner stride, ``legal`` contiguous, the action buffer, and the entries' common arguments from ``game`` on."""
     from . import _native
     E, A = legal.shape
-    logits = logits.float()
-    if logits.stride(1) != 1:
-        logits = logits.contiguous()
     legal = legal.contiguous()
-    assert logits.shape[0] == E and logits.shape[1] >= A and legal.dtype == torch.bool
+    assert legal.dtype == torch.bool
+    rows = list(rows)
+    for i, logits in enumerate(rows):
+        if logits is not None:
+            logits = logits.float()
+            if logits.stride(1) != 1:
+                logits = logits.contiguous()
+            assert logits.shape[0] == E and logits.shape[1] >= A
+            rows[i] = logits
     for k in ('game', 'ply', 'seat'):
         assert st[k].shape == (E,) and st[k].dtype == torch.long and st[k].is_contiguous()
     assert st['active'].shape == (E,) and st['active'].dtype == torch.bool
@@ -175,19 +159,27 @@ def act_hip(st, logits, legal, mover, seed, temperature, G, forced=None, trace=N
         assert tr[0].dtype == tr[1].dtype == torch.long and tr[2].dtype == torch.float32 and tr[2].shape[2] == A
         assert tr[3].dtype == torch.bool
     a = torch.empty(E, dtype=torch.long, device=legal.device)
+    tail = [_native.ptr(st['game']), _native.ptr(st['ply']), _native.ptr(st['active']), _native.ptr(st['seat']),
+            int(mover), _native.ptr(forced), E, A, Tm, st['P'], G, _native.ptr(a), *[_native.ptr(x) for x in tr],
+            _native.stream_of(legal.device)]
+    return rows, legal, a, tail
+
+
+def act_hip(st, logits, legal, mover, seed, temperature, G, forced=None, trace=None):
+    """act_torch as ONE launch (the hrl_eval_act entry, one wave per slot)."""
+    from . import _native
+    (logits,), legal, a, tail = _act_operands(st, [logits], legal, mover, G, forced, trace)
     _native.check(_native.load().hrl_eval_act(
         _native.ptr(logits), logits.stride(0), _native.ptr(legal), int(seed) & 0xffffffffffffffff,
-        float(temperature), _native.ptr(st['game']), _native.ptr(st['ply']), _native.ptr(st['active']),
-        _native.ptr(st['seat']), int(mover), _native.ptr(forced), E, A, Tm, st['P'], G, _native.ptr(a),
-        *[_native.ptr(x) for x in tr], _native.stream_of(legal.device)), 'hrl_eval_act')
+        float(temperature), *tail), 'hrl_eval_act')
     return a
 
 
 def match_act_torch(st, logits_home, logits_opp, legal, mover, seed, temperature_home, temperature_opp, opening, G,
                     forced=None, trace=None):
-    """hrl_match_act: ``act_torch`` with a second net on the other seats (``logits_opp`` None: they play
-    ``eval_pick``) and ``opening`` random plies on every seat.  With ``logits_opp`` None and ``opening`` 0 these are
-    ``act_torch``'s operations."""
+    """hrl_match_act, the one decision of every evaluator: the home net where ``seat == mover``, a second net on the
+    other seats (``logits_opp`` None: they play ``eval_pick``) and ``opening`` random plies on every seat.  The action
+    of every slot, 0 for an inactive one; ``trace`` (dict or None) gets the records."""
     game, ply, active, seat = st['game'], st['ply'], st['active'], st['seat']
     E, A = legal.shape
     Tm = st['Tm']
@@ -232,37 +224,11 @@ def match_act_hip(st, logits_home, logits_opp, legal, mover, seed, temperature_h
                   forced=None, trace=None):
     """match_act_torch as ONE launch (hrl_match_act, one wave per slot)."""
     from . import _native
-    E, A = legal.shape
-    legal = legal.contiguous()
-    assert legal.dtype == torch.bool
-    rows = []
-    for logits in (logits_home, logits_opp):
-        if logits is not None:
-            logits = logits.float()
-            if logits.stride(1) != 1:
-                logits = logits.contiguous()
-            assert logits.shape[0] == E and logits.shape[1] >= A
-        rows.append(logits)
-    for k in ('game', 'ply', 'seat'):
-        assert st[k].shape == (E,) and st[k].dtype == torch.long and st[k].is_contiguous()
-    assert st['active'].shape == (E,) and st['active'].dtype == torch.bool
-    Tm = st['Tm']
-    if forced is not None:
-        assert forced.dtype == torch.long and forced.is_contiguous() and forced.shape[0] >= G
-        assert forced.shape[1] == Tm
-    tr = [None] * 4
-    if trace is not None:
-        tr = [trace[k] for k in ('action', 'picked', 'policy', 'model_ply')]
-        assert all(x.is_contiguous() and x.shape[0] >= G and x.shape[1] == Tm for x in tr)
-        assert tr[0].dtype == tr[1].dtype == torch.long and tr[2].dtype == torch.float32 and tr[2].shape[2] == A
-        assert tr[3].dtype == torch.bool
-    a = torch.empty(E, dtype=torch.long, device=legal.device)
+    (home, opp), legal, a, tail = _act_operands(st, [logits_home, logits_opp], legal, mover, G, forced, trace)
     _native.check(_native.load().hrl_match_act(
-        _native.ptr(rows[0]), rows[0].stride(0), _native.ptr(rows[1]), 0 if rows[1] is None else rows[1].stride(0),
-        _native.ptr(legal), int(seed) & 0xffffffffffffffff, float(temperature_home), float(temperature_opp),
-        int(opening), _native.ptr(st['game']), _native.ptr(st['ply']), _native.ptr(st['active']),
-        _native.ptr(st['seat']), int(mover), _native.ptr(forced), E, A, Tm, st['P'], G, _native.ptr(a),
-        *[_native.ptr(x) for x in tr], _native.stream_of(legal.device)), 'hrl_match_act')
+        _native.ptr(home), home.stride(0), _native.ptr(opp), 0 if opp is None else opp.stride(0), _native.ptr(legal),
+        int(seed) & 0xffffffffffffffff, float(temperature_home), float(temperature_opp), int(opening), *tail),
+        'hrl_match_act')
     return a
 
 
@@ -289,15 +255,23 @@ def finish_torch(st, terminal, outcome, G, outcome_out, length_out):
     state[1:2].copy_(torch.clamp(state[1] + c, max=G).view(1))
 
 
+def _finish_operands(st, terminal, outcome, rows, outcome_out, length_out):
+    """The env's ``terminal`` and ``outcome`` as the finish kernels read them, and the checks both share on them and
+    on the two result buffers of at least ``rows`` rows."""
+    E, P = st['game'].shape[0], st['P']
+    terminal, outcome = terminal.contiguous(), outcome.float().contiguous()
+    assert terminal.shape == (E,) and terminal.dtype == torch.bool and outcome.shape == (E, P)
+    assert outcome_out.shape[0] >= rows and outcome_out.shape[1] == P and outcome_out.dtype == torch.float32
+    assert length_out.shape[0] >= rows and length_out.dtype == torch.long
+    assert outcome_out.is_contiguous() and length_out.is_contiguous()
+    return terminal, outcome
+
+
 def finish_hip(st, terminal, outcome, G, outcome_out, length_out):
     """finish_torch as ONE launch of one workgroup (hrl_eval_finish)."""
     from . import _native
     E, P = st['game'].shape[0], st['P']
-    terminal, outcome = terminal.contiguous(), outcome.float().contiguous()
-    assert terminal.shape == (E,) and terminal.dtype == torch.bool and outcome.shape == (E, P)
-    assert outcome_out.shape[0] >= G and outcome_out.shape[1] == P and outcome_out.dtype == torch.float32
-    assert length_out.shape[0] >= G and length_out.dtype == torch.long
-    assert outcome_out.is_contiguous() and length_out.is_contiguous()
+    terminal, outcome = _finish_operands(st, terminal, outcome, G, outcome_out, length_out)
     assert st['pending'].dtype == torch.bool and st['state'].shape == (2,) and st['state'].dtype == torch.long
     _native.check(_native.load().hrl_eval_finish(
         _native.ptr(terminal), _native.ptr(outcome), E, st['Tm'], P, G, _native.ptr(st['active']),
@@ -352,13 +326,8 @@ def league_finish_hip(st, terminal, outcome, G, outcome_out, length_out):
     """league_finish_torch as ONE launch of one workgroup (hrl_league_finish); the kernel needs no spare row."""
     from . import _native
     E, P, S = st['game'].shape[0], st['P'], st['S']
-    terminal, outcome = terminal.contiguous(), outcome.float().contiguous()
-    assert terminal.shape == (E,) and terminal.dtype == torch.bool and outcome.shape == (E, P)
     assert S >= 2 and S % 2 == 0 and E % S == 0
-    rows = (E // S) * G
-    assert outcome_out.shape[0] >= rows and outcome_out.shape[1] == P and outcome_out.dtype == torch.float32
-    assert length_out.shape[0] >= rows and length_out.dtype == torch.long
-    assert outcome_out.is_contiguous() and length_out.is_contiguous()
+    terminal, outcome = _finish_operands(st, terminal, outcome, (E // S) * G, outcome_out, length_out)
     for k in ('game', 'ply'):
         assert st[k].shape == (E,) and st[k].dtype == torch.long and st[k].is_contiguous()
     for k in ('active', 'pending'):
@@ -405,7 +374,82 @@ def rows_permute_hip(dst, src, src_index=None, dst_index=None, n=None):
         _native.stream_of(dst[0].device)), 'hrl_rows_permute')
 
 
-class DeviceEvaluator:
+def _tally(outcomes):
+    """The {outcome: count} table of a list of outcomes, the best outcome first; a draw's -0.0 counts as 0.0."""
+    table = {}
+    for o in outcomes:
+        table[o + 0.0] = table.get(o + 0.0, 0) + 1
+    return {k: table[k] for k in sorted(table, reverse=True)}
+
+
+class _PlyEvaluator:
+    """What ``DeviceEvaluator`` and ``LeagueEvaluator`` share: the common arguments, one captured graph per mover
+    (``rollout.capture_graphs``), the replay loop that reads the device state every ``check_every`` steps, and the
+    nets' eval mode and inference sessions around a call.  A subclass has ``_state()``, ``_begin(st, run)`` (every
+    buffer as at the start of a call) and ``_ply(st, run, mover)`` (one global step), and keeps its run in
+    ``_run``: {'key', 'G', 'graphs', ...}."""
+
+    def __init__(self, env_batch, observation, temperature, opening_plies, seed, check_every, graph):
+        _check_env(type(env_batch))
+        if not temperature >= 0:
+            raise ValueError('temperature must be >= 0, not %r' % (temperature,))
+        if int(opening_plies) < 0:
+            raise ValueError('opening_plies must be >= 0, not %r' % (opening_plies,))
+        self.env = env_batch
+        self.observation, self.temperature = bool(observation), float(temperature)
+        self.opening_plies = int(opening_plies)
+        self.seed = int(seed) & 0xffffffffffffffff
+        self.check_every = max(1, int(check_every or 1))
+        self.graph = graph
+        self._st = None
+        self._run = None      # (key, per-G buffers, graphs) of the last evaluate()
+
+    def _use_graph(self):
+        return graph_wanted(self.env.device, self.graph)
+
+    def _capture(self, st, run):
+        """One graph per mover, everything of a ply one after another on the capturing stream (no parallel
+        branches); warm-up plies run first on a side stream.  ``_play`` starts the call afresh with ``_begin``, so
+        warm-up and capture leave no trace."""
+        self._begin(st, run)
+        return capture_graphs(self.env.device,
+                              {m: functools.partial(self._ply, st, run, m) for m in range(st['P'])})
+
+    def _play(self, st, run, slots, target, unfinished):
+        """Global steps until ``target`` games are finished; ``slots``: the slots one stream of game numbers 0 .. G-1
+        is played on; ``unfinished``: the error's text for (target, steps)."""
+        G, P = run['G'], st['P']
+        if G == 0:
+            return 0
+        self._begin(st, run)
+        graphs = run['graphs']
+        s = 0
+        limit = (-(-G // max(1, min(slots, G))) + 1) * (st['Tm'] + P) + self.check_every
+        while True:
+            for _ in range(self.check_every):
+                if graphs is not None:
+                    graphs[s % P].replay()
+                else:
+                    self._ply(st, run, s % P)
+                s += 1
+            if int(st['state'][0]) >= target:
+                return s
+            if s > limit:
+                raise RuntimeError(unfinished % (target, s))
+
+    @staticmethod
+    @contextlib.contextmanager
+    def _sessions(nets, inplace):
+        """The nets in eval mode and inside their inference sessions (``inplace``, per net: the session advances the
+        recurrent state in place); the training modes are put back."""
+        with eval_mode(*nets), contextlib.ExitStack() as stack:
+            for n, own in zip(nets, inplace):
+                if hasattr(n, 'inference_session'):
+                    stack.enter_context(n.inference_session(inplace_state=True) if own else n.inference_session())
+            yield
+
+
+class DeviceEvaluator(_PlyEvaluator):
     """Plays ``games`` games of ``net`` (``Agent(model, observation, temperature)``, agent.py:55-110) against
     uniform random agents (``RandomAgent``) on the E slots of ``env_batch`` (TicTacToeBatch, GeisterBatch,
     CIGeisterBatch) by the module's public rules.
@@ -431,30 +475,17 @@ class DeviceEvaluator:
 
     def __init__(self, env_batch, net, observation=False, temperature=0.0, seed=0, check_every=16, graph=None,
                  opponent=None, opponent_temperature=None, opening_plies=0):
-        _check_env(type(env_batch))
-        if not temperature >= 0:
-            raise ValueError('temperature must be >= 0, not %r' % (temperature,))
+        super().__init__(env_batch, observation, temperature, opening_plies, seed, check_every, graph)
         if opponent_temperature is None:
             opponent_temperature = temperature
         if not opponent_temperature >= 0:
             raise ValueError('opponent_temperature must be >= 0, not %r' % (opponent_temperature,))
-        if int(opening_plies) < 0:
-            raise ValueError('opening_plies must be >= 0, not %r' % (opening_plies,))
         if opponent is net:
             raise ValueError('the opponent must be a module of its own (a copy of the net plays a self-match)')
-        self.env, self.net = env_batch, net
-        self.opponent, self.opponent_temperature = opponent, float(opponent_temperature)
-        self.opening_plies = int(opening_plies)
-        self.observation, self.temperature = bool(observation), float(temperature)
-        self.seed = int(seed) & 0xffffffffffffffff
-        self.check_every = max(1, int(check_every or 1))
-        self.graph = graph
-        self._st = None
-        self._run = None      # (key, per-G buffers, graphs) of the last evaluate()
+        self.net, self.opponent, self.opponent_temperature = net, opponent, float(opponent_temperature)
 
-    def _use_graph(self):
-        dev = torch.device(self.env.device)
-        return dev.type == 'cuda' and (self.graph is None or bool(self.graph))
+    def _nets(self):
+        return [self.net] + ([] if self.opponent is None else [self.opponent])
 
     def _state(self):
         if self._st is not None:
@@ -518,15 +549,9 @@ class DeviceEvaluator:
             other = (seat + 1) % st['P']
             opp_seat = other if st['P'] == 2 else torch.where(seat != mover, torch.full_like(seat, mover), other)
             out_opp = self.opponent(env.observation(opp_seat), hidden_opp)
-        if out_opp is None and self.opening_plies == 0:
-            act = act_hip if fused else act_torch
-            a = act(st, out['policy'], env.legal(), mover, self.seed, self.temperature, run['G'], run['forced'],
-                    run['trace'])
-        else:
-            act = match_act_hip if fused else match_act_torch
-            a = act(st, out['policy'], None if out_opp is None else out_opp['policy'], env.legal(), mover, self.seed,
-                    self.temperature, self.opponent_temperature, self.opening_plies, run['G'], run['forced'],
-                    run['trace'])
+        act = match_act_hip if fused else match_act_torch
+        a = act(st, out['policy'], None if out_opp is None else out_opp['policy'], env.legal(), mover, self.seed,
+                self.temperature, self.opponent_temperature, self.opening_plies, run['G'], run['forced'], run['trace'])
         # a net's state moves where it played, or (observation) wherever a game is running
         for h, o, mine in ((hidden, out, True), (hidden_opp, out_opp, False)):
             if h is None:
@@ -543,34 +568,12 @@ class DeviceEvaluator:
         finish = finish_hip if fused else finish_torch
         finish(st, env.terminal(), env.outcome(), run['G'], run['outcome'], run['length'])
 
-    def _capture(self, st, run):
-        """One graph per mover; warm-up plies run first on a side stream (library workspaces).  ``_begin`` then
-        starts the call afresh, so warm-up and capture leave no trace."""
-        dev = torch.device(self.env.device)
-        P = st['P']
-        self._begin(st, run)
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            for m in range(P):
-                self._ply(st, run, m)
-        torch.cuda.current_stream(dev).wait_stream(side)
-        graphs, pool = {}, None
-        for m in range(P):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pool):
-                self._ply(st, run, m)
-            pool = g.pool()
-            graphs[m] = g
-        return graphs
-
     def _prepare(self, st, G, forced, trace):
         """The buffers that depend on G (a captured ply addresses them) and the graphs, kept for the next call with
         the same G, forced / trace choice and parameter addresses."""
         dev = self.env.device
-        nets = [self.net] + ([] if self.opponent is None else [self.opponent])
         key = (G, forced is not None, bool(trace), FUSED_EVAL, self._use_graph(), self.opponent is not None,
-               self.opening_plies) + tuple(t.data_ptr() for n in nets for t in list(n.parameters()) + list(n.buffers()))
+               self.opening_plies) + params_key(*self._nets())
         if self._run is None or self._run['key'] != key:
             Tm, P, A = st['Tm'], st['P'], self.env.A
             run = {'key': key, 'G': G, 'graphs': None, 'forced': None, 'trace': None,
@@ -605,37 +608,21 @@ class DeviceEvaluator:
         if G < 0:
             raise ValueError('games must be >= 0')
         st = self._state()
-        nets = [self.net] + ([] if self.opponent is None else [self.opponent])
-        was_training = [n.training for n in nets]
-        try:
-            with contextlib.ExitStack() as stack:
-                for n in nets:
-                    n.eval()
-                    if hasattr(n, 'inference_session'):
-                        stack.enter_context(n.inference_session())
-                run = self._prepare(st, G, forced, trace)
-                plies = self._play(st, run)
-        finally:
-            for n, mode in zip(nets, was_training):
-                n.train(mode)
+        nets = self._nets()
+        with self._sessions(nets, [False] * len(nets)):
+            run = self._prepare(st, G, forced, trace)
+            plies = self._play(st, run, self.env.E, G, 'evaluation did not finish %d games in %d steps')
         dev = self.env.device
         P = st['P']
         outcome, length = run['outcome'][:G].clone(), run['length'][:G].clone()
         seat = torch.arange(G, device=dev) % P
         mine = outcome[torch.arange(G, device=dev), seat].tolist() if G else []
-        results = {}
-        for o in mine:
-            o = o + 0.0   # a draw's -0.0 counts as 0.0
-            results[o] = results.get(o, 0) + 1
-        results = {k: results[k] for k in sorted(results, reverse=True)}
+        results = _tally(mine)
         res = {'outcome': outcome, 'length': length, 'seat': seat, 'results': results, 'win_rate': wp_func(results),
                'games': G, 'plies': plies, 'env_steps': int(length.sum())}
         if self.opponent is not None:
             others = outcome[(torch.arange(P, device=dev) != seat.view(-1, 1))].tolist() if G else []
-            table = {}
-            for o in others:
-                table[o + 0.0] = table.get(o + 0.0, 0) + 1
-            res['opponent_results'] = {k: table[k] for k in sorted(table, reverse=True)}
+            res['opponent_results'] = _tally(others)
             res['opponent_win_rate'] = wp_func(res['opponent_results'])
         if run['trace'] is not None:
             res['trace'] = {k: v[:G].clone() for k, v in run['trace'].items()}
@@ -646,26 +633,6 @@ class DeviceEvaluator:
         """Copy weights and buffers into the opponent IN PLACE (no tensor is replaced), so the captured graphs, which
         address them, stay valid."""
         self.opponent.load_state_dict(state_dict)
-
-    def _play(self, st, run):
-        G, P = run['G'], st['P']
-        if G == 0:
-            return 0
-        self._begin(st, run)
-        graphs = run['graphs']
-        s = 0
-        limit = (-(-G // max(1, min(self.env.E, G))) + 1) * (st['Tm'] + P) + self.check_every
-        while True:
-            for _ in range(self.check_every):
-                if graphs is not None:
-                    graphs[s % P].replay()
-                else:
-                    self._ply(st, run, s % P)
-                s += 1
-            if int(st['state'][0]) >= G:
-                return s
-            if s > limit:
-                raise RuntimeError('evaluation did not finish %d games in %d steps' % (G, s))
 
 
 def _connected(K, pairs):
@@ -717,7 +684,7 @@ def bradley_terry(score, games):
     return elo - elo.mean()
 
 
-class LeagueEvaluator:
+class LeagueEvaluator(_PlyEvaluator):
     """A round robin of K nets on the E slots of ``env_batch`` (an alternating env with two players): every pairing
     (i, j) plays ``games`` games, and game g of the pairing is the game g that
     ``DeviceEvaluator(env, nets[i], opponent=nets[j], observation=, temperature=, opening_plies=, seed=)`` plays.
@@ -738,7 +705,7 @@ class LeagueEvaluator:
 
     def __init__(self, env_batch, nets, pairings=None, observation=False, temperature=0.0, opening_plies=0, seed=0,
                  check_every=16, graph=None):
-        _check_env(type(env_batch))
+        super().__init__(env_batch, observation, temperature, opening_plies, seed, check_every, graph)
         if env_batch.P != 2:
             raise ValueError('a league seats two nets per game: %s has %d players'
                              % (type(env_batch).__name__, env_batch.P))
@@ -748,10 +715,6 @@ class LeagueEvaluator:
             raise ValueError('a league needs at least two nets, not %d' % K)
         if len({id(n) for n in nets}) != K:
             raise ValueError('every agent must be a module of its own (a copy of a net plays against it)')
-        if not temperature >= 0:
-            raise ValueError('temperature must be >= 0, not %r' % (temperature,))
-        if int(opening_plies) < 0:
-            raise ValueError('opening_plies must be >= 0, not %r' % (opening_plies,))
         if pairings is None:
             pairings = [(i, j) for i in range(K) for j in range(i + 1, K)]
         pairings = [(int(i), int(j)) for i, j in pairings]
@@ -767,19 +730,8 @@ class LeagueEvaluator:
         if env_batch.E <= 0 or env_batch.E % (2 * Q) != 0:
             raise ValueError('env_batch.E must be a positive multiple of 2Q = %d (Q = %d pairings, an even number of '
                              'slots each), not %d' % (2 * Q, Q, env_batch.E))
-        self.env, self.nets, self.pairings = env_batch, nets, pairings
+        self.nets, self.pairings = nets, pairings
         self.K, self.Q, self.S = K, Q, env_batch.E // Q
-        self.observation, self.temperature = bool(observation), float(temperature)
-        self.opening_plies = int(opening_plies)
-        self.seed = int(seed) & 0xffffffffffffffff
-        self.check_every = max(1, int(check_every or 1))
-        self.graph = graph
-        self._st = None
-        self._run = None
-
-    def _use_graph(self):
-        dev = torch.device(self.env.device)
-        return dev.type == 'cuda' and (self.graph is None or bool(self.graph))
 
     def _layout(self):
         """The fixed routes.  rows[k][s]: the slots where agent k sits on seat s, ascending.  Net-major order is agent
@@ -945,30 +897,9 @@ class LeagueEvaluator:
         finish = league_finish_hip if fused else league_finish_torch
         finish(st, env.terminal(), env.outcome(), run['G'], run['outcome'], run['length'])
 
-    def _capture(self, st, run):
-        """One graph per mover, the K forwards one after another on the capturing stream (no parallel branches);
-        warm-up plies run first on a side stream.  ``_begin`` then starts the call afresh."""
-        dev = torch.device(self.env.device)
-        self._begin(st, run)
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            for m in range(2):
-                self._ply(st, run, m)
-        torch.cuda.current_stream(dev).wait_stream(side)
-        graphs, pool = {}, None
-        for m in range(2):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pool):
-                self._ply(st, run, m)
-            pool = g.pool()
-            graphs[m] = g
-        return graphs
-
     def _prepare(self, st, G):
         dev = self.env.device
-        key = (G, FUSED_LEAGUE, self._use_graph()) + tuple(
-            t.data_ptr() for n in self.nets for t in list(n.parameters()) + list(n.buffers()))
+        key = (G, FUSED_LEAGUE, self._use_graph()) + params_key(*self.nets)
         if self._run is None or self._run['key'] != key:
             rows = self.Q * G + 1
             run = {'key': key, 'G': G, 'graphs': None, 'outcome': torch.zeros(rows, 2, device=dev),
@@ -977,26 +908,6 @@ class LeagueEvaluator:
             if self._use_graph() and G > 0:
                 run['graphs'] = self._capture(st, run)
         return self._run
-
-    def _play(self, st, run):
-        G = run['G']
-        if G == 0:
-            return 0
-        self._begin(st, run)
-        graphs = run['graphs']
-        s = 0
-        limit = (-(-G // min(self.S, G)) + 1) * (st['Tm'] + 2) + self.check_every
-        while True:
-            for _ in range(self.check_every):
-                if graphs is not None:
-                    graphs[s % 2].replay()
-                else:
-                    self._ply(st, run, s % 2)
-                s += 1
-            if int(st['state'][0]) >= self.Q * G:
-                return s
-            if s > limit:
-                raise RuntimeError('the league did not finish %d games in %d steps' % (self.Q * G, s))
 
     @torch.no_grad()
     def evaluate(self, games):
@@ -1009,19 +920,9 @@ class LeagueEvaluator:
         if G < 0:
             raise ValueError('games must be >= 0')
         st = self._state()
-        was_training = [n.training for n in self.nets]
-        try:
-            with contextlib.ExitStack() as stack:
-                for n, inplace in zip(self.nets, st['inplace']):
-                    n.eval()
-                    if hasattr(n, 'inference_session'):
-                        stack.enter_context(n.inference_session(inplace_state=True) if inplace
-                                            else n.inference_session())
-                run = self._prepare(st, G)
-                plies = self._play(st, run)
-        finally:
-            for n, mode in zip(self.nets, was_training):
-                n.train(mode)
+        with self._sessions(self.nets, st['inplace']):
+            run = self._prepare(st, G)
+            plies = self._play(st, run, self.S, self.Q * G, 'the league did not finish %d games in %d steps')
         K, Q = self.K, self.Q
         outcome = run['outcome'][:Q * G].view(Q, G, 2).clone()
         length = run['length'][:Q * G].view(Q, G).clone()
@@ -1029,7 +930,7 @@ class LeagueEvaluator:
         home = torch.arange(G) % 2
         score = torch.zeros(K, K, dtype=torch.float64)
         count = torch.zeros(K, K, dtype=torch.long)
-        tables = [{} for _ in range(K)]
+        played = [[] for _ in range(K)]
         for q, (i, j) in enumerate(self.pairings):
             mine = o[q].gather(1, home.view(-1, 1)).view(-1)
             theirs = o[q].gather(1, (1 - home).view(-1, 1)).view(-1)
@@ -1037,10 +938,9 @@ class LeagueEvaluator:
             score[j, i] += ((theirs + 1) / 2).sum()
             count[i, j] += G
             count[j, i] += G
-            for k, values in ((i, mine), (j, theirs)):
-                for v in values.tolist():
-                    tables[k][v + 0.0] = tables[k].get(v + 0.0, 0) + 1
-        win_rate = torch.tensor([wp_func(t) for t in tables], dtype=torch.float64)
+            played[i] += mine.tolist()
+            played[j] += theirs.tolist()
+        win_rate = torch.tensor([wp_func(_tally(o)) for o in played], dtype=torch.float64)
         rating = bradley_terry(score, count) if G > 0 else torch.zeros(K, dtype=torch.float64)
         return {'pairings': list(self.pairings), 'outcome': outcome, 'length': length, 'score': score, 'games': count,
                 'win_rate': win_rate, 'rating': rating, 'plies': plies, 'env_steps': int(length.sum())}
@@ -1198,15 +1098,11 @@ def eval_match_main(args, argv, device=None, log=print):
     outcome, seat = res['outcome'].tolist(), res['seat'].tolist()
     for agent in (0, 1):
         log('---agent %d---' % agent)
-        total = {}
+        total = []
         for tag, first in (('default-F', 0), ('default-S', 1)):     # agent 0 moves first / second
-            table = {}
-            for g in range(games):
-                if seat[g] == first:
-                    o = outcome[g][seat[g] if agent == 0 else 1 - seat[g]] + 0.0
-                    table[o] = table.get(o, 0) + 1
-                    total[o] = total.get(o, 0) + 1
-            if table:
-                log('%s %s %s' % (tag, {k: table[k] for k in sorted(table, reverse=True)}, wp_func(table)))
-        log('total %s %s' % ({k: total[k] for k in sorted(total, reverse=True)}, wp_func(total)))
+            mine = [outcome[g][seat[g] if agent == 0 else 1 - seat[g]] for g in range(games) if seat[g] == first]
+            total += mine
+            if mine:
+                log('%s %s %s' % (tag, _tally(mine), wp_func(_tally(mine))))
+        log('total %s %s' % (_tally(total), wp_func(_tally(total))))
     return res

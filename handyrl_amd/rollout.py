@@ -37,6 +37,7 @@ players sampled, per-player records with the turn and observation masks;
 
 import contextlib
 import ctypes
+import functools
 
 import numpy as np
 import torch
@@ -260,6 +261,54 @@ def sample_record_hip(st, logits, legal, value, active, player, reward):
     return a
 
 
+def params_key(*nets):
+    """The addresses of the nets' parameters and buffers.  A captured ply reads them where they live: the generators
+    and evaluators recapture when this key changes (an in-place ``load_state_dict`` keeps it)."""
+    return tuple(t.data_ptr() for n in nets for t in list(n.parameters()) + list(n.buffers()))
+
+
+@contextlib.contextmanager
+def eval_mode(*nets):
+    """The nets in eval mode; their training modes are put back on the way out, also when the body raises."""
+    was_training = [n.training for n in nets]
+    try:
+        for n in nets:
+            n.eval()
+        yield
+    finally:
+        for n, mode in zip(nets, was_training):
+            n.train(mode)
+
+
+def graph_wanted(device, graph):
+    """``graph=None`` (default) or true on a CUDA device: the ply is replayed from captured graphs."""
+    return torch.device(device).type == 'cuda' and (graph is None or bool(graph))
+
+
+def capture_graphs(device, bodies, warm=None):
+    """{key: CUDAGraph} of the ordered {key: callable} ``bodies``, captured in that order out of one shared pool.
+    ``warm`` (default: every body once) runs first on a side stream, so that library workspaces exist before the
+    capture.  What warm-up and capture did to the caller's buffers is the caller's to put back."""
+    dev = torch.device(device)
+    side = torch.cuda.Stream(dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        if warm is not None:
+            warm()
+        else:
+            for body in bodies.values():
+                body()
+    torch.cuda.current_stream(dev).wait_stream(side)
+    graphs, pool = {}, None
+    for key, body in bodies.items():
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, pool=pool):
+            body()
+        pool = g.pool()
+        graphs[key] = g
+    return graphs
+
+
 class DeviceGenerator:
     """Batched self-play of E games with one env-network forward per ply (generation.py:20-88).
 
@@ -331,7 +380,7 @@ class DeviceGenerator:
     def _state(self):
         """The call's buffers, allocated once per (generator, net)."""
         # a captured ply reads the net's parameters and buffers where they live: recapture if any moved
-        key = tuple(t.data_ptr() for t in list(self.net.parameters()) + list(self.net.buffers()))
+        key = params_key(self.net)
         if self._st is not None and self._st['net'] is self.net and self._st['key'] == key:
             return self._st
         env, E, dev = self.env, self.env.E, self.env.device
@@ -554,25 +603,9 @@ class DeviceGenerator:
     def _capture(self, st, keys):
         """Graphs of the ply (one per mover key) and of the return loop; warm-up plies run first on a side
         stream (library workspaces), then the state is reset."""
-        dev = torch.device(self.env.device)
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            for k in keys:
-                self._ply(st, k)
-            self._returns(st)
-        torch.cuda.current_stream(dev).wait_stream(side)
-        graphs, pool = {}, None
-        for k in list(keys) + ['returns']:
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pool):
-                if k == 'returns':
-                    self._returns(st)
-                else:
-                    self._ply(st, k)
-            pool = g.pool()
-            graphs[k] = g
-        st['graphs'] = graphs
+        bodies = {k: functools.partial(self._ply, st, k) for k in keys}
+        bodies['returns'] = functools.partial(self._returns, st)
+        st['graphs'] = capture_graphs(self.env.device, bodies)
         self._reset(st, None, draw=False)   # the call's uniforms stay as drawn
 
     @torch.no_grad()
@@ -582,21 +615,17 @@ class DeviceGenerator:
         st = self._state()
         if reference is not None and not self.per_player:
             raise ValueError('the reference sampler is the per-player ply\'s (observation or simultaneous envs)')
-        was_training = self.net.training
-        self.net.eval()
         # per-call weight preparation (GeisterNet); its own stacked state is advanced in place by the net (the
         # per-player ply too when every player infers; otherwise it runs the net's ordinary forward).  A wrapper
         # without state (nn.BoardInference) is entered in every mode
         session = (getattr(self.net, 'inference_session', None)
                    if (not self.per_player or st.get('flat_state') or getattr(self.net, 'stateless_session', False))
                    else None)
-        with session(inplace_state=st['pmajor']) if session is not None else contextlib.nullcontext():
+        with eval_mode(self.net), \
+                session(inplace_state=st['pmajor']) if session is not None else contextlib.nullcontext():
             if self.fused_game and st['obs_dev'] == 'cuda':
-                out = self._generate_fused(st, generator)
-            else:
-                out = self._generate(st, generator, alternating, reference)
-        self.net.train(was_training)
-        return out
+                return self._generate_fused(st, generator)
+            return self._generate(st, generator, alternating, reference)
 
     def _generate_fused(self, st, generator):
         """``_generate`` with the ply loop as one launch (``fused_game``), inside the net's inference session.  The
@@ -947,8 +976,7 @@ class StreamGenerator:
         self.ring_game = torch.full((replay.N,), -1, dtype=torch.long, device=env_batch.device)
 
     def _use_graph(self):
-        dev = torch.device(self.env.device)
-        return dev.type == 'cuda' and (self.graph is None or bool(self.graph))
+        return graph_wanted(self.env.device, self.graph)
 
     def _state(self):
         """The slots' buffers, allocated once: the games live in them across calls."""
@@ -1044,22 +1072,13 @@ class StreamGenerator:
         """One graph per mover.  Warm-up plies run first on a side stream (library workspaces) and harvest
         nothing; the games, the ring state and the recurrent state are then put back, so that warm-up and capture
         leave no trace (a slot record the warm-up wrote is written again by the ply that owns it)."""
-        dev = torch.device(self.env.device)
         P = self.env.P
         keep = [t.clone() for t in self._persistent(st)]
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
+
+        def warm():
             for m in range(P):
                 self._ply(st, m, dry=True)
-        torch.cuda.current_stream(dev).wait_stream(side)
-        graphs, pool = {}, None
-        for m in range(P):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pool):
-                self._ply(st, m)
-            pool = g.pool()
-            graphs[m] = g
+        graphs = capture_graphs(self.env.device, {m: functools.partial(self._ply, st, m) for m in range(P)}, warm)
         for t, k in zip(self._persistent(st), keep):
             t.copy_(k)
         return graphs
@@ -1070,13 +1089,10 @@ class StreamGenerator:
         ``check_every`` steps, so a call may overshoot).  Returns {'episodes': emitted by this call, 'env_steps':
         the sum of their lengths, 'plies': global steps run}."""
         st = self._state()
-        was_training = self.net.training
-        self.net.eval()
         session = getattr(self.net, 'inference_session', None)
-        with session(inplace_state=st['pmajor']) if session is not None else contextlib.nullcontext():
-            out = self._generate(st, int(episodes))
-        self.net.train(was_training)
-        return out
+        with eval_mode(self.net), \
+                session(inplace_state=st['pmajor']) if session is not None else contextlib.nullcontext():
+            return self._generate(st, int(episodes))
 
     def _generate(self, st, episodes):
         P, N = self.env.P, self.replay.N
@@ -1084,7 +1100,7 @@ class StreamGenerator:
         if self._use_graph():
             # a captured ply reads the net's parameters and buffers where they live: recapture if any moved (the
             # games stay); the switch between the kernels and their torch formulation is part of the capture too
-            key = (FUSED_STREAM,) + tuple(t.data_ptr() for t in list(self.net.parameters()) + list(self.net.buffers()))
+            key = (FUSED_STREAM,) + params_key(self.net)
             if self._graphs is None or self._graphs[0] != key:
                 self._graphs = (key, self._capture(st))
             graphs = self._graphs[1]

@@ -199,7 +199,9 @@ int hrl_masked_rows_copy(int nleaves, float *const *dst, const int64_t *dst_stri
  * to restart; also one whose ply[e] is outside [0, Tm) or game[e] outside [0, G)) gets action[e] = 0 and NO other
  * store.  An active slot plays the model's move where seat[e] == mover and the random agent's elsewhere.
  * logits (E, >= A) rows of stride logit_stride, legal (E, A) bytes, game / ply / seat (E,) int64, active (E,) bytes;
- * action (E,) int64 is written for every slot and nothing else outside the trace. */
+ * action (E,) int64 is written for every slot and nothing else outside the trace.
+ * There is one decision kernel: this entry is hrl_match_act (below) with logits_opp = NULL, stride_opp = 0,
+ * temperature_opp = 0 and opening = 0, and its argument checks are that entry's. */
 int hrl_eval_act(const float *logits, int64_t logit_stride, const uint8_t *legal, uint64_t seed, double temperature,
                  const int64_t *game, const int64_t *ply, const uint8_t *active, const int64_t *seat, int64_t mover,
                  const int64_t *forced, int64_t E, int64_t A, int64_t Tm, int64_t P, int64_t G, int64_t *action,
@@ -221,7 +223,7 @@ int hrl_eval_act(const float *logits, int64_t logit_stride, const uint8_t *legal
  *   Which rows the evaluator feeds: the home net sees the board from `seat`; the opponent sees it from the mover's seat
  *     where the mover is not home and from seat (seat + 1) mod P otherwise (for P == 2: always the other seat).
  * An inactive, retired or out-of-range slot gets action[e] = 0 and no other store.  With logits_opp == NULL and
- * opening == 0 every output equals hrl_eval_act's bit for bit.  HRL_EINVAL as for hrl_eval_act, and for
+ * opening == 0 this is hrl_eval_act (the same launch).  HRL_EINVAL as for hrl_eval_act, and for
  * stride_home < A, stride_opp < A when logits_opp is given, either temperature < 0 or NaN, opening < 0. */
 int hrl_match_act(const float *logits_home, int64_t stride_home, const float *logits_opp, int64_t stride_opp,
                   const uint8_t *legal, uint64_t seed, double temperature_home, double temperature_opp,

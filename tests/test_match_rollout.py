@@ -275,13 +275,22 @@ def _by_hand(cls, net, E, G, observation):
 @pytest.mark.parametrize('recurrent,observation', [(False, False), (True, False), (True, True)])
 def test_default_arguments_play_the_random_agents_as_before(dev, monkeypatch, recurrent, observation):
     """No opponent, no opening plies: the games are those of act_torch / finish_torch driven by hand, the result has
-    no new key and the match decision is never called."""
-    def never(*a, **k):
-        raise AssertionError('the match decision ran without an opponent or opening plies')
-    monkeypatch.setattr(evaluation, 'match_act_torch', never)
-    monkeypatch.setattr(evaluation, 'match_act_hip', never)
+    no new key and the one decision (match_act_*) only ever runs in its no-opponent form: no second net's logits, no
+    opening plies."""
+    calls = []
+
+    def no_opponent(decide):
+        def spy(st, logits_home, logits_opp, legal, mover, seed, temperature_home, temperature_opp, opening, *a, **k):
+            assert logits_opp is None and opening == 0, 'the decision saw an opponent or opening plies'
+            calls.append(decide.__name__)
+            return decide(st, logits_home, logits_opp, legal, mover, seed, temperature_home, temperature_opp, opening,
+                          *a, **k)
+        return spy
+    monkeypatch.setattr(evaluation, 'match_act_torch', no_opponent(evaluation.match_act_torch))
+    monkeypatch.setattr(evaluation, 'match_act_hip', no_opponent(evaluation.match_act_hip))
     net = IntNet(TicTacToeBatch, recurrent).to(dev)
     res = DeviceEvaluator(TicTacToeBatch(7, dev), net, observation=observation, seed=SEED).evaluate(48, trace=True)
+    assert calls
     assert sorted(res) == ['env_steps', 'games', 'length', 'outcome', 'plies', 'results', 'seat', 'trace', 'win_rate']
     want = _by_hand(TicTacToeBatch, IntNet(TicTacToeBatch, recurrent), 7, 48, observation)
     assert torch.equal(res['outcome'].cpu(), want['outcome']) and torch.equal(res['length'].cpu(), want['length'])
