@@ -29,7 +29,58 @@ def declared_symbols():
 def test_header_symbols_bound():
     syms = declared_symbols()
     assert 'hrl_compute_target' in syms and 'hrl_compute_targets_fused' in syms
-    assert syms == set(_native.SIGNATURES), 'ctypes signatures out of sync with include/*.h'
+    # the binding is derived from the headers by a strict parser: it missed nothing this loose reading sees
+    assert syms == set(_native.SIGNATURES), 'derived ctypes signatures out of sync with include/*.h'
+    assert len(_native.SIGNATURES) >= 130
+
+
+def test_derived_signatures_match_a_reading_by_hand():
+    """A sample of include/*.h read by hand (not a second table): every scalar type and both return kinds in use."""
+    I, I64, U64, D, P = ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_double, ctypes.c_void_p
+    pinned = {
+        'hrl_compute_target': (I, [I, P, P, P, P, P, I64, I64, I64, I64, I64, I64, D, D, P, P, P]),
+        'hrl_match_act': (I, [P, I64, P, I64, P, U64, D, D, I64, P, P, P, P, I64, P, I64, I64, I64, I64, I64,
+                              P, P, P, P, P, P]),
+        'hrl_bn_workspace_bytes': (I64, [I64, I64, I64]),
+        'hrl_strerror': (ctypes.c_char_p, [I]),
+        'hrl_abi_version': (I, []),
+        'hrl_replay_gather': (I, [I, P, P, P, P, I64, I64, P, P]),
+    }
+    for name, (res, args) in pinned.items():
+        assert _native.SIGNATURES[name] == (res, args), name
+
+
+def test_derived_struct_layouts_match_a_reading_by_hand():
+    """sizeof and offsets of the three descriptor structs, laid out by hand from the headers for the LP64 target
+    (offsetof / sizeof in a C program that includes the headers give the same numbers)."""
+    offsets = lambda cls, names: {n: getattr(cls, n).offset for n in names}   # noqa: E731
+    ring, batch, slots = _native.ReplayRing, _native.ReplayBatch, _native.SelfplaySlots
+    assert (ctypes.sizeof(ring), ctypes.sizeof(batch), ctypes.sizeof(slots)) == (288, 152, 216)
+    assert offsets(ring, ('nleaves', 'obs_type', 'obs_width', 'obs', 'policy', 'omask')) == {
+        'nleaves': 32, 'obs_type': 36, 'obs_width': 72, 'obs': 136, 'policy': 200, 'omask': 280}
+    assert offsets(batch, ('obs', 'policy', 'progress')) == {'obs': 0, 'policy': 64, 'progress': 144}
+    assert offsets(slots, ('nleaves', 'obs_width', 'obs', 'policy', 'reward')) == {
+        'nleaves': 32, 'obs_width': 40, 'obs': 104, 'policy': 168, 'reward': 208}
+    assert [n for n, _ in ring._fields_] == [
+        'N', 'Tm', 'P', 'A', 'nleaves', 'obs_type', 'obs_width', 'obs', 'policy', 'amask', 'action', 'value',
+        'reward', 'ret', 'length', 'outcome', 'turn', 'tmask', 'omask']
+    assert ring._fields_[-1][0] == 'omask' and batch._fields_[-1][0] == 'progress'
+    assert slots._fields_[-1][0] == 'reward'
+    assert all(t is ctypes.c_void_p for _, t in batch._fields_[1:])
+
+
+def test_derived_constants():
+    assert _native.HRL_OK == 0 and _native.HRL_EINVAL == -22
+    assert _native.REPLAY_MAX_LEAVES == 8 and (_native.REPLAY_U8, _native.REPLAY_F32) == (0, 1)
+    assert _native.ALG == {'MC': 0, 'TD': 1, 'UPGO': 2, 'VTRACE': 3}
+    assert _native.REPLAY_LAYOUT == {'mover_records': 0, 'players_all': 1, 'players_solo': 2, 'players_mover': 3}
+    assert _native.ABI_VERSION == 30
+
+
+def test_missing_headers_fail_loudly(monkeypatch, tmp_path):
+    monkeypatch.setattr(_native, 'INCLUDE_DIR', str(tmp_path / 'include'))
+    with pytest.raises(RuntimeError, match=str(tmp_path / 'include')):
+        _native._headers()
 
 
 def test_library_exports_every_declared_symbol():
@@ -38,7 +89,8 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, s), s
     out = subprocess.run(['nm', '-D', '--defined-only', _native.LIB_PATH], capture_output=True, text=True).stdout
     exported = set(re.findall(r' T (hrl_[a-z0-9_]+)', out))
-    assert declared_symbols() <= exported
+    # equality: an exported function with no prototype would have no binding
+    assert declared_symbols() == exported
 
 
 def test_abi_version_and_errors():

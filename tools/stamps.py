@@ -54,14 +54,9 @@ def main():
     import numpy as np
     import torch
     dev = torch.device('cuda', 0)
-    lib = ctypes.CDLL(LIB)
-    vp, i64, dbl = ctypes.c_void_p, ctypes.c_int64, ctypes.c_double
-    lib.hrl_compute_targets_fused.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, i64, i64, i64, i64,
-                                              i64, i64, dbl, dbl, vp, vp, vp]
-    lib.hrl_loss_workspace_bytes.restype = i64
-    lib.hrl_loss_workspace_bytes.argtypes = [i64, i64, i64, i64]
-    lib.hrl_loss_forward.argtypes = [vp, vp, vp, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                     ctypes.c_int, ctypes.c_int, ctypes.c_int, dbl, dbl, dbl, dbl, vp, i64, vp, vp]
+    sys.path.insert(0, ROOT)
+    from handyrl_amd import _native
+    lib = _native.bind(ctypes.CDLL(LIB))   # the header prototypes; the hrl_debug_set_stamps_* extras take one pointer
     p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
     stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     g = torch.Generator(device=dev).manual_seed(0)
@@ -119,13 +114,6 @@ def main():
                    'wave fold + partial store'])
 
     def run_block(M=131072):
-        lib.hrl_conv3x3_workspace_bytes.restype = i64
-        lib.hrl_conv3x3_workspace_bytes.argtypes = [i64]
-        lib.hrl_conv3x3_stats_blocks.restype = i64
-        lib.hrl_conv3x3_stats_blocks.argtypes = [i64]
-        lib.hrl_conv3x3_pack_n.argtypes = [vp, ctypes.c_int, vp, vp]
-        lib.hrl_conv3x3_block_backward.argtypes = [vp, vp, i64] + [vp] * 12 + [ctypes.c_int, vp, vp, vp, vp, vp,
-                                                                            i64, vp]
         r = lambda *sh: torch.randn(*sh, device=dev, generator=g)   # noqa: E731
         gg, y, x = r(M, 288), r(M, 288), r(M, 288)
         w = r(32, 32, 3, 3) * 0.1
