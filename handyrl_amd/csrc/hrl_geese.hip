@@ -1,0 +1,305 @@
+// hrl_geese.hip — batched Hungry Geese for device self-play (include/hrl_geese.h has the state layout and the
+// pick rule; handyrl_amd/envs/geese.py:step_game is the specification these kernels are tested against).
+//
+//   reset    lane per game: six picks of Philox words (heads, food), reset values, the body ring zeroed
+//   step     lane per game: the whole step.  A goose's cells are a 77-bit occupancy mask (two 64-bit words) built
+//            from its ring; the moves run in goose order on those masks, collisions are mask tests, the food
+//            respawn takes the r-th zero bit of the occupancy.  The ring is written once, after the collisions:
+//            a surviving goose's head index steps back by one and the new head is stored there; a dead goose
+//            only gets len = 0 (its ring bytes stay).  A few hundred bytes per game: launch latency is the cost.
+//   observe  block of four waves per game, wave p = view p.  Lanes 0-3 of each wave build the four geese's masks,
+//            17 plane masks go to LDS, then the wave streams the 1309 floats of the view into the forward's input
+//            row and, where infer is set, into the episode record.  1309 is 1 mod 4, so a row starts at any of the
+//            four 4-byte phases of a 16-byte line: scalar stores up to the first aligned float, float4 stores, then
+//            the scalar tail.  This kernel moves the bytes (2 x 21 KB per game and ply).
+// Every value is written with ordinary vector stores in plain C++.
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "hrl_pick.h"
+
+extern "C" {
+#include "../../include/hrl_geese.h"
+}
+#include "../../include/hrl_targets.h"
+
+namespace {
+
+constexpr int kGeese = 4, kRing = 80, kRows = 7, kCols = 11, kCells = kRows * kCols, kPlanes = 17;
+constexpr int kView = kPlanes * kCells;   // 1309 floats
+constexpr int kLastStep = 199, kHunger = 40;
+
+struct Mask {
+    uint64_t lo, hi;   // cells 0-63, 64-76
+    __device__ __forceinline__ bool has(int c) const { return ((c < 64 ? lo >> c : hi >> (c - 64)) & 1) != 0; }
+    __device__ __forceinline__ void set(int c) { if (c < 64) lo |= 1ull << c; else hi |= 1ull << (c - 64); }
+    __device__ __forceinline__ void clear(int c) { if (c < 64) lo &= ~(1ull << c); else hi &= ~(1ull << (c - 64)); }
+    __device__ __forceinline__ int count() const { return __popcll(lo) + __popcll(hi); }
+};
+
+__device__ __forceinline__ int translate(int cell, int a) {
+    int r = cell / kCols, c = cell % kCols;
+    if (a == 0) r = r == 0 ? kRows - 1 : r - 1;
+    else if (a == 1) r = r == kRows - 1 ? 0 : r + 1;
+    else if (a == 2) c = c == 0 ? kCols - 1 : c - 1;
+    else c = c == kCols - 1 ? 0 : c + 1;
+    return r * kCols + c;
+}
+
+// the r-th (from 0) cell that is not in occ, ascending; the caller guarantees r < 77 - occ.count()
+__device__ __forceinline__ int nth_free(const Mask &occ, int r) {
+    uint64_t w = ~occ.lo;
+    int base = 0;
+    const int n = __popcll(w);
+    if (r >= n) {
+        r -= n;
+        w = ~occ.hi & ((1ull << (kCells - 64)) - 1);
+        base = 64;
+    }
+    for (int k = 0; k < r; ++k) w &= w - 1;
+    return base + __ffsll((unsigned long long)w) - 1;
+}
+
+// pick among the free cells with a 32-bit word: r = (x * n) >> 32
+__device__ __forceinline__ int pick_free(Mask &occ, uint32_t x) {
+    const int n = kCells - occ.count();
+    const int cell = nth_free(occ, (int)(((uint64_t)x * (uint64_t)n) >> 32));
+    occ.set(cell);
+    return cell;
+}
+
+__global__ void __launch_bounds__(256)
+reset_kernel(uint8_t *body, uint8_t *hd, uint8_t *len, int8_t *food, int8_t *last, int8_t *prev, int32_t *reward,
+             int32_t *step, int64_t *game, uint8_t *live, const uint8_t *mask, const int64_t *rank, int64_t base,
+             uint64_t seed, int64_t E) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E || (mask && !mask[e])) return;
+    const int64_t g = base + (rank ? rank[e] : e);
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    const uint32_t c0 = (uint32_t)(uint64_t)g, c1 = (uint32_t)((uint64_t)g >> 32);
+    for (int k = 0; k < kGeese * kRing; ++k) body[e * kGeese * kRing + k] = 0;   // once per game, any alignment
+    Mask occ{0, 0};
+    for (int i = 0; i < kGeese; ++i) {
+        const int cell = pick_free(occ, philox_word(k0, k1, c0, c1, 0, 0, i));
+        body[(e * kGeese + i) * kRing] = (uint8_t)cell;
+        hd[e * kGeese + i] = 0;
+        len[e * kGeese + i] = 1;
+        last[e * kGeese + i] = -1;
+        prev[e * kGeese + i] = -1;
+        reward[e * kGeese + i] = 0;
+    }
+    for (int j = 0; j < 2; ++j) food[e * 2 + j] = (int8_t)pick_free(occ, philox_word(k0, k1, c0, c1, 0, 1, j));
+    step[e] = 0;
+    game[e] = g;
+    live[e] = 1;
+}
+
+__global__ void __launch_bounds__(256)
+step_kernel(uint8_t *body, uint8_t *hd, uint8_t *len, int8_t *food, int8_t *last, int8_t *prev, int32_t *reward,
+            int32_t *step, const int64_t *game, uint8_t *live, const int64_t *actions, const uint8_t *active,
+            uint64_t seed, int64_t E) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E || !active[e]) return;
+    const int s = step[e] + 1;
+    int f0 = food[e * 2], f1 = food[e * 2 + 1];
+    Mask m[kGeese];
+    int head[kGeese], nlen[kGeese], act[kGeese];
+    bool was[kGeese], ok[kGeese];
+    // 1. the moves, in goose order (a lower goose eats a shared food cell first)
+    for (int i = 0; i < kGeese; ++i) {
+        const int64_t gi = e * kGeese + i;
+        const uint8_t *ring = body + gi * kRing;
+        const int h0 = hd[gi], L0 = len[gi];
+        m[i] = Mask{0, 0};
+        head[i] = -1;
+        nlen[i] = 0;
+        act[i] = (int)(actions[gi] & 3);
+        was[i] = L0 > 0;
+        ok[i] = false;
+        if (!was[i]) {
+            prev[gi] = -1;
+            continue;
+        }
+        const int old_head = ring[h0];
+        prev[gi] = (int8_t)old_head;
+        const int la = last[gi];
+        last[gi] = (int8_t)act[i];
+        if (s > 1 && la >= 0 && act[i] == (la ^ 1)) continue;              // reversal
+        Mask mk{0, 0};
+        for (int k = 0; k < L0; ++k) mk.set(ring[(h0 + k) % kRing]);
+        const int h = translate(old_head, act[i]);
+        int L = L0;
+        if (h == f0) f0 = -1;                                              // grows
+        else if (h == f1) f1 = -1;
+        else {
+            mk.clear(ring[(h0 + L - 1) % kRing]);
+            --L;
+        }
+        if (mk.has(h)) continue;                                           // into its own body
+        mk.set(h);
+        ++L;                                                               // cells: h, then ring cells 0 .. L - 2
+        if (s % kHunger == 0) {
+            if (L == 1) continue;                                          // starved
+            mk.clear(ring[(h0 + L - 2) % kRing]);
+            --L;
+        }
+        m[i] = mk;
+        head[i] = h;
+        nlen[i] = L;
+        ok[i] = true;
+    }
+    // 2. a head on a cell that any other goose holds dies (every list is free of repeats by itself)
+    bool dies[kGeese];
+    for (int i = 0; i < kGeese; ++i) {
+        dies[i] = false;
+        if (!ok[i]) continue;
+        for (int j = 0; j < kGeese; ++j)
+            if (j != i && ok[j] && m[j].has(head[i])) dies[i] = true;
+    }
+    Mask occ{0, 0};
+    int alive = 0;
+    for (int i = 0; i < kGeese; ++i) {
+        const int64_t gi = e * kGeese + i;
+        if (ok[i] && !dies[i]) {
+            const int h1 = (hd[gi] + kRing - 1) % kRing;
+            body[gi * kRing + h1] = (uint8_t)head[i];
+            hd[gi] = (uint8_t)h1;
+            len[gi] = (uint8_t)nlen[i];
+            reward[gi] = s * 100 + nlen[i];                                // 4.
+            occ.lo |= m[i].lo;
+            occ.hi |= m[i].hi;
+            ++alive;
+        } else if (was[i]) {
+            len[gi] = 0;
+        }
+    }
+    // 3. food respawn: the lowest empty slot first, words 0 and 1 of this step
+    if (f0 >= 0) occ.set(f0);
+    if (f1 >= 0) occ.set(f1);
+    if (f0 < 0 || f1 < 0) {
+        const int64_t g = game[e];
+        const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+        const uint32_t c0 = (uint32_t)(uint64_t)g, c1 = (uint32_t)((uint64_t)g >> 32);
+        int j = 0;
+        if (f0 < 0 && occ.count() < kCells) f0 = pick_free(occ, philox_word(k0, k1, c0, c1, (uint32_t)s, 0, j++));
+        if (f1 < 0 && occ.count() < kCells) f1 = pick_free(occ, philox_word(k0, k1, c0, c1, (uint32_t)s, 0, j++));
+    }
+    food[e * 2] = (int8_t)f0;
+    food[e * 2 + 1] = (int8_t)f1;
+    step[e] = s;
+    live[e] = (alive >= 2 && s < kLastStep) ? 1 : 0;
+}
+
+__device__ __forceinline__ float plane_bit(const uint64_t (*pm)[2], int k) {
+    const int plane = k / kCells, cell = k - plane * kCells;
+    return (float)((pm[plane][cell >> 6] >> (cell & 63)) & 1ull);
+}
+
+// the kView floats of one view into dst (any 4-byte phase of a 16-byte line)
+__device__ __forceinline__ void store_view(float *dst, const uint64_t (*pm)[2], int lane) {
+    const int lead = (int)((4 - ((reinterpret_cast<uintptr_t>(dst) >> 2) & 3)) & 3);
+    if (lane < lead) dst[lane] = plane_bit(pm, lane);
+    const int nvec = (kView - lead) >> 2;
+    for (int v = lane; v < nvec; v += kWave) {
+        const int k = lead + 4 * v;
+        float4 x;
+        x.x = plane_bit(pm, k);
+        x.y = plane_bit(pm, k + 1);
+        x.z = plane_bit(pm, k + 2);
+        x.w = plane_bit(pm, k + 3);
+        *reinterpret_cast<float4 *>(dst + k) = x;
+    }
+    const int done = lead + 4 * nvec;
+    if (lane < kView - done) dst[done + lane] = plane_bit(pm, done + lane);
+}
+
+__global__ void __launch_bounds__(256)
+observe_kernel(const uint8_t *body, const uint8_t *hd, const uint8_t *len, const int8_t *food, const int8_t *prev,
+               float *views, float *record, const int64_t *t, const uint8_t *infer, int64_t E, int64_t Tm) {
+    __shared__ uint64_t planes[kGeese][kPlanes][2];
+    const int64_t e = blockIdx.x;                     // grid = E blocks of four waves: no thread is out of range
+    const int p = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+    uint64_t (*pm)[2] = planes[p];
+    if (lane < kGeese) {
+        const int i = lane, q = (i - p + kGeese) % kGeese;
+        const int64_t gi = e * kGeese + i;
+        const uint8_t *ring = body + gi * kRing;
+        const int h0 = hd[gi], L = len[gi];
+        Mask whole{0, 0}, hm{0, 0}, tm{0, 0}, pv{0, 0};
+        for (int k = 0; k < L; ++k) whole.set(ring[(h0 + k) % kRing]);
+        if (L > 0) {
+            hm.set(ring[h0]);
+            tm.set(ring[(h0 + L - 1) % kRing]);
+        }
+        const int ph = prev[gi];
+        if (ph >= 0 && ph < kCells) pv.set(ph);
+        pm[q][0] = hm.lo;         pm[q][1] = hm.hi;
+        pm[4 + q][0] = tm.lo;     pm[4 + q][1] = tm.hi;
+        pm[8 + q][0] = whole.lo;  pm[8 + q][1] = whole.hi;
+        pm[12 + q][0] = pv.lo;    pm[12 + q][1] = pv.hi;
+    } else if (lane == kGeese) {
+        Mask fm{0, 0};
+        for (int j = 0; j < 2; ++j) {
+            const int f = food[e * 2 + j];
+            if (f >= 0 && f < kCells) fm.set(f);
+        }
+        pm[16][0] = fm.lo;
+        pm[16][1] = fm.hi;
+    }
+    __syncthreads();
+    store_view(views + ((int64_t)p * E + e) * kView, pm, lane);
+    if (record && infer[e * kGeese + p]) {
+        const int64_t tt = *t;
+        if (tt >= 0 && tt < Tm) store_view(record + ((e * Tm + tt) * kGeese + p) * kView, pm, lane);
+    }
+}
+
+inline int grid_for(int64_t n) { return (int)((n + 255) / 256); }
+
+inline int launched() {
+    const hipError_t err = hipGetLastError();
+    return err == hipSuccess ? HRL_OK : HRL_ELAUNCH_BASE - (int)err;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hrl_geese_reset(uint8_t *body, uint8_t *hd, uint8_t *len, int8_t *food, int8_t *last, int8_t *prev,
+                    int32_t *reward, int32_t *step, int64_t *game, uint8_t *live, const uint8_t *mask,
+                    const int64_t *rank, int64_t base, uint64_t seed, int64_t E, int64_t P, void *stream) {
+    if (!body || !hd || !len || !food || !last || !prev || !reward || !step || !game || !live || E < 0 ||
+        P != kGeese)
+        return HRL_EINVAL;
+    if (E == 0) return HRL_OK;
+    hipLaunchKernelGGL(reset_kernel, dim3(grid_for(E)), dim3(256), 0, static_cast<hipStream_t>(stream), body, hd, len,
+                       food, last, prev, reward, step, game, live, mask, rank, base, seed, E);
+    return launched();
+}
+
+int hrl_geese_step(uint8_t *body, uint8_t *hd, uint8_t *len, int8_t *food, int8_t *last, int8_t *prev,
+                   int32_t *reward, int32_t *step, const int64_t *game, uint8_t *live, const int64_t *actions,
+                   const uint8_t *active, uint64_t seed, int64_t E, int64_t P, int64_t A, void *stream) {
+    if (!body || !hd || !len || !food || !last || !prev || !reward || !step || !game || !live || !actions ||
+        !active || E < 0 || P != kGeese || A != 4)
+        return HRL_EINVAL;
+    if (E == 0) return HRL_OK;
+    hipLaunchKernelGGL(step_kernel, dim3(grid_for(E)), dim3(256), 0, static_cast<hipStream_t>(stream), body, hd, len,
+                       food, last, prev, reward, step, game, live, actions, active, seed, E);
+    return launched();
+}
+
+int hrl_geese_observe(const uint8_t *body, const uint8_t *hd, const uint8_t *len, const int8_t *food,
+                      const int8_t *prev, float *views, float *record, const int64_t *t, const uint8_t *infer,
+                      int64_t E, int64_t P, int64_t Tm, void *stream) {
+    if (!body || !hd || !len || !food || !prev || !views || E < 0 || E > 0x7fffffff || P != kGeese)
+        return HRL_EINVAL;
+    if (record && (!t || !infer || Tm < 1)) return HRL_EINVAL;
+    if (E == 0) return HRL_OK;
+    hipLaunchKernelGGL(observe_kernel, dim3((unsigned)E), dim3(256), 0, static_cast<hipStream_t>(stream), body, hd,
+                       len, food, prev, views, record, t, infer, E, Tm);
+    return launched();
+}
+
+}  // extern "C"

@@ -20,6 +20,7 @@ ENVS = {   # environment.py:9-15, every key resolved inside this package
     'CIGeister': 'handyrl_amd.envs.ci_geister',
     'ParallelTicTacToe': 'handyrl_amd.envs.parallel_tictactoe',
     'HungryGeese': 'handyrl_amd.envs.hungry_geese',
+    'Geese': 'handyrl_amd.envs.geese',             # Hungry Geese with this package's own rules (envs/geese.py)
 }
 
 

@@ -16,7 +16,7 @@ written) with the actors and the learner on the GPU:
 * ``prepare_env`` / ``make_env`` resolve the env by name or module path
   (environment.py:18-39) and ``env.net()`` gives the model class;
 * generation: an env module with a batched (device) twin (TicTacToe,
-  ParallelTicTacToe, Geister, CIGeister) is played by
+  ParallelTicTacToe, Geister, CIGeister, Geese) is played by
   ``rollout.DeviceGenerator``: in the stock layout of an alternating env
   (turn_based_training, no opponent observation) the mover-only ply into
   ``rollout.DeviceReplay``; with ``observation: True``, solo training or a
@@ -93,8 +93,9 @@ from .trainer import Trainer
 def _batched_envs():
     from .envs.geister import GeisterBatch
     from .envs.ci_geister import CIGeisterBatch
+    from .envs.geese import HungryGeeseBatch
     return {'handyrl_amd.envs.tictactoe': TicTacToeBatch, 'handyrl_amd.envs.geister': GeisterBatch,
-            'handyrl_amd.envs.ci_geister': CIGeisterBatch,
+            'handyrl_amd.envs.ci_geister': CIGeisterBatch, 'handyrl_amd.envs.geese': HungryGeeseBatch,
             'handyrl_amd.envs.parallel_tictactoe': ParallelTicTacToeBatch}
 
 
@@ -244,7 +245,10 @@ def train_main(args, device=None, loss_fn=None, model_dir='models', log=print):
             played[0] = out['episodes']
             return float(out['env_steps'])
     elif use_device:
-        gen = DeviceGenerator(batched(games, device), play_net, gamma=targs['gamma'], observation=observe,
+        env_batch = batched(games, device)
+        if hasattr(env_batch, 'seed'):     # an env with randomness of its own (Geese's food): per rank, like `rng`
+            env_batch.seed(seed)
+        gen = DeviceGenerator(env_batch, play_net, gamma=targs['gamma'], observation=observe,
                               per_player=per_player, fused_game=self_play == 'fused')
         # binary observation planes live in HBM as uint8 (widened by the gather)
         if per_player:
@@ -262,7 +266,16 @@ def train_main(args, device=None, loss_fn=None, model_dir='models', log=print):
             return float(ep['length'].float().sum())
     else:
         slots = min(games, int(targs.get('host_envs', 256)))
-        gen = HostBatchGenerator(lambda: make_env(env_args), play_net, targs, E=slots, seed=seed)
+        made = [0]
+
+        def host_env():
+            # an env that numbers its games per instance under a seed from its args (SEEDED: Geese) gets a seed per
+            # slot and rank unless env_args name one: otherwise every slot would play the same games
+            if 'seed' in env_args or not getattr(type(env), 'SEEDED', False):
+                return make_env(env_args)
+            made[0] += 1
+            return make_env({**env_args, 'seed': (seed << 20) + made[0]})
+        gen = HostBatchGenerator(host_env, play_net, targs, E=slots, seed=seed)
         replay = MomentReplay({**targs, 'maximum_episodes': maximum}, device, maximum_episodes=maximum)
 
         def play():

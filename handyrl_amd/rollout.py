@@ -464,8 +464,13 @@ class DeviceGenerator:
         turns = (env.turns_mask() if hasattr(env, 'turns_mask') else
                  torch.nn.functional.one_hot(env.turn().long(), P).bool()) & live          # (E, P)
         infer = live.expand(E, P) if self.observation else turns
-        views = [env.observation(st['players'][p]) for p in range(P)]
-        o = _stack_views(views)                                                           # (P * E, ...)
+        views = None
+        if hasattr(env, 'observe_players_record'):
+            # the env builds every view and records slot t of the (game, player) pairs of `infer` in one launch
+            o = env.observe_players_record(st['obs'], t, infer)                           # (P * E, ...)
+        else:
+            views = [env.observation(st['players'][p]) for p in range(P)]
+            o = _stack_views(views)                                                       # (P * E, ...)
         h_in = (None if hidden is None else hidden if st['flat_state'] else
                 map_r(hidden, lambda h: h.view(P * E, *h.shape[2:])))
         out = self.net(o, h_in)
@@ -498,8 +503,9 @@ class DeviceGenerator:
         def record(buf, x, mask, fill=0):
             keep = mask.view(*mask.shape, *([1] * (x.dim() - mask.dim())))
             buf.index_copy_(1, t, torch.where(keep, x, fill).to(buf.dtype).unsqueeze(1))
-        views_e = _stack_views(views, batch_first=True)                                   # (E, P, ...)
-        bimap_r(st['obs'], views_e, lambda b, v: record(b, v, infer))
+        if views is not None:
+            views_e = _stack_views(views, batch_first=True)                               # (E, P, ...)
+            bimap_r(st['obs'], views_e, lambda b, v: record(b, v, infer))
         record(st['value'], value, infer)
         record(st['policy'], p, turns)
         record(st['amask'], m, turns, 1e32)
