@@ -17,8 +17,9 @@ With ``workspace_bytes - 1`` every entry point that takes a workspace returns HR
 guard untouched.
 
 Outputs that accumulate by contract would go through ``Arena.acc``: no header sentence of the entry points covered
-here says so (``hrl_gboard_wgrad``'s "ADDED into" is out of scope), so none does.  The running statistics are updated
-in place ("running stats updated in place", hrl_bn_forward_train) and go through ``Arena.inout``.
+here says so, so none does (``hrl_gboard_wgrad``'s "ADDED into" and the rest of csrc/hrl_gboard.hip have a module of
+their own, tests/test_gboard_guard_bands_gpu.py).  The running statistics are updated in place ("running stats updated
+in place", hrl_bn_forward_train) and go through ``Arena.inout``.
 
 Row counts are the smallest at which a tile limit can go wrong (the constants are quoted in each case's docstring):
 1, tile - 1, tile, tile + 1, one row more than one workgroup covers and, where that is at most about 20,000 rows,
