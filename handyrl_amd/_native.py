@@ -54,6 +54,7 @@ REPLAY_LAYOUT = {k: _constants['HRL_REPLAY_' + k.upper()]
 ReplayRing = _structs['hrl_replay_ring']
 ReplayBatch = _structs['hrl_replay_batch']
 SelfplaySlots = _structs['hrl_selfplay_slots']   # include/hrl_env.h
+SelfplayPlayerSlots = _structs['hrl_selfplay_player_slots']
 
 # the version this package expects of the library (hrl_abi_version()); no header states it
 ABI_VERSION = 30

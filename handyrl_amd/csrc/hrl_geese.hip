@@ -12,6 +12,9 @@
 //            row and, where infer is set, into the episode record.  1309 is 1 mod 4, so a row starts at any of the
 //            four 4-byte phases of a 16-byte line: scalar stores up to the first aligned float, float4 stores, then
 //            the scalar tail.  This kernel moves the bytes (2 x 21 KB per game and ply).
+//   observe_at  the same views for the streaming per-player generator: the record is uint8 (a quarter of the bytes),
+//            addressed by a per-game ply, and every player's slot of an active game is written -- zeros where the
+//            player does not infer.  A 1309-byte view starts at any byte phase: bytes, 16-byte stores, bytes.
 // Every value is written with ordinary vector stores in plain C++.
 
 #include <hip/hip_runtime.h>
@@ -214,13 +217,10 @@ __device__ __forceinline__ void store_view(float *dst, const uint64_t (*pm)[2], 
     if (lane < kView - done) dst[done + lane] = plane_bit(pm, done + lane);
 }
 
-__global__ void __launch_bounds__(256)
-observe_kernel(const uint8_t *body, const uint8_t *hd, const uint8_t *len, const int8_t *food, const int8_t *prev,
-               float *views, float *record, const int64_t *t, const uint8_t *infer, int64_t E, int64_t Tm) {
-    __shared__ uint64_t planes[kGeese][kPlanes][2];
-    const int64_t e = blockIdx.x;                     // grid = E blocks of four waves: no thread is out of range
-    const int p = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-    uint64_t (*pm)[2] = planes[p];
+// the 17 plane masks of view p of game e into pm (LDS), by lanes 0-4 of the view's wave
+__device__ __forceinline__ void build_planes(const uint8_t *body, const uint8_t *hd, const uint8_t *len,
+                                             const int8_t *food, const int8_t *prev, int64_t e, int p, int lane,
+                                             uint64_t (*pm)[2]) {
     if (lane < kGeese) {
         const int i = lane, q = (i - p + kGeese) % kGeese;
         const int64_t gi = e * kGeese + i;
@@ -247,12 +247,73 @@ observe_kernel(const uint8_t *body, const uint8_t *hd, const uint8_t *len, const
         pm[16][0] = fm.lo;
         pm[16][1] = fm.hi;
     }
+}
+
+__global__ void __launch_bounds__(256)
+observe_kernel(const uint8_t *body, const uint8_t *hd, const uint8_t *len, const int8_t *food, const int8_t *prev,
+               float *views, float *record, const int64_t *t, const uint8_t *infer, int64_t E, int64_t Tm) {
+    __shared__ uint64_t planes[kGeese][kPlanes][2];
+    const int64_t e = blockIdx.x;                     // grid = E blocks of four waves: no thread is out of range
+    const int p = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+    uint64_t (*pm)[2] = planes[p];
+    build_planes(body, hd, len, food, prev, e, p, lane, pm);
     __syncthreads();
     store_view(views + ((int64_t)p * E + e) * kView, pm, lane);
     if (record && infer[e * kGeese + p]) {
         const int64_t tt = *t;
         if (tt >= 0 && tt < Tm) store_view(record + ((e * Tm + tt) * kGeese + p) * kView, pm, lane);
     }
+}
+
+// sixteen bytes of a view from byte k on (k + 16 <= kView) as four little-endian words; on == 0: zeros
+__device__ __forceinline__ uint4 view_bytes16(const uint64_t (*pm)[2], int k, uint32_t on) {
+    int plane = k / kCells, cell = k - plane * kCells;
+    uint32_t w[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        uint32_t x = 0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            x |= (uint32_t)((pm[plane][cell >> 6] >> (cell & 63)) & 1ull) << (8 * b);
+            if (++cell == kCells && plane < kPlanes - 1) {   // the step after the view's last byte stays in range
+                cell = 0;
+                ++plane;
+            }
+        }
+        w[j] = x & (0u - on);
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// the kView bytes of one view (on == 0: kView zeros) into dst, which starts at any byte of a 16-byte line
+__device__ __forceinline__ void store_view_u8(uint8_t *dst, const uint64_t (*pm)[2], int lane, uint32_t on) {
+    const int lead = (int)((16 - (reinterpret_cast<uintptr_t>(dst) & 15)) & 15);
+    if (lane < lead) dst[lane] = (uint8_t)((uint32_t)plane_bit(pm, lane) & on);
+    const int nvec = (kView - lead) >> 4;
+    for (int v = lane; v < nvec; v += kWave) {
+        const int k = lead + 16 * v;
+        *reinterpret_cast<uint4 *>(dst + k) = view_bytes16(pm, k, on);
+    }
+    const int done = lead + 16 * nvec;
+    if (lane < kView - done) dst[done + lane] = (uint8_t)((uint32_t)plane_bit(pm, done + lane) & on);
+}
+
+// observe_kernel for the streaming per-player generator: a ply index and an active byte per game, a uint8 record
+// whose slot is written for every player of an active game -- the view where infer is set, zeros where it is not.
+__global__ void __launch_bounds__(256)
+observe_at_kernel(const uint8_t *body, const uint8_t *hd, const uint8_t *len, const int8_t *food, const int8_t *prev,
+                  float *views, uint8_t *record, const int64_t *ply, const uint8_t *infer, const uint8_t *active,
+                  int64_t E, int64_t Tm) {
+    __shared__ uint64_t planes[kGeese][kPlanes][2];
+    const int64_t e = blockIdx.x;                     // grid = E blocks of four waves: no thread is out of range
+    const int p = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+    uint64_t (*pm)[2] = planes[p];
+    build_planes(body, hd, len, food, prev, e, p, lane, pm);
+    __syncthreads();
+    store_view(views + ((int64_t)p * E + e) * kView, pm, lane);
+    const int64_t tt = ply[e];
+    if (!active[e] || tt < 0 || tt >= Tm) return;    // block-uniform, after the only barrier
+    store_view_u8(record + ((e * Tm + tt) * kGeese + p) * kView, pm, lane, infer[e * kGeese + p] ? 1u : 0u);
 }
 
 inline int grid_for(int64_t n) { return (int)((n + 255) / 256); }
@@ -299,6 +360,18 @@ int hrl_geese_observe(const uint8_t *body, const uint8_t *hd, const uint8_t *len
     if (E == 0) return HRL_OK;
     hipLaunchKernelGGL(observe_kernel, dim3((unsigned)E), dim3(256), 0, static_cast<hipStream_t>(stream), body, hd,
                        len, food, prev, views, record, t, infer, E, Tm);
+    return launched();
+}
+
+int hrl_geese_observe_at(const uint8_t *body, const uint8_t *hd, const uint8_t *len, const int8_t *food,
+                         const int8_t *prev, float *views, uint8_t *record, const int64_t *ply, const uint8_t *infer,
+                         const uint8_t *active, int64_t E, int64_t P, int64_t Tm, void *stream) {
+    if (!body || !hd || !len || !food || !prev || !views || !record || !ply || !infer || !active || E < 0 ||
+        E > 0x7fffffff || P != kGeese || Tm < 1)
+        return HRL_EINVAL;
+    if (E == 0) return HRL_OK;
+    hipLaunchKernelGGL(observe_at_kernel, dim3((unsigned)E), dim3(256), 0, static_cast<hipStream_t>(stream), body, hd,
+                       len, food, prev, views, record, ply, infer, active, E, Tm);
     return launched();
 }
 

@@ -213,8 +213,8 @@ __device__ void harvest_returns(const HarvestArgs &a, int64_t e, int64_t row, in
     }
 }
 
-// One done slot e, by the block's share blockIdx.y; every branch that leaves is block-uniform.
-__device__ void harvest_slot(const HarvestArgs &a, int64_t e, int *s_r, int *s_c) {
+// The ring row and the length of done slot e: false when a higher slot claims the row in the same call.  Block-uniform.
+__device__ bool harvest_row(const HarvestArgs &a, int64_t e, int *s_r, int *s_c, int64_t *row_out, int64_t *L_out) {
     int r = 0, c = 0;
     for (int64_t i = threadIdx.x; i < a.E; i += kHarvestThreads) {
         const int d = a.done[i] != 0;
@@ -235,20 +235,32 @@ __device__ void harvest_slot(const HarvestArgs &a, int64_t e, int *s_r, int *s_c
         r += s_r[w];
         c += s_c[w];
     }
-    if ((int64_t)r + a.N < (int64_t)c) return;   // a higher slot claims this row in the same call
+    if ((int64_t)r + a.N < (int64_t)c) return false;   // a higher slot claims this row in the same call
     int64_t base = a.state[0] % a.N;
     if (base < 0) base += a.N;
-    const int64_t row = (base + r) % a.N;
-    int64_t L = a.ply[e];
-    L = L < 0 ? 0 : L > a.Tm ? a.Tm : L;
+    *row_out = (base + r) % a.N;
+    const int64_t L = a.ply[e];
+    *L_out = L < 0 ? 0 : L > a.Tm ? a.Tm : L;
+    return true;
+}
+
+// The slot's last block: the returns, length, outcome, game number.
+__device__ void harvest_tail(const HarvestArgs &a, int64_t e, int64_t row, int64_t L) {
+    harvest_returns(a, e, row, a.reward ? L : 0);
+    for (int q = threadIdx.x; q < a.P; q += kHarvestThreads) a.r_outcome[row * a.P + q] = a.outcome[e * a.P + q];
+    if (threadIdx.x == 0) {
+        a.r_length[row] = L;
+        a.ring_game[row] = a.game[e];
+    }
+}
+
+// One done slot e, by the block's share blockIdx.y; every branch that leaves is block-uniform.
+__device__ void harvest_slot(const HarvestArgs &a, int64_t e, int *s_r, int *s_c) {
+    int64_t row, L;
+    if (!harvest_row(a, e, s_r, s_c, &row, &L)) return;
     const int64_t TP = a.Tm * a.P;
-    if (blockIdx.y == kHarvestSplit) {   // the slot's last block: the returns, length, outcome, game number
-        harvest_returns(a, e, row, a.reward ? L : 0);
-        for (int q = threadIdx.x; q < a.P; q += kHarvestThreads) a.r_outcome[row * a.P + q] = a.outcome[e * a.P + q];
-        if (threadIdx.x == 0) {
-            a.r_length[row] = L;
-            a.ring_game[row] = a.game[e];
-        }
+    if (blockIdx.y == kHarvestSplit) {
+        harvest_tail(a, e, row, L);
         return;
     }
     const int64_t first = (int64_t)blockIdx.y * kHarvestThreads + threadIdx.x;
@@ -342,6 +354,229 @@ __global__ __launch_bounds__(kHarvestThreads) void harvest_advance_kernel(
         state[0] = (b + total) % N;
         state[1] = emitted + total;
         state[2] = next + total;
+    }
+}
+
+// ---- the per-player streaming generator (rollout.PlayerStreamGenerator): simultaneous-move envs ----
+// The public rules (w3 of the counter) are in include/hrl_env.h and rollout.stream_player_uniforms /
+// stream_select_uniform.
+
+constexpr uint32_t kPlayerW3 = 0x40000000u, kSelectW3 = 0x80000000u;
+
+__device__ __forceinline__ float philox_uniform(uint32_t x) { return ((float)(x >> 9) + 0.5f) * 0x1p-23f; }
+
+// sample_record_stream_kernel with one wave per (game, player): every player's slot of a played game is stored.
+__global__ __launch_bounds__(kWave *kGamesPerBlock) void sample_record_players_stream_kernel(
+    const float *__restrict__ logits, int64_t lstride, const float *__restrict__ value,
+    const uint8_t *__restrict__ legal, int64_t lpstride, const uint8_t *__restrict__ turns,
+    const uint8_t *__restrict__ infer, const uint8_t *__restrict__ active, uint32_t k0, uint32_t k1,
+    const int64_t *__restrict__ game, const int64_t *__restrict__ ply, int64_t E, int P, int A, int64_t Tm,
+    int64_t *__restrict__ action, float *__restrict__ usel, float *__restrict__ policy_buf,
+    float *__restrict__ amask_buf, int64_t *__restrict__ action_buf, float *__restrict__ value_buf,
+    uint8_t *__restrict__ tmask_buf, uint8_t *__restrict__ omask_buf) {
+    const int lane = threadIdx.x % kWave;
+    const int64_t w = (int64_t)blockIdx.x * kGamesPerBlock + threadIdx.x / kWave;   // the pair e * P + p
+    if (w >= E * P) return;
+    const int64_t e = w / P;
+    const int p = (int)(w - e * P);
+    const int64_t t = ply[e];
+    const uint64_t n = (uint64_t)game[e];
+    const uint32_t n0 = (uint32_t)n, n1 = (uint32_t)(n >> 32), tw = (uint32_t)(uint64_t)t;
+    if (p == 0 && lane == 0) usel[e] = philox_uniform(philox_word(k0, k1, n0, n1, tw, kSelectW3, 0));
+    if (!active[e] || t < 0 || t >= Tm) {   // wave-uniform
+        if (lane == 0) action[w] = 0;
+        return;
+    }
+    const bool turn = turns[w] != 0;
+    const int64_t row = (int64_t)p * E + e;
+    const float *lg = logits + row * lstride;
+    const uint8_t *lm = legal + e * (lpstride ? (int64_t)P * A : (int64_t)A) + p * lpstride;
+    const int64_t s = (e * Tm + t) * P + p;
+    float *pol = policy_buf + s * A;
+    float *am = amask_buf + s * A;
+    const uint32_t w3 = kPlayerW3 + (uint32_t)p * (uint32_t)((A + 3) >> 2);
+    float best = 0.0f;
+    int ib = A;   // no label yet
+    for (int j = lane; j < A; j += kWave) {
+        const float u = philox_uniform(philox_word(k0, k1, n0, n1, tw, w3 + (uint32_t)(j >> 2), j & 3));
+        const float m = lm[j] ? 0.0f : 1e32f;
+        const float pv = lg[j] - m;
+        const float g = pv - logf(-logf(u));
+        if (ib == A || better(g, j, best, ib)) {
+            best = g;
+            ib = j;
+        }
+        pol[j] = turn ? pv : 0.0f;
+        am[j] = turn ? m : 1e32f;
+    }
+    for (int off = kWave / 2; off > 0; off >>= 1) {
+        const float ob = __shfl_xor(best, off);
+        const int oi = __shfl_xor(ib, off);
+        if (oi != A && (ib == A || better(ob, oi, best, ib))) {
+            best = ob;
+            ib = oi;
+        }
+    }
+    if (lane == 0) {
+        const int64_t a = turn ? ib : 0;
+        const bool inf = infer[w] != 0;
+        action[w] = a;
+        action_buf[s] = a;
+        tmask_buf[s] = turn ? 1 : 0;
+        value_buf[s] = inf ? value[row] : 0.0f;
+        omask_buf[s] = inf ? 1 : 0;
+    }
+}
+
+// The per-player harvest.  The grid and the row rule are harvest_kernel's (harvest_row, harvest_tail); what differs is
+// the copy.  A slot's record of one field is Tm * width contiguous elements (width = P * w), uint8 or fp32 on either
+// side, and a Hungry Geese leaf is 1 MB per slot of which the mean game fills a few plies: the source is read for
+// the flat indices below lim = L * width only (copy_run), and [lim, total) is stores of the reset value
+// (fill_run), 16 bytes per lane between the run's unaligned edges.  The copy's unit -- 16, 4 or 1 source elements
+// per lane -- is the largest that is aligned for every slot and row (the host decides: PlayerField::unit).
+template <typename T> struct Elem;
+template <> struct Elem<float> {
+    __device__ static float to_f(float x) { return x; }
+    __device__ static float from_f(float x) { return x; }
+};
+template <> struct Elem<uint8_t> {
+    __device__ static float to_f(uint8_t x) { return (float)x; }
+    __device__ static uint8_t from_f(float x) { return (uint8_t)(int)x; }
+};
+// src.to(dst.dtype): uint8 -> uint8 and fp32 -> fp32 keep the bits
+template <typename S, typename D> __device__ __forceinline__ D convert(S x) { return Elem<D>::from_f(Elem<S>::to_f(x)); }
+template <> __device__ __forceinline__ uint8_t convert<uint8_t, uint8_t>(uint8_t x) { return x; }
+
+// four elements from a 16-byte aligned (fp32) or 4-byte aligned (uint8) address, and four to one
+__device__ __forceinline__ void load4(const float *p, float *x) {
+    const float4 v = *reinterpret_cast<const float4 *>(p);
+    x[0] = v.x, x[1] = v.y, x[2] = v.z, x[3] = v.w;
+}
+__device__ __forceinline__ void load4(const uint8_t *p, uint8_t *x) {
+    const uchar4 v = *reinterpret_cast<const uchar4 *>(p);
+    x[0] = v.x, x[1] = v.y, x[2] = v.z, x[3] = v.w;
+}
+__device__ __forceinline__ void store4(float *p, const float *x) {
+    *reinterpret_cast<float4 *>(p) = make_float4(x[0], x[1], x[2], x[3]);
+}
+__device__ __forceinline__ void store4(uint8_t *p, const uint8_t *x) {
+    *reinterpret_cast<uchar4 *>(p) = make_uchar4(x[0], x[1], x[2], x[3]);
+}
+
+template <typename S, typename D>
+__device__ void copy_run(const S *src, D *dst, int64_t lim, int unit, int64_t first, int64_t step) {
+    int64_t done = 0;
+    if (sizeof(S) == 1 && unit == 16) {   // uint8 sources only: one 16-byte load per lane
+        const int64_t nv = lim >> 4;
+        for (int64_t i = first; i < nv; i += step) {
+            const uint4 v = reinterpret_cast<const uint4 *>(src)[i];
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+            D out[16];
+#pragma unroll
+            for (int k = 0; k < 16; ++k) out[k] = convert<uint8_t, D>((uint8_t)(w[k >> 2] >> (8 * (k & 3))));
+#pragma unroll
+            for (int k = 0; k < 16; k += 4) store4(dst + i * 16 + k, out + k);
+        }
+        done = nv << 4;
+    } else if (unit == 4) {
+        const int64_t nv = lim >> 2;
+        for (int64_t i = first; i < nv; i += step) {
+            S in[4];
+            D out[4];
+            load4(src + i * 4, in);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) out[k] = convert<S, D>(in[k]);
+            store4(dst + i * 4, out);
+        }
+        done = nv << 2;
+    }
+    for (int64_t i = done + first; i < lim; i += step) dst[i] = convert<S, D>(src[i]);
+}
+
+__device__ __forceinline__ uint4 pattern16(float x) {
+    const uint32_t b = __float_as_uint(x);
+    return make_uint4(b, b, b, b);
+}
+__device__ __forceinline__ uint4 pattern16(uint8_t x) {
+    const uint32_t b = 0x01010101u * x;
+    return make_uint4(b, b, b, b);
+}
+
+// dst[lim, total) = fill
+template <typename D>
+__device__ void fill_run(D *dst, int64_t lim, int64_t total, float fill, int64_t first, int64_t step) {
+    constexpr int K = 16 / (int)sizeof(D);
+    const D x = Elem<D>::from_f(fill);
+    D *d = dst + lim;
+    const int64_t n = total - lim;
+    int64_t lead = (int64_t)(((16 - (reinterpret_cast<uintptr_t>(d) & 15)) & 15) / sizeof(D));
+    lead = lead < n ? lead : n;
+    for (int64_t i = first; i < lead; i += step) d[i] = x;
+    const int64_t nv = (n - lead) / K;
+    const uint4 pattern = pattern16(x);
+    uint4 *dv = reinterpret_cast<uint4 *>(d + lead);
+    for (int64_t i = first; i < nv; i += step) dv[i] = pattern;
+    for (int64_t i = lead + nv * K + first; i < n; i += step) d[i] = x;
+}
+
+template <typename S, typename D>
+__device__ void harvest_field(const void *src, void *dst, int64_t e, int64_t row, int64_t total, int64_t lim, int unit,
+                              float fill, int64_t first, int64_t step) {
+    D *d = static_cast<D *>(dst) + row * total;
+    copy_run<S, D>(static_cast<const S *>(src) + e * total, d, lim, unit, first, step);
+    fill_run<D>(d, lim, total, fill, first, step);
+}
+
+constexpr int kPlayerFields = HRL_REPLAY_MAX_LEAVES + 3;   // obs leaves, policy, amask, value
+struct PlayerField {
+    const void *src;
+    void *dst;
+    int64_t width;   // elements per ply: P * w
+    float fill;
+    int32_t stype, dtype, unit;
+};
+struct PlayerHarvestArgs {
+    HarvestArgs h;   // the rule's operands, the returns and the per-episode records; its own field table stays empty
+    PlayerField f[kPlayerFields];
+    int32_t nf;
+    const int64_t *action;
+    int64_t *r_action;
+    const uint8_t *tmask, *omask;
+    uint8_t *r_tmask, *r_omask;
+};
+
+__global__ __launch_bounds__(kHarvestThreads) void harvest_players_kernel(const PlayerHarvestArgs a) {
+    __shared__ int s_r[kHarvestThreads / kWave], s_c[kHarvestThreads / kWave];
+    const int64_t e = blockIdx.x;
+    if (!a.h.done[e]) return;   // block-uniform
+    int64_t row, L;
+    if (!harvest_row(a.h, e, s_r, s_c, &row, &L)) return;
+    if (blockIdx.y == kHarvestSplit) {
+        harvest_tail(a.h, e, row, L);
+        return;
+    }
+    const int64_t first = (int64_t)blockIdx.y * kHarvestThreads + threadIdx.x;
+    const int64_t step = (int64_t)kHarvestSplit * kHarvestThreads;
+    for (int k = 0; k < a.nf; ++k) {
+        const PlayerField &f = a.f[k];
+        const int64_t total = a.h.Tm * f.width, lim = L * f.width;
+        const bool su8 = f.stype == HRL_REPLAY_U8, du8 = f.dtype == HRL_REPLAY_U8;
+        if (su8 && du8)
+            harvest_field<uint8_t, uint8_t>(f.src, f.dst, e, row, total, lim, f.unit, f.fill, first, step);
+        else if (su8)
+            harvest_field<uint8_t, float>(f.src, f.dst, e, row, total, lim, f.unit, f.fill, first, step);
+        else if (du8)
+            harvest_field<float, uint8_t>(f.src, f.dst, e, row, total, lim, f.unit, f.fill, first, step);
+        else
+            harvest_field<float, float>(f.src, f.dst, e, row, total, lim, f.unit, f.fill, first, step);
+    }
+    const int64_t TP = a.h.Tm * a.h.P, LP = L * a.h.P;
+    for (int64_t i = first; i < TP; i += step) {
+        const bool v = i < LP;
+        a.r_action[row * TP + i] = v ? a.action[e * TP + i] : 0;
+        a.r_tmask[row * TP + i] = v ? a.tmask[e * TP + i] : 0;
+        a.r_omask[row * TP + i] = v ? a.omask[e * TP + i] : 0;
+        a.h.r_reward[row * TP + i] = (a.h.reward && v) ? (float)a.h.reward[e * TP + i] : 0.0f;
     }
 }
 
@@ -489,6 +724,111 @@ int hrl_selfplay_harvest(const uint8_t *done, const hrl_selfplay_slots *slots, i
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(harvest_kernel, dim3((unsigned)((E + kSlotsPerBlock - 1) / kSlotsPerBlock), kHarvestSplit + 1),
                        dim3(kHarvestThreads), 0, s, a);
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return HRL_ELAUNCH_BASE - (int)err;
+    hipLaunchKernelGGL(harvest_advance_kernel, dim3(1), dim3(kHarvestThreads), 0, s, done, E, N, game, ply, pending,
+                       state);
+    err = hipGetLastError();
+    return err == hipSuccess ? HRL_OK : HRL_ELAUNCH_BASE - (int)err;
+}
+
+int hrl_selfplay_sample_record_players_stream(const float *logits, int64_t logit_stride, const float *value,
+                                              const uint8_t *legal, int64_t legal_player_stride, const uint8_t *turns,
+                                              const uint8_t *infer, const uint8_t *active, uint64_t seed,
+                                              const int64_t *game, const int64_t *ply, int64_t E, int64_t P, int64_t A,
+                                              int64_t Tm, int64_t *action, float *usel, float *policy_buf,
+                                              float *amask_buf, int64_t *action_buf, float *value_buf,
+                                              uint8_t *tmask_buf, uint8_t *omask_buf, void *stream) {
+    if (!logits || !value || !legal || !turns || !infer || !active || !game || !ply || !action || !usel ||
+        !policy_buf || !amask_buf || !action_buf || !value_buf || !tmask_buf || !omask_buf || E < 0 || P < 1 ||
+        A < 1 || A > (1 << 20) || Tm < 1 || logit_stride < A || (legal_player_stride != 0 && legal_player_stride != A))
+        return HRL_EINVAL;
+    constexpr int64_t kLimit = 0x40000000;
+    if (P >= kLimit || E >= kLimit || P * E >= kLimit || P * ((A + 3) / 4) >= kLimit) return HRL_EINVAL;
+    if (E == 0) return HRL_OK;
+    const int blocks = (int)((E * P + kGamesPerBlock - 1) / kGamesPerBlock);
+    hipLaunchKernelGGL(sample_record_players_stream_kernel, dim3(blocks), dim3(kWave * kGamesPerBlock), 0,
+                       static_cast<hipStream_t>(stream), logits, logit_stride, value, legal, legal_player_stride, turns,
+                       infer, active, (uint32_t)seed, (uint32_t)(seed >> 32), game, ply, E, (int)P, (int)A, Tm, action,
+                       usel, policy_buf, amask_buf, action_buf, value_buf, tmask_buf, omask_buf);
+    const hipError_t err = hipGetLastError();
+    return err == hipSuccess ? HRL_OK : HRL_ELAUNCH_BASE - (int)err;
+}
+
+int hrl_selfplay_harvest_players(const uint8_t *done, const hrl_selfplay_player_slots *slots, int64_t *ply,
+                                 const float *outcome, double gamma, const hrl_replay_ring *ring, int64_t *ring_game,
+                                 int64_t *game, uint8_t *pending, int64_t *state, void *stream) {
+    if (!done || !slots || !ply || !outcome || !ring || !ring_game || !game || !pending || !state) return HRL_EINVAL;
+    const int64_t E = slots->E, Tm = slots->Tm, P = slots->P, A = slots->A, N = ring->N;
+    const int nl = slots->nleaves;
+    if (E < 0 || E > 0x7fffffff || Tm < 1 || P < 1 || A < 1 || N < 1 || ring->Tm != Tm || ring->P != P ||
+        ring->A != A || nl < 1 || nl > HRL_REPLAY_MAX_LEAVES || ring->nleaves != nl)
+        return HRL_EINVAL;
+    constexpr int64_t kMaxRecord = (int64_t)1 << 31;
+    if (Tm >= kMaxRecord || A >= kMaxRecord || P >= kMaxRecord || Tm * P >= kMaxRecord || P * A >= kMaxRecord ||
+        Tm * P * A >= kMaxRecord)
+        return HRL_EINVAL;
+    if (!slots->policy || !slots->amask || !slots->action || !slots->value || !slots->tmask || !slots->omask ||
+        !ring->policy || !ring->amask || !ring->action || !ring->value || !ring->tmask || !ring->omask ||
+        !ring->reward || !ring->ret || !ring->length || !ring->outcome)
+        return HRL_EINVAL;
+    PlayerHarvestArgs a{};
+    // the copy's unit: the most source elements per lane whose loads and stores are aligned in every slot and row
+    auto field = [&a, Tm](const void *src, const void *dst, int64_t width, int stype, int dtype, float fill) {
+        PlayerField &f = a.f[a.nf++];
+        f.src = src;
+        f.dst = const_cast<void *>(dst);
+        f.width = width;
+        f.stype = stype;
+        f.dtype = dtype;
+        f.fill = fill;
+        const int64_t total = Tm * width;
+        const uintptr_t sb = (uintptr_t)src, db = (uintptr_t)dst;
+        const int ssize = stype == HRL_REPLAY_U8 ? 1 : 4, dsize = dtype == HRL_REPLAY_U8 ? 1 : 4;
+        f.unit = 1;
+        for (int unit : {4, 16}) {
+            if (unit * ssize > 16) continue;   // one load of at most 16 bytes per lane
+            const int store = unit * dsize < 16 ? unit * dsize : 16;
+            if (total % unit == 0 && sb % (unit * ssize) == 0 && db % store == 0) f.unit = unit;
+        }
+    };
+    for (int l = 0; l < nl; ++l) {
+        const int64_t w = slots->obs_width[l];
+        const int stype = slots->obs_type[l], dtype = ring->obs_type[l];
+        if (w < 1 || w != ring->obs_width[l] || w >= kMaxRecord || P * w >= kMaxRecord || Tm * P * w >= kMaxRecord ||
+            !slots->obs[l] || !ring->obs[l] || (stype != HRL_REPLAY_U8 && stype != HRL_REPLAY_F32) ||
+            (dtype != HRL_REPLAY_U8 && dtype != HRL_REPLAY_F32))
+            return HRL_EINVAL;
+        field(slots->obs[l], ring->obs[l], P * w, stype, dtype, 0.0f);
+    }
+    field(slots->policy, ring->policy, P * A, HRL_REPLAY_F32, HRL_REPLAY_F32, 0.0f);
+    field(slots->amask, ring->amask, P * A, HRL_REPLAY_F32, HRL_REPLAY_F32, 1e32f);
+    field(slots->value, ring->value, P, HRL_REPLAY_F32, HRL_REPLAY_F32, 0.0f);
+    if (E == 0) return HRL_OK;
+    a.h.P = (int32_t)P;
+    a.h.reward = slots->reward;
+    a.h.r_reward = const_cast<float *>(ring->reward);
+    a.h.r_ret = const_cast<float *>(ring->ret);
+    a.h.r_outcome = const_cast<float *>(ring->outcome);
+    a.h.r_length = const_cast<int64_t *>(ring->length);
+    a.h.ring_game = ring_game;
+    a.h.outcome = outcome;
+    a.h.game = game;
+    a.h.ply = ply;
+    a.h.state = state;
+    a.h.done = done;
+    a.h.E = E;
+    a.h.Tm = Tm;
+    a.h.N = N;
+    a.h.gamma = gamma;
+    a.action = slots->action;
+    a.r_action = const_cast<int64_t *>(ring->action);
+    a.tmask = slots->tmask;
+    a.omask = slots->omask;
+    a.r_tmask = const_cast<uint8_t *>(ring->tmask);
+    a.r_omask = const_cast<uint8_t *>(ring->omask);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(harvest_players_kernel, dim3((unsigned)E, kHarvestSplit + 1), dim3(kHarvestThreads), 0, s, a);
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return HRL_ELAUNCH_BASE - (int)err;
     hipLaunchKernelGGL(harvest_advance_kernel, dim3(1), dim3(kHarvestThreads), 0, s, done, E, N, game, ply, pending,

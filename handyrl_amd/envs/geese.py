@@ -377,6 +377,22 @@ class HungryGeeseBatch:
                     _encode(self._np, e, self._games[e])
         self.next_game += count
 
+    def restart_games(self, mask, games):
+        """Slot e with mask[e] set becomes game number games[e] (both (E,) device tensors: nothing is read on the
+        host, so a captured graph may hold this).  ``next_game`` is not touched: the caller numbers the games
+        (``rollout.PlayerStreamGenerator``)."""
+        mask = mask.to(torch.bool).contiguous()
+        games = games.to(torch.long).contiguous()
+        assert mask.shape == (self.E,) and games.shape == (self.E,)
+        if self._hip():
+            self._state_ok()
+            self._native('hrl_geese_reset', self.body, self.head, self.length, self.food, self.last, self.prev,
+                         self.score, self.nstep, self.game, self.live, mask, games, 0, self._seed, self.E, self.P)
+            return
+        for e in np.flatnonzero(mask.numpy()):
+            self._games[e] = new_game(self._seed, int(games[e]))
+            _encode(self._np, e, self._games[e])
+
     def load_games(self, states, slots):
         """Python game states into the given slots (canonical ring form)."""
         slots = [int(e) for e in slots]
@@ -451,6 +467,31 @@ class HungryGeeseBatch:
         """All four views of every game as the forward's (4 * E, 17, 7, 11) input rows, player-major, and in the
         same launch the observation record of slot t for the (game, player) pairs of ``infer``."""
         return self._views(rec, t, infer).view(GEESE * self.E, *self.OBS_SHAPE)
+
+    def observe_players_record_at(self, rec, ply, infer, active):
+        """``observe_players_record`` for the streaming generator: game e records at its own ply index ply[e] into
+        the UINT8 record ``rec`` (E, Tm, 4, 17, 7, 11).  An ``active`` game with ply[e] in [0, Tm) gets view p in
+        slot (e, ply[e], p) where infer[e, p] and zeros where not (the slot buffers outlive a game: a dead goose's
+        slot must not keep an earlier game's planes); any other game stores nothing.  Returns the forward's
+        (4 * E, 17, 7, 11) fp32 input rows, player-major, for every game."""
+        E = self.E
+        infer, active = infer.to(torch.bool).contiguous(), active.to(torch.bool).contiguous()
+        assert rec.shape[0] == E and rec.shape[2:] == (GEESE, *self.OBS_SHAPE) and rec.is_contiguous()
+        assert rec.dtype == torch.uint8 and infer.shape == (E, GEESE) and active.shape == (E,)
+        assert ply.shape == (E,) and ply.dtype == torch.long and ply.is_contiguous()
+        if self._hip():
+            self._state_ok()
+            views = torch.empty(GEESE, E, *self.OBS_SHAPE, device=self.device)
+            self._native('hrl_geese_observe_at', self.body, self.head, self.length, self.food, self.prev, views, rec,
+                         ply, infer, active, E, self.P, rec.shape[1])
+            return views.view(GEESE * E, *self.OBS_SHAPE)
+        views = self._views()
+        for e in np.flatnonzero(active.numpy()):
+            t = int(ply[e])
+            if 0 <= t < rec.shape[1]:
+                for p in range(GEESE):
+                    rec[e, t, p] = views[p, e].to(torch.uint8) if bool(infer[e, p]) else 0
+        return views.view(GEESE * E, *self.OBS_SHAPE)
 
     def views_torch(self):
         """``_views()`` as batched torch ops on the state tensors: the formulation tools/geese_selfplay_bench.py

@@ -32,7 +32,10 @@ written) with the actors and the learner on the GPU:
   finished game written into the ``DeviceReplay`` ring by one launch and its slot restarted at once, so no slot
   waits for the longest game of a batch.  Every call plays until ``update_episodes`` more games are in the ring
   (it may overshoot by less than one check interval) and the episode counts follow what was actually emitted;
-  any other mode with ``stream`` raises at start-up;
+  a simultaneous-move env (Hungry Geese, ParallelTicTacToe) with ``observation`` or solo training
+  (``turn_based_training: False``) streams its per-player ply with ``rollout.PlayerStreamGenerator`` into a
+  ``PlayerReplay`` the same way, a finished slot restarting on the very next step; any other mode with ``stream``
+  (an alternating env with ``observation`` or solo training, a simultaneous env in the stock mode) raises at start-up;
 * ``self_play: fused`` is the lockstep generator with ``fused_game=True``: every ``generate`` call is one launch that
   plays all the games to the end (TicTacToe's stock mode on a CUDA device with ``inference: fused``; else it raises);
 * ``update_episodes`` games per epoch with the current weights (the
@@ -85,8 +88,8 @@ import yaml
 from . import distributed as hdist
 from .environment import make_env, prepare_env
 from .hostgen import HostBatchGenerator, MomentReplay
-from .rollout import (DeviceGenerator, DeviceReplay, ParallelTicTacToeBatch, PlayerReplay, StreamGenerator,
-                      TicTacToeBatch)
+from .rollout import (DeviceGenerator, DeviceReplay, ParallelTicTacToeBatch, PlayerReplay, PlayerStreamGenerator,
+                      StreamGenerator, TicTacToeBatch)
 from .trainer import Trainer
 
 
@@ -207,7 +210,11 @@ def train_main(args, device=None, loss_fn=None, model_dir='models', log=print):
         raise ValueError("train_args['self_play']: 'fused' plays whole TicTacToe games in one launch: it needs a CUDA "
                          "device, the stock mode (turn_based_training without observation) of the TicTacToe batched "
                          "env and inference: fused; this configuration is played by self_play: lockstep")
-    if self_play == 'stream' and (not use_device or per_player or not getattr(batched, 'ALTERNATING', False)):
+    # a simultaneous-move env under a per-player configuration (observation or solo training) streams its per-player
+    # ply (PlayerStreamGenerator), an alternating env in the stock mode its mover-only ply
+    stream_players = use_device and getattr(batched, 'SIMULTANEOUS', False) and (observe or not tbt)
+    if self_play == 'stream' and not stream_players and (not use_device or per_player
+                                                        or not getattr(batched, 'ALTERNATING', False)):
         raise ValueError("train_args['self_play']: 'stream' plays the mover-only ply of an alternating env with a "
                          "batched (device) form (turn_based_training without observation); this configuration is "
                          "played by the lockstep generator (self_play: lockstep)")
@@ -232,7 +239,22 @@ def train_main(args, device=None, loss_fn=None, model_dir='models', log=print):
             evaluator = DeviceEvaluator(eval_cls(eval_slots, device), play_net, observation=observe,
                                         temperature=float(targs.get('eval_temperature', 0.0)), seed=seed, **match)
     played = None   # a generator that reports what it emitted (stream): episodes of the last play()
-    if use_device and self_play == 'stream':
+    if use_device and self_play == 'stream' and stream_players:
+        slots = int(targs.get('stream_slots') or games)
+        env_batch = batched(slots, device)
+        if hasattr(env_batch, 'seed'):     # an env with randomness of its own (Geese's food): per rank, like `rng`
+            env_batch.seed(seed)
+        replay = PlayerReplay(maximum, batched.MAX_PLIES, batched.OBS_SHAPE, batched.A, batched.P, device,
+                              maximum_episodes=maximum, obs_dtype=torch.uint8, solo=not tbt,
+                              mover=tbt and not observe, draw=targs.get('window_draw', 'multinomial'))
+        gen = PlayerStreamGenerator(env_batch, play_net, replay, gamma=targs['gamma'], seed=seed, observation=observe)
+        played = [0]
+
+        def play():
+            out = gen.generate(games)       # at least `games` more episodes, straight into the ring
+            played[0] = out['episodes']
+            return float(out['env_steps'])
+    elif use_device and self_play == 'stream':
         slots = int(targs.get('stream_slots') or games)
         replay = DeviceReplay(maximum, batched.MAX_PLIES, batched.OBS_SHAPE, batched.A, batched.P, device,
                               maximum_episodes=maximum, obs_dtype=torch.uint8,

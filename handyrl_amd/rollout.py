@@ -46,7 +46,7 @@ from .util import map_r, bimap_r
 
 __all__ = ['TicTacToeBatch', 'ParallelTicTacToeBatch', 'DeviceGenerator', 'DeviceReplay', 'PlayerReplay',
            'episodes_to_wire', 'player_episodes_to_wire', 'reference_uniforms', 'StreamGenerator', 'stream_uniforms',
-           'philox4x32']
+           'philox4x32', 'PlayerStreamGenerator', 'stream_player_uniforms', 'stream_select_uniform']
 
 
 class TicTacToeBatch:
@@ -771,6 +771,90 @@ def stream_uniforms_torch(seed, game, ply, A):
     return ((x >> 9).float() + 0.5) * (2.0 ** -23)
 
 
+PLAYER_W3, SELECT_W3 = 0x40000000, 0x80000000
+
+
+def _player_blocks(P, A):
+    """ceil(A / 4), the Philox calls per player; the players' range of the last counter word must end below
+    ``SELECT_W3 - PLAYER_W3``."""
+    blocks = (int(A) + 3) // 4
+    if int(P) * blocks >= 0x40000000:
+        raise ValueError('P * ceil(A / 4) = %d leaves the counter range of the player uniforms (< 0x40000000)'
+                         % (int(P) * blocks))
+    return blocks
+
+
+def _words_to_uniform(out, word):
+    x = np.select([word == 0, word == 1, word == 2], out[:3], out[3])
+    return ((x >> np.uint64(9)).astype(np.float32) + np.float32(0.5)) * np.float32(2.0 ** -23)
+
+
+def stream_player_uniforms(seed, game, ply, P, A):
+    """The uniforms the players of game number ``game`` sample ply ``ply`` with in a simultaneous-move env: (P, A)
+    float32 (``game`` / ``ply`` integer arrays: (..., P, A)).  The public rule of ``PlayerStreamGenerator``, which
+    hrl_selfplay_sample_record_players_stream reproduces bit for bit: ``stream_uniforms``' generator, key and float
+    mapping with the counter (game & 0xffffffff, game >> 32, ply, w3), w3 = 0x40000000 + p * ceil(A / 4) + a // 4
+    for player p and label a, output word a % 4.
+
+    The last counter word w3 keeps apart what one (seed, game, ply) draws -- ``main`` gives the env and the generator
+    the same seed: the mover rule (``stream_uniforms``) takes a // 4, below 0x40000000; the Hungry Geese picks
+    (``geese.geese_picks``) 0 and 1; these player uniforms [0x40000000, 0x80000000); ``stream_select_uniform``
+    0x80000000; ``evaluation.eval_pick`` 0xffffffff.  Without the offset a game's food placement and its geese's action
+    noise would be the same random words.  ``ValueError`` when P * ceil(A / 4) >= 0x40000000."""
+    blocks = _player_blocks(P, A)
+    seed = int(seed) & 0xffffffffffffffff
+    game = np.asarray(game, dtype=np.int64).astype(np.uint64)[..., None, None]
+    ply = np.asarray(ply, dtype=np.int64).astype(np.uint64)[..., None, None]
+    a = np.arange(A, dtype=np.uint64).reshape(1, A)
+    p = np.arange(P, dtype=np.uint64).reshape(P, 1)
+    w3 = np.uint64(PLAYER_W3) + p * np.uint64(blocks) + (a >> np.uint64(2))
+    out = philox4x32((game, game >> np.uint64(32), ply, w3), (seed & _M32, seed >> 32))
+    return _words_to_uniform(out, np.broadcast_to(a & np.uint64(3), out[0].shape))
+
+
+def stream_select_uniform(seed, game, ply):
+    """The uniform ``u`` a simultaneous env's ``step_players`` takes at ply ``ply`` of game number ``game`` (float32
+    scalar; arrays: the broadcast shape): the rule of ``stream_player_uniforms`` with w3 = 0x80000000 and output word
+    0.  ParallelTicTacToe plays player floor(u * P); Hungry Geese ignores it."""
+    seed = int(seed) & 0xffffffffffffffff
+    game = np.asarray(game, dtype=np.int64).astype(np.uint64)
+    ply = np.asarray(ply, dtype=np.int64).astype(np.uint64)
+    out = philox4x32((game, game >> np.uint64(32), ply, SELECT_W3), (seed & _M32, seed >> 32))
+    return ((out[0] >> np.uint64(9)).astype(np.float32) + np.float32(0.5)) * np.float32(2.0 ** -23)
+
+
+def _philox_torch(seed, c0, c1, c2, c3):
+    """Philox4x32-10 on int64 tensors holding 32-bit words (a 32 x 32 product wraps in int64 to the right 64 bits)."""
+    k0, k1 = seed & _M32, seed >> 32
+    for _ in range(10):
+        p0, p1 = c0 * _PHILOX_M[0], c2 * _PHILOX_M[1]
+        c0, c1, c2, c3 = ((p1 >> 32) & _M32) ^ c1 ^ k0, p1 & _M32, ((p0 >> 32) & _M32) ^ c3 ^ k1, p0 & _M32
+        k0, k1 = (k0 + _PHILOX_W[0]) & _M32, (k1 + _PHILOX_W[1]) & _M32
+    return c0, c1, c2, c3
+
+
+def stream_player_uniforms_torch(seed, game, ply, P, A):
+    """``stream_player_uniforms`` for E games as torch ops: game, ply (E,) int64 -> (E, P, A) float32."""
+    blocks = _player_blocks(P, A)
+    seed = int(seed) & 0xffffffffffffffff
+    E, dev = game.shape[0], game.device
+    a = torch.arange(A, device=dev).view(1, 1, A)
+    p = torch.arange(P, device=dev).view(1, P, 1)
+    shape = (E, P, A)
+    c = _philox_torch(seed, (game & _M32).view(E, 1, 1).expand(shape), ((game >> 32) & _M32).view(E, 1, 1).expand(shape),
+                      (ply & _M32).view(E, 1, 1).expand(shape), (PLAYER_W3 + p * blocks + (a >> 2)).expand(shape))
+    w = a & 3
+    x = torch.where(w == 0, c[0], torch.where(w == 1, c[1], torch.where(w == 2, c[2], c[3])))
+    return ((x >> 9).float() + 0.5) * (2.0 ** -23)
+
+
+def stream_select_uniform_torch(seed, game, ply):
+    """``stream_select_uniform`` for E games as torch ops: game, ply (E,) int64 -> (E,) float32."""
+    seed = int(seed) & 0xffffffffffffffff
+    c = _philox_torch(seed, game & _M32, (game >> 32) & _M32, ply & _M32, torch.full_like(game, SELECT_W3))
+    return ((c[0] >> 9).float() + 0.5) * (2.0 ** -23)
+
+
 def _record_at(buf, rows, ply, x, active):
     """Slot (e, ply[e]) of ``buf`` (E, Tm, ...) becomes x[e] where active[e]; an inactive game stores nothing (its
     ply may equal Tm: the index is clamped and the old value written back)."""
@@ -901,7 +985,10 @@ def _ring_struct(replay):
         ring.obs_width[l] = int(np.prod(o.shape[replay._lead:], dtype=np.int64))
     for k in ('policy', 'amask', 'action', 'value', 'reward', 'ret', 'length', 'outcome'):
         setattr(ring, k, getattr(replay, k).data_ptr())
-    ring.turn = replay.turn.data_ptr()
+    if replay._lead == 3:      # PlayerReplay: the PLAYERS layouts
+        ring.tmask, ring.omask = replay.tmask.data_ptr(), replay.omask.data_ptr()
+    else:
+        ring.turn = replay.turn.data_ptr()
     return ring
 
 
@@ -1126,6 +1213,348 @@ class StreamGenerator:
         self.replay.ptr = ring_ptr
         self.replay.count = min(self.replay.count + emitted - emitted0, N)
         self._emitted, self.games_started = emitted, next_game
+        return {'episodes': emitted - emitted0, 'env_steps': self._steps - steps0, 'plies': self.s - s0}
+
+
+# ---- streaming self-play of simultaneous-move envs: per-player records (PlayerStreamGenerator) ----
+
+def _record_players_at(buf, rows, ply, x, played):
+    """Slot (e, ply[e]) of ``buf`` (E, Tm, P, ...) becomes x[e] (P, ...) where played[e]; other games store nothing
+    (the index is clamped and the old value written back)."""
+    idx = ply.clamp(0, buf.shape[1] - 1)
+    keep = played.view(-1, *([1] * (x.dim() - 1)))
+    buf[rows, idx] = torch.where(keep, x.to(buf.dtype), buf[rows, idx])
+
+
+def sample_record_players_stream_torch(st, seed, logits, legal, value, turns, infer, active):
+    """The per-player streaming ply's sampling and recording tail as torch ops (the contract of
+    hrl_selfplay_sample_record_players_stream, include/hrl_env.h, which equals this bit for bit).  ``logits``
+    (P * E, >= A) and ``value`` (P * E, ...) are the forward's rows, player-major; ``legal`` (E, A) or (E, P, A);
+    ``turns`` / ``infer`` (E, P) and ``active`` (E,) bool.  A game is played when it is active and its ply lies in
+    [0, Tm); a played game stores slot (e, ply[e]) of EVERY player: the live values where ``turns`` (policy, action
+    mask, action, turn mask) or ``infer`` (value, observation mask) is set and the reset values elsewhere.  Returns
+    the actions (E, P) (0 where not played or no turn) and the select uniforms (E,)."""
+    rows, ply, game = st['rows'], st['ply'], st['game']
+    E, P = turns.shape
+    Tm, A = st['policy'].shape[1], st['policy'].shape[3]
+    played = active & (ply >= 0) & (ply < Tm)
+    lg = logits.float().view(P, E, -1)[:, :, :A].transpose(0, 1)                  # (E, P, A)
+    val = value.float().reshape(P, E).t()                                         # (E, P)
+    if legal.dim() == 2:
+        legal = legal.view(E, 1, A).expand(E, P, A)
+    m = torch.where(legal, 0.0, 1e32)
+    p = lg - m
+    u = stream_player_uniforms_torch(seed, game, ply, P, A)
+    a = torch.argmax(p - torch.log(-torch.log(u)), dim=-1)
+    sampled = turns & played.view(E, 1)
+    a = torch.where(sampled, a, torch.zeros_like(a))
+    t3 = turns.view(E, P, 1)
+    _record_players_at(st['policy'], rows, ply, torch.where(t3, p, 0.0), played)
+    _record_players_at(st['amask'], rows, ply, torch.where(t3, m, 1e32), played)
+    _record_players_at(st['action'], rows, ply, a, played)
+    _record_players_at(st['tmask'], rows, ply, turns, played)
+    _record_players_at(st['value'], rows, ply, torch.where(infer, val, 0.0), played)
+    _record_players_at(st['omask'], rows, ply, infer, played)
+    return a, stream_select_uniform_torch(seed, game, ply)
+
+
+def sample_record_players_stream_hip(st, seed, logits, legal, value, turns, infer, active):
+    """sample_record_players_stream_torch as ONE launch, one wave per (game, player)."""
+    from . import _native
+    E, P = turns.shape
+    Tm, A = st['policy'].shape[1], st['policy'].shape[3]
+    _player_blocks(P, A)
+    logits = logits.float()
+    if logits.stride(1) != 1:
+        logits = logits.contiguous()
+    value = value.reshape(P * E).float().contiguous()
+    legal, turns, infer, active = legal.contiguous(), turns.contiguous(), infer.contiguous(), active.contiguous()
+    assert logits.shape[0] == P * E and logits.shape[1] >= A
+    assert legal.dtype == torch.bool and legal.shape in ((E, A), (E, P, A))
+    assert infer.shape == (E, P) and active.shape == (E,)
+    assert turns.dtype == infer.dtype == active.dtype == torch.bool
+    assert st['policy'].shape == st['amask'].shape == (E, Tm, P, A)
+    for k, dt in (('policy', torch.float32), ('amask', torch.float32), ('action', torch.long),
+                  ('value', torch.float32), ('tmask', torch.bool), ('omask', torch.bool)):
+        assert st[k].dtype == dt and st[k].is_contiguous() and st[k].shape[:3] == (E, Tm, P), k
+    for k in ('game', 'ply'):
+        assert st[k].shape == (E,) and st[k].dtype == torch.long and st[k].is_contiguous()
+    a = torch.empty(E, P, dtype=torch.long, device=logits.device)
+    usel = torch.empty(E, device=logits.device)
+    _native.check(_native.load().hrl_selfplay_sample_record_players_stream(
+        _native.ptr(logits), logits.stride(0), _native.ptr(value), _native.ptr(legal), A if legal.dim() == 3 else 0,
+        _native.ptr(turns), _native.ptr(infer), _native.ptr(active), int(seed) & 0xffffffffffffffff,
+        _native.ptr(st['game']), _native.ptr(st['ply']), E, P, A, Tm, _native.ptr(a), _native.ptr(usel),
+        _native.ptr(st['policy']), _native.ptr(st['amask']), _native.ptr(st['action']), _native.ptr(st['value']),
+        _native.ptr(st['tmask']), _native.ptr(st['omask']), _native.stream_of(logits.device)),
+        'hrl_selfplay_sample_record_players_stream')
+    return a, usel
+
+
+def harvest_players_torch(st, done, outcome, gamma, replay, ring_game, has_reward=False):
+    """``harvest_torch`` for per-player records into a ``PlayerReplay`` (the contract of
+    hrl_selfplay_harvest_players, which equals this bit for bit): the same rows, the same order and restart; the
+    records carry a player axis, ``tmask`` / ``omask`` take the place of ``turn``, and an observation leaf is
+    converted as ``src.to(dst.dtype)``.  ``st``: the slot records and 'ply', 'game', 'pending', 'state', 'rows'."""
+    E, N, Tm = done.shape[0], replay.N, replay.Tm
+    dev = done.device
+    if dev.type == 'cpu' and not bool(done.any()):
+        return      # nothing changes; on the CPU the look costs nothing (a GPU call must not read the device)
+    state, ply, game = st['state'], st['ply'], st['game']
+    W = min(E, N)
+    d = done.long()
+    r = torch.cumsum(d, 0) - d
+    c = d.sum()
+    e_idx = st['rows']
+    order = torch.empty_like(e_idx).scatter_(0, torch.where(done, r, c + (e_idx - r)), e_idx)   # done slots first
+    k = torch.arange(W, device=dev)
+    written = k < c
+    last = k + N * torch.div(torch.clamp(c - 1 - k, min=0), N, rounding_mode='floor')
+    slot = order[torch.where(written, last, k)]
+    rows = (state[0] + k) % N
+    L = ply[slot].clamp(0, Tm)
+    valid = torch.arange(Tm, device=dev).view(1, Tm) < L.view(W, 1)
+
+    def put(dst, new):
+        w = written.view(W, *([1] * (new.dim() - 1)))
+        dst.index_copy_(0, rows, torch.where(w, new.to(dst.dtype), dst.index_select(0, rows)))
+
+    def plies(src, fill=0):
+        v = valid.view(W, Tm, *([1] * (src.dim() - 2)))
+        return torch.where(v, src.index_select(0, slot), fill)
+    bimap_r(replay.obs, st['obs'], lambda dst, src: put(dst, plies(src).to(dst.dtype)))
+    put(replay.policy, plies(st['policy']))
+    put(replay.amask, plies(st['amask'], 1e32))
+    for key in ('action', 'value', 'tmask', 'omask'):
+        put(getattr(replay, key), plies(st[key]))
+    rew = plies(st['reward']) if has_reward else torch.zeros(W, Tm, replay.P, dtype=torch.float64, device=dev)
+    put(replay.reward, rew.float())
+    ret = torch.zeros(W, Tm, replay.P, device=dev)
+    acc = torch.zeros_like(rew[:, 0])
+    for t in range(Tm - 1, -1, -1):       # DeviceGenerator._returns: fp64 from the top
+        acc = rew[:, t] + gamma * acc
+        ret[:, t].copy_(acc)
+    put(replay.ret, ret)
+    put(replay.length, L)
+    put(replay.outcome, outcome.index_select(0, slot))
+    put(ring_game, game.index_select(0, slot))
+    game.copy_(torch.where(done, state[2] + r, game))
+    ply.masked_fill_(done, 0)
+    st['pending'].logical_or_(done)
+    state[0:1].copy_(((state[0] + c) % N).view(1))
+    state[1:3].add_(c)
+
+
+def _obs_type(t):
+    from . import _native
+    if t.dtype not in (torch.uint8, torch.float32):
+        raise ValueError('observation records are uint8 or float32, not %s' % t.dtype)
+    return _native.REPLAY_F32 if t.dtype == torch.float32 else _native.REPLAY_U8
+
+
+def harvest_players_hip(st, done, outcome, gamma, replay, ring_game, has_reward=False):
+    """harvest_players_torch as the two launches of hrl_selfplay_harvest_players."""
+    from . import _native
+    E, Tm, P, A = st['policy'].shape
+    src = _leaves(st['obs'])
+    slots = _native.SelfplayPlayerSlots()
+    slots.E, slots.Tm, slots.P, slots.A, slots.nleaves = E, Tm, P, A, len(src)
+    if len(src) > _native.REPLAY_MAX_LEAVES:
+        raise ValueError('at most %d observation leaves' % _native.REPLAY_MAX_LEAVES)
+    for l, o in enumerate(src):
+        assert o.is_contiguous() and o.shape[:3] == (E, Tm, P)
+        slots.obs[l] = o.data_ptr()
+        slots.obs_type[l] = _obs_type(o)
+        slots.obs_width[l] = int(np.prod(o.shape[3:], dtype=np.int64))
+    for k in ('policy', 'amask', 'action', 'value', 'tmask', 'omask'):
+        assert st[k].is_contiguous()
+        setattr(slots, k, st[k].data_ptr())
+    slots.reward = st['reward'].data_ptr() if has_reward else None
+    done, outcome = done.contiguous(), outcome.float().contiguous()
+    assert done.shape == (E,) and done.dtype == torch.bool and outcome.shape == (E, replay.P)
+    assert st['tmask'].dtype == st['omask'].dtype == torch.bool and st['action'].dtype == torch.long
+    assert st['pending'].dtype == torch.bool and st['state'].shape == (3,) and st['state'].dtype == torch.long
+    assert ring_game.shape == (replay.N,) and ring_game.dtype == torch.long and ring_game.is_contiguous()
+    ring = _ring_struct(replay)
+    _native.check(_native.load().hrl_selfplay_harvest_players(
+        _native.ptr(done), ctypes.byref(slots), _native.ptr(st['ply']), _native.ptr(outcome), float(gamma),
+        ctypes.byref(ring), _native.ptr(ring_game), _native.ptr(st['game']), _native.ptr(st['pending']),
+        _native.ptr(st['state']), _native.stream_of(done.device)), 'hrl_selfplay_harvest_players')
+
+
+class PlayerStreamGenerator:
+    """``StreamGenerator`` for simultaneous-move envs (``SIMULTANEOUS``: Hungry Geese, ParallelTicTacToe): E slots,
+    each at its own ply, every player moving every ply; a finished game goes straight into a ``PlayerReplay`` ring
+    and its slot starts the next game on the very next step (a simultaneous env has no mover parity to wait for).
+    The lockstep ``DeviceGenerator`` runs every ply until the last of its E games ends; with games of a few plies
+    most of its forward rows belong to finished games.
+
+    One global step: the ``pending`` slots restart (``env.restart_games(mask, games)`` where the env numbers its
+    games itself, else ``reset_where``); ``active`` / ``turns`` / ``infer`` are snapshot; every view is built and
+    recorded at (e, ply[e]) (``env.observe_players_record_at``: uint8 slot records, one launch; else torch ops on
+    fp32 ones); one forward over the P * E rows; the sampling and recording tail
+    (hrl_selfplay_sample_record_players_stream); ``env.step_players``; ``ply += active``; the harvest of the games
+    that ended (hrl_selfplay_harvest_players).  The step is one captured graph.
+
+    Game number n samples ply t with ``stream_player_uniforms(seed, n, t, P, A)`` and steps with
+    ``stream_select_uniform(seed, n, t)`` whatever slot it is played in and whenever, so every ring row can be
+    refereed on its own (``ring_game`` names its game).  State persists across calls: ``generate(64)`` and four
+    ``generate(16)`` emit the same first 64 episodes.  ``generate`` mirrors the device ring state into
+    ``replay.ptr`` / ``replay.count``, ``games_started`` and ``env.next_game``.
+
+    Scope: a ``SIMULTANEOUS`` env, a net without recurrent state and a ``PlayerReplay`` of the env's (Tm, P, A);
+    ``observation=True`` records every live player's view (for these envs every live player is a turn player
+    anyway).  Everything else is played by the lockstep ``DeviceGenerator`` and raises ``ValueError`` here."""
+
+    def __init__(self, env_batch, net, replay, gamma=0.8, seed=0, check_every=16, graph=None, observation=False):
+        if (not getattr(env_batch, 'SIMULTANEOUS', False) or hasattr(net, 'init_hidden')
+                or getattr(replay, '_lead', 2) != 3):
+            raise ValueError('PlayerStreamGenerator plays a simultaneous-move env with a net without recurrent state '
+                             'into a PlayerReplay; alternating envs stream through rollout.StreamGenerator, and '
+                             'everything else is played by the lockstep generator (rollout.DeviceGenerator)')
+        if (replay.Tm, replay.P, replay.policy.shape[-1]) != (env_batch.MAX_PLIES, env_batch.P, env_batch.A):
+            raise ValueError('the replay does not have the env\'s MAX_PLIES, P and A; the lockstep generator '
+                             '(rollout.DeviceGenerator) returns episodes of any replay\'s shape')
+        _player_blocks(env_batch.P, env_batch.A)
+        self.env, self.net, self.replay = env_batch, net, replay
+        self.gamma, self.seed = float(gamma), int(seed) & 0xffffffffffffffff
+        self.check_every = max(1, int(check_every or 1))
+        self.graph = graph
+        self.observation = bool(observation)
+        self.s = 0                         # global steps run
+        self.games_started = env_batch.E
+        self._emitted = 0
+        self._steps = 0                    # env-steps of the emitted episodes
+        self._st = None
+        self._graphs = None
+        self.ring_game = torch.full((replay.N,), -1, dtype=torch.long, device=env_batch.device)
+
+    def _use_graph(self):
+        return graph_wanted(self.env.device, self.graph)
+
+    def _state(self):
+        """The slots' buffers, allocated once: the games live in them across calls.  Every slot starts ``pending``
+        with its own index as game number, so the first step starts games 0 .. E-1 like any later restart."""
+        if self._st is not None:
+            return self._st
+        env, E, dev = self.env, self.env.E, self.env.device
+        Tm, A, P = env.MAX_PLIES, env.A, env.P
+        u8 = hasattr(env, 'observe_players_record_at')
+        st = {'obs': _alloc(env.OBS_SHAPE, (E, Tm, P), dev, torch.uint8 if u8 else torch.float32),
+              'policy': torch.zeros(E, Tm, P, A, device=dev),
+              'amask': torch.full((E, Tm, P, A), 1e32, device=dev),
+              'action': torch.zeros(E, Tm, P, dtype=torch.long, device=dev),
+              'value': torch.zeros(E, Tm, P, device=dev),
+              'tmask': torch.zeros(E, Tm, P, dtype=torch.bool, device=dev),
+              'omask': torch.zeros(E, Tm, P, dtype=torch.bool, device=dev),
+              'ply': torch.zeros(E, dtype=torch.long, device=dev),
+              'game': torch.arange(E, dtype=torch.long, device=dev),
+              'pending': torch.ones(E, dtype=torch.bool, device=dev),
+              'played': torch.zeros(E, dtype=torch.long, device=dev),     # plies played by the slot, all games
+              'state': torch.tensor([self.replay.ptr, 0, E], dtype=torch.long, device=dev),
+              'rows': torch.arange(E, device=dev),
+              'players': torch.arange(P, device=dev).view(P, 1).expand(P, E).contiguous(),
+              'obs_dev': torch.device(dev).type}
+        if hasattr(env, 'reward'):
+            st['reward'] = torch.zeros(E, Tm, P, device=dev, dtype=torch.float64)
+        self._st = st
+        return st
+
+    def _persistent(self, st):
+        """Everything a step changes besides the slot records and the ring."""
+        return self.env.state_tensors() + [st[k] for k in ('ply', 'game', 'pending', 'played', 'state')]
+
+    def _ply(self, st, dry=False):
+        """One global step; ``dry``: nothing is harvested (capture warm-up)."""
+        env, E, P, Tm = self.env, self.env.E, self.env.P, self.env.MAX_PLIES
+        fused = FUSED_STREAM and st['obs_dev'] == 'cuda'
+        ply, rows, pending = st['ply'], st['rows'], st['pending']
+        if hasattr(env, 'restart_games'):
+            env.restart_games(pending, st['game'])
+        else:
+            env.reset_where(pending)
+        pending.zero_()
+        # snapshots: an env's active() may be state its step updates in place
+        active = (env.active() if hasattr(env, 'active') else ~env.terminal()).clone()
+        turns = (env.turns_mask() & active.view(E, 1)).contiguous()
+        infer = active.view(E, 1).expand(E, P).contiguous() if self.observation else turns
+        if hasattr(env, 'observe_players_record_at'):
+            o = env.observe_players_record_at(st['obs'], ply, infer, active)                  # (P * E, ...)
+        else:
+            views = [env.observation(st['players'][p]) for p in range(P)]
+            o = _stack_views(views)
+            played = active & (ply < Tm)
+
+            def record(buf, v):
+                keep = infer.view(E, P, *([1] * (v.dim() - 2)))
+                _record_players_at(buf, rows, ply, torch.where(keep, v, 0.0), played)
+            bimap_r(st['obs'], _stack_views(views, batch_first=True), record)
+        out = self.net(o, None)
+        legal = env.legal_players() if hasattr(env, 'legal_players') else env.legal()
+        sample = sample_record_players_stream_hip if fused else sample_record_players_stream_torch
+        a, usel = sample(st, self.seed, out['policy'], legal, out['value'], turns, infer, active)
+        env.step_players(a, turns, active, usel)
+        has_reward = 'reward' in st
+        if has_reward:
+            _record_players_at(st['reward'], rows, ply, env.reward().to(st['reward'].dtype), active & (ply < Tm))
+        ply.add_(active)
+        st['played'].add_(active)
+        done = active & (env.terminal() | (ply >= Tm))
+        if dry:
+            done = torch.zeros_like(done)
+        harvest = harvest_players_hip if fused else harvest_players_torch
+        harvest(st, done, env.outcome(), self.gamma, self.replay, self.ring_game, has_reward)
+
+    def _capture(self, st):
+        """The step as one graph.  A warm-up step runs first on a side stream (library workspaces) and harvests
+        nothing; the games and the ring state are then put back, so that warm-up and capture leave no trace (a slot
+        record the warm-up wrote is written again by the ply that owns it)."""
+        keep = [t.clone() for t in self._persistent(st)]
+        graphs = capture_graphs(self.env.device, {None: functools.partial(self._ply, st)},
+                                functools.partial(self._ply, st, True))
+        for t, k in zip(self._persistent(st), keep):
+            t.copy_(k)
+        return graphs
+
+    @torch.no_grad()
+    def generate(self, episodes):
+        """Run global steps until ``episodes`` more games have been emitted into the ring (checked every
+        ``check_every`` steps, so a call may overshoot).  Returns {'episodes': emitted by this call, 'env_steps':
+        the sum of their lengths, 'plies': global steps run}."""
+        st = self._state()
+        session = (getattr(self.net, 'inference_session', None)
+                   if getattr(self.net, 'stateless_session', False) else None)
+        with eval_mode(self.net), session() if session is not None else contextlib.nullcontext():
+            return self._generate(st, int(episodes))
+
+    def _generate(self, st, episodes):
+        N = self.replay.N
+        graph = None
+        if self._use_graph():
+            # a captured step reads the net's parameters and buffers where they live: recapture if any moved (the
+            # games stay); the switch between the kernels and their torch formulation is part of the capture too
+            key = (FUSED_STREAM,) + params_key(self.net)
+            if self._graphs is None or self._graphs[0] != key:
+                self._graphs = (key, self._capture(st))
+            graph = self._graphs[1][None]
+        emitted0, steps0, s0 = self._emitted, self._steps, self.s
+        target = emitted0 + episodes
+        emitted = emitted0
+        while emitted < target:
+            for _ in range(self.check_every):
+                if graph is not None:
+                    graph.replay()
+                else:
+                    self._ply(st)
+                self.s += 1
+            emitted = int(st['state'][1])
+        ring_ptr, emitted, next_game = (int(v) for v in st['state'].tolist())
+        self._steps = int(st['played'].sum()) - int(st['ply'].sum())   # all plies played less the games in flight
+        self.replay.ptr = ring_ptr
+        self.replay.count = min(self.replay.count + emitted - emitted0, N)
+        self._emitted, self.games_started = emitted, next_game
+        if hasattr(self.env, 'next_game'):
+            self.env.next_game = next_game
         return {'episodes': emitted - emitted0, 'env_steps': self._steps - steps0, 'plies': self.s - s0}
 
 

@@ -156,6 +156,86 @@ int hrl_selfplay_harvest(const uint8_t *done, const hrl_selfplay_slots *slots, i
                          double gamma, const hrl_replay_ring *ring, int64_t *ring_game, int64_t *game,
                          uint8_t *pending, int64_t *state, void *stream);
 
+/* ---- The streaming generator for simultaneous-move envs (rollout.PlayerStreamGenerator): per-player records.
+ *
+ * Public sampling rules (pure-Python and torch twins in handyrl_amd/rollout.py), both Philox4x32-10 with key
+ * (seed & 0xffffffff, seed >> 32), counter (game & 0xffffffff, game >> 32, ply, w3) and the float mapping above,
+ * u = ((float)(x >> 9) + 0.5f) * 2^-23:
+ *   stream_player_uniforms: player p, label a uses w3 = 0x40000000 + p * ceil(A / 4) + a / 4, output word a % 4;
+ *   stream_select_uniform:  w3 = 0x80000000, output word 0 (the u that step_players takes).
+ * The last counter word keeps the streams of one (seed, game, ply) apart: the mover rule above takes a / 4
+ * (< 0x40000000), the Hungry Geese picks 0 and 1 (include/hrl_geese.h), eval_pick 0xffffffff, the player uniforms
+ * [0x40000000, 0x80000000) and the select uniform 0x80000000.  P * ceil(A / 4) must stay below 0x40000000. */
+
+/* The sampling and recording tail of the per-player ply in ONE launch, one wave per (game, player).
+ * logits (P * E, >= A) fp32 rows of stride logit_stride, player-major: row p * E + e; value (P * E,) fp32 likewise.
+ * legal: bytes, legal_player_stride == 0: (E, A), the same for every player; == A: (E, P, A).
+ * turns, infer (E, P) bytes; active (E,) bytes; game, ply (E,) int64.
+ *   m = legal ? 0 : 1e32;  p = logit - m;  a = argmax_a(p - log(-log(u)))  with u of stream_player_uniforms, the fp32
+ *   operations of hrl_selfplay_sample_record_stream and torch.argmax's tie order (NaN first, then the lowest label).
+ * A game is PLAYED when active[e] != 0 and 0 <= ply[e] < Tm.
+ *   action (E, P) int64: the sample where the game is played and turns is set, else 0; written for every (e, p).
+ *   usel (E,) fp32 = stream_select_uniform(seed, game[e], ply[e]); written for every game.
+ *   A played game stores slot (e, ply[e], p) of EVERY player p (the slot buffers outlive a game):
+ *     policy_buf, amask_buf (E, Tm, P, A) fp32, action_buf (E, Tm, P) int64, tmask_buf (E, Tm, P) bytes:
+ *       p, m, a, 1 where turns is set, else 0, 1e32, 0, 0;
+ *     value_buf (E, Tm, P) fp32, omask_buf (E, Tm, P) bytes: value, 1 where infer is set, else 0, 0.
+ *   A game that is not played stores nothing into the records.
+ * HRL_EINVAL (before any HIP call) for a NULL pointer, E < 0, P < 1, A < 1, A > 2^20, Tm < 1, logit_stride < A,
+ * legal_player_stride other than 0 or A, P * E or P * ceil(A / 4) of 0x40000000 or more; E == 0: HRL_OK, no launch. */
+int hrl_selfplay_sample_record_players_stream(const float *logits, int64_t logit_stride, const float *value,
+                                              const uint8_t *legal, int64_t legal_player_stride, const uint8_t *turns,
+                                              const uint8_t *infer, const uint8_t *active, uint64_t seed,
+                                              const int64_t *game, const int64_t *ply, int64_t E, int64_t P, int64_t A,
+                                              int64_t Tm, int64_t *action, float *usel, float *policy_buf,
+                                              float *amask_buf, int64_t *action_buf, float *value_buf,
+                                              uint8_t *tmask_buf, uint8_t *omask_buf, void *stream);
+
+/* The slot records of the per-player streaming generator, DEVICE pointers to C-contiguous tensors; the struct itself
+ * is HOST memory read before the call returns:
+ *   obs[l] (E, Tm, P, obs_width[l]) uint8 or fp32 per obs_type[l] (HRL_REPLAY_U8 / HRL_REPLAY_F32), l < nleaves <= 8
+ *   policy, amask (E, Tm, P, A) fp32     action (E, Tm, P) int64     value (E, Tm, P) fp32
+ *   tmask, omask (E, Tm, P) bytes 0/1    reward (E, Tm, P) fp64 or NULL (no reward) */
+typedef struct hrl_selfplay_player_slots {
+    int64_t E, Tm, P, A;
+    int32_t nleaves;
+    int32_t obs_type[HRL_REPLAY_MAX_LEAVES];
+    int64_t obs_width[HRL_REPLAY_MAX_LEAVES];
+    const void *obs[HRL_REPLAY_MAX_LEAVES];
+    const float *policy, *amask;
+    const int64_t *action;
+    const float *value;
+    const uint8_t *tmask, *omask;
+    const double *reward;
+} hrl_selfplay_player_slots;
+
+/* hrl_selfplay_harvest for per-player records: `ring` is a rollout.PlayerReplay (the PLAYERS layouts of
+ * hrl_replay.h: records (N, Tm, P, ...), tmask / omask required, turn ignored).  The contract is that entry's: done
+ * (E,) bytes, ply[e] the length L (clamped to [0, Tm]), c done slots, r(e) done slots below e, base = state[0]:
+ *   ring row (base + r) mod N receives the whole episode of slot e, in slot order, without atomics; when c > N the
+ *   highest slot that claims a row wins;
+ *     plies t < L   the slot's records; an observation leaf converted as src.to(dst.dtype) does for each of the four
+ *                   U8 / F32 pairs ((uint8)x for x in [0, 255], (float)b), the reward narrowed to fp32, ret[t] =
+ *                   reward[t] + gamma * ret[t+1] per player in fp64 from t = L-1 down, stored as fp32;
+ *     plies t >= L  the reset values: obs 0, policy 0, amask 1e32, action, value, tmask, omask, reward, ret 0;
+ *     length = L, outcome = outcome[e] ((E, P) fp32), ring_game[row] = game[e]  (ring_game (N,) int64);
+ *   the slot records are READ for t < L only (a Hungry Geese slot is 1 MB and the mean game a few plies), the
+ *   rest of the row is stores of the reset values.
+ * The second launch (one workgroup) is hrl_selfplay_harvest's: game[e] = state[2] + r, ply[e] = 0, pending[e] = 1
+ * for the done slots, state = {ring_ptr, emitted, next_game} becomes {(base + c) mod N, emitted + c, next_game + c}.
+ * A call with no done slot changes nothing.  slots->reward NULL: the ring's reward and ret get zeros.
+ * 16-byte accesses are used only where the record's size per slot and both bases make them aligned for every slot
+ * and row (then 4-byte ones under the same rule, else single elements); the reset values of a row are stored 16 bytes
+ * at a time between the row's unaligned edges.  Offsets are formed in 64 bits.
+ * HRL_EINVAL (before any HIP call) for: a NULL done / slots / ply / outcome / ring / ring_game / game / pending /
+ * state; E < 0; Tm, P, A or N < 1; ring Tm, P, A or leaf count / widths other than the slots'; nleaves not in [1, 8];
+ * an obs_type (slots or ring) other than HRL_REPLAY_U8 / HRL_REPLAY_F32; an obs_width < 1; a NULL required record
+ * (all but slots->reward and ring->turn); a record of 2^31 elements or more per slot.  E == 0 passes the same
+ * validation, returns HRL_OK and launches nothing. */
+int hrl_selfplay_harvest_players(const uint8_t *done, const hrl_selfplay_player_slots *slots, int64_t *ply,
+                                 const float *outcome, double gamma, const hrl_replay_ring *ring, int64_t *ring_game,
+                                 int64_t *game, uint8_t *pending, int64_t *state, void *stream);
+
 /* Masked row copy for the movers' recurrent state (generation.py:38-41: only the mover's hidden state
  * advances): for each of nleaves (<= 16) fp32 tensors, row e of dst[l] (E rows of F[l] contiguous floats,
  * row stride dst_stride[l] elements) becomes row e of src[l] where mask[e] != 0; other rows are untouched.

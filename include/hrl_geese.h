@@ -58,6 +58,19 @@ int hrl_geese_observe(const uint8_t *body, const uint8_t *hd, const uint8_t *len
                       const int8_t *prev, float *views, float *record, const int64_t *t, const uint8_t *infer,
                       int64_t E, int64_t P, int64_t Tm, void *stream);
 
+/* hrl_geese_observe for the streaming per-player generator (rollout.PlayerStreamGenerator): every game records at
+ * its own ply index ply[e] ((E,) int64, device memory) and the record is UINT8 (the planes are binary), (E, Tm, 4,
+ * 17, 7, 11) bytes.  views (4, E, 17, 7, 11) float is written for every game, as above.  For a game with
+ * active[e] != 0 and 0 <= ply[e] < Tm, slot (e, ply[e], p) gets view p where infer[e * 4 + p] is set and ZEROS where
+ * it is not (the slot buffers outlive a game: a dead goose's slot must not keep an earlier game's planes); a game
+ * with active[e] == 0 or a ply outside [0, Tm) stores nothing into the record.  One wave per (game, view); a view is
+ * 1309 bytes, so a slot starts at any byte phase of a 16-byte line: single bytes up to the first aligned one, 16-byte
+ * stores, then the tail.  All pointers required; HRL_EINVAL (before any HIP call) for a NULL one, E < 0, P != 4 or
+ * Tm < 1; E == 0: HRL_OK, no launch. */
+int hrl_geese_observe_at(const uint8_t *body, const uint8_t *hd, const uint8_t *len, const int8_t *food,
+                         const int8_t *prev, float *views, uint8_t *record, const int64_t *ply, const uint8_t *infer,
+                         const uint8_t *active, int64_t E, int64_t P, int64_t Tm, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
