@@ -14,6 +14,10 @@
 // Nothing is recorded but the result, so the ply costs two launches besides the env's and the net's.  The rules are
 // public (include/hrl_env.h); evaluation.py holds the torch formulation the kernels equal bit for bit.
 // masked_rows_fill_kernel zeroes a restarting slot's recurrent-state rows (the twin of hrl_masked_rows_copy).
+// evaluation.PlayerEvaluator plays a simultaneous-move env (Hungry Geese) the same way with
+//   players_act_kernel   one wave per (slot, player): every player decides in the one launch -- the home net on
+//                        seat(g), a second net or eval_pick_player on the others -- from relative-seat-major logits;
+// the finish is eval_finish_kernel unchanged.
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -34,10 +38,11 @@ struct EvalTrace {   // all four or none (action NULL: no trace)
 };
 
 // A net's move for one slot (the whole wave): p = logits - (legal ? 0 : 1e32) goes to pol when pol is given; the
-// argmax of p, or at inv_t > 0 the Gumbel-max over p * inv_t, under better().
+// argmax of p, or at inv_t > 0 the Gumbel-max over p * inv_t, under better().  Label j draws its uniform from the
+// Philox call with last counter word w3 + j / 4 (w3 = 0: the mover rule; the players' rule has its own base).
 __device__ __forceinline__ int net_pick(const float *__restrict__ lg, const uint8_t *__restrict__ lm, float *pol,
                                         int A, float inv_t, uint32_t k0, uint32_t k1, uint32_t g0, uint32_t g1,
-                                        uint32_t tw, int lane) {
+                                        uint32_t tw, uint32_t w3, int lane) {
     float best = 0.0f;
     int ib = A;   // no label yet
     for (int j = lane; j < A; j += kWave) {
@@ -45,7 +50,7 @@ __device__ __forceinline__ int net_pick(const float *__restrict__ lg, const uint
         const float p = lg[j] - m;
         float v = p;
         if (inv_t > 0.0f) {   // Gumbel-max over p / temperature: the fp32 operations of the streaming tail
-            const uint32_t x = philox_word(k0, k1, g0, g1, tw, (uint32_t)(j >> 2), j & 3);
+            const uint32_t x = philox_word(k0, k1, g0, g1, tw, w3 + (uint32_t)(j >> 2), j & 3);
             const float u = ((float)(x >> 9) + 0.5f) * 0x1p-23f;
             v = p * inv_t - logf(-logf(u));
         }
@@ -67,15 +72,16 @@ __device__ __forceinline__ int net_pick(const float *__restrict__ lg, const uint
 }
 
 // eval_pick for one slot (the whole wave): n legal labels by ballot and popcount, k = (w * n) >> 23, the k-th by
-// prefix count; 0 for a row without a legal label.
+// prefix count; 0 for a row without a legal label.  (c3, word) name the Philox word: (0xffffffff, 0) is eval_pick,
+// (0xffffffff - (player >> 2), player & 3) eval_pick_player.
 __device__ __forceinline__ int random_pick(const uint8_t *__restrict__ lm, int A, uint32_t k0, uint32_t k1,
-                                           uint32_t g0, uint32_t g1, uint32_t tw, int lane) {
+                                           uint32_t g0, uint32_t g1, uint32_t tw, uint32_t c3, int word, int lane) {
     int64_t n = 0;
     for (int j0 = 0; j0 < A; j0 += kWave) {
         const int j = j0 + lane;
         n += __popcll(__ballot(j < A && lm[j] != 0));
     }
-    const uint64_t w = philox_word(k0, k1, g0, g1, tw, 0xffffffffu, 0) >> 9;
+    const uint64_t w = philox_word(k0, k1, g0, g1, tw, c3, word) >> 9;
     int64_t k = (int64_t)((w * (uint64_t)n) >> 23);   // < n
     for (int j0 = 0; j0 < A && n > 0; j0 += kWave) {
         const int j = j0 + lane;
@@ -131,10 +137,78 @@ __global__ __launch_bounds__(kWave *kSlotsPerBlock) void match_act_kernel(
     if (lg) {
         float *pol = tr.action ? tr.policy + (g * Tm + t) * A : nullptr;
         if (t >= opening || pol)
-            pick = net_pick(lg, lm, pol, A, model ? inv_t_home : inv_t_opp, k0, k1, g0, g1, tw, lane);
+            pick = net_pick(lg, lm, pol, A, model ? inv_t_home : inv_t_opp, k0, k1, g0, g1, tw, 0u, lane);
     }
-    if (!lg || t < opening) pick = random_pick(lm, A, k0, k1, g0, g1, tw, lane);
+    if (!lg || t < opening) pick = random_pick(lm, A, k0, k1, g0, g1, tw, 0xffffffffu, 0, lane);
     if (lane == 0) store_move(forced, g * Tm + t, pick, model, action + e, tr);
+}
+
+// ---- simultaneous-move envs (evaluation.PlayerEvaluator): every player of every slot decides in the one launch ----
+constexpr uint32_t kPlayerW3 = 0x40000000u, kSelectW3 = 0x80000000u;   // include/hrl_env.h: the counter's last word
+
+struct PlayersTrace {   // all four or none (action NULL: no trace)
+    int64_t *action, *picked;
+    float *policy;
+    uint8_t *alive;
+};
+
+// One wave per (slot, player), lanes over the A labels.  Player p of slot e sits k = (p - seat[e]) mod P seats after the
+// home net: k = 0 reads row e of home, k >= 1 row (k - 1) * E + e of opp (or has no net: opp NULL).  Everything that
+// branches is wave-uniform.
+__global__ __launch_bounds__(kWave *kSlotsPerBlock) void players_act_kernel(
+    const float *__restrict__ home, int64_t hstride, const float *__restrict__ opp, int64_t ostride,
+    const uint8_t *__restrict__ legal, int64_t lpstride, const uint8_t *__restrict__ turns, uint32_t k0, uint32_t k1,
+    float inv_t_home, float inv_t_opp, int64_t opening, const int64_t *__restrict__ game,
+    const int64_t *__restrict__ ply, const uint8_t *__restrict__ active, const int64_t *__restrict__ seat,
+    const int64_t *__restrict__ forced, int64_t E, int P, int A, int64_t Tm, int64_t G, int64_t *__restrict__ action,
+    float *__restrict__ usel, PlayersTrace tr) {
+    const int lane = threadIdx.x % kWave;
+    const int64_t w = (int64_t)blockIdx.x * kSlotsPerBlock + threadIdx.x / kWave;   // the pair e * P + p
+    if (w >= E * P) return;
+    const int64_t e = w / P;
+    const int p = (int)(w - e * P);
+    const int64_t t = ply[e], g = game[e];
+    const uint32_t g0 = (uint32_t)(uint64_t)g, g1 = (uint32_t)((uint64_t)g >> 32), tw = (uint32_t)(uint64_t)t;
+    if (p == 0 && lane == 0)
+        usel[e] = ((float)(philox_word(k0, k1, g0, g1, tw, kSelectW3, 0) >> 9) + 0.5f) * 0x1p-23f;
+    if (!active[e] || t < 0 || t >= Tm || g < 0 || g >= G) {
+        if (lane == 0) action[w] = 0;
+        return;
+    }
+    const int64_t s = (g * Tm + t) * P + p;
+    if (!turns[w]) {   // the player does not move: no decision, the trace says so
+        if (lane == 0) {
+            action[w] = 0;
+            if (tr.action) {
+                tr.action[s] = -1;
+                tr.picked[s] = -1;
+                tr.alive[s] = 0;
+            }
+        }
+        return;
+    }
+    const int k = (int)((((int64_t)p - seat[e]) % P + P) % P);
+    const uint8_t *lm = legal + e * (lpstride ? (int64_t)P * A : (int64_t)A) + p * lpstride;
+    const float *lg = k == 0 ? home + e * hstride : opp ? opp + ((int64_t)(k - 1) * E + e) * ostride : nullptr;
+    int pick = 0;
+    if (lg) {
+        float *pol = tr.action ? tr.policy + s * A : nullptr;
+        if (t >= opening || pol)
+            pick = net_pick(lg, lm, pol, A, k == 0 ? inv_t_home : inv_t_opp, k0, k1, g0, g1, tw,
+                            kPlayerW3 + (uint32_t)p * (uint32_t)((A + 3) >> 2), lane);
+    }
+    if (!lg || t < opening)
+        pick = random_pick(lm, A, k0, k1, g0, g1, tw, 0xffffffffu - (uint32_t)(p >> 2), p & 3, lane);
+    if (lane == 0) {
+        const int64_t f = forced ? forced[s] : -1;
+        const int64_t a = f >= 0 ? f : pick;
+        action[w] = a;
+        if (tr.action) {
+            tr.action[s] = a;
+            tr.picked[s] = pick;
+            tr.alive[s] = 1;
+        }
+    }
 }
 
 // One workgroup; thread k owns the slots [k * chunk, (k + 1) * chunk).  Every store is a plain vector store.
@@ -243,6 +317,35 @@ int hrl_match_act(const float *logits_home, int64_t stride_home, const float *lo
                        static_cast<hipStream_t>(stream), logits_home, stride_home, logits_opp, stride_opp, legal,
                        (uint32_t)seed, (uint32_t)(seed >> 32), inv_home, inv_opp, opening, game, ply, active, seat,
                        mover, forced, E, (int)A, Tm, G, action, tr);
+    const hipError_t err = hipGetLastError();
+    return err == hipSuccess ? HRL_OK : HRL_ELAUNCH_BASE - (int)err;
+}
+
+int hrl_players_act(const float *logits_home, int64_t stride_home, const float *logits_opp, int64_t stride_opp,
+                    const uint8_t *legal, int64_t legal_player_stride, const uint8_t *turns, uint64_t seed,
+                    double temperature_home, double temperature_opp, int64_t opening, const int64_t *game,
+                    const int64_t *ply, const uint8_t *active, const int64_t *seat, const int64_t *forced, int64_t E,
+                    int64_t P, int64_t A, int64_t Tm, int64_t G, int64_t *action, float *usel,
+                    int64_t *trace_action, int64_t *trace_picked, float *trace_policy, uint8_t *trace_alive,
+                    void *stream) {
+    const int ntrace = (trace_action != nullptr) + (trace_picked != nullptr) + (trace_policy != nullptr) +
+                       (trace_alive != nullptr);
+    if (!logits_home || !legal || !turns || !game || !ply || !active || !seat || !action || !usel || E < 0 || P < 1 ||
+        A < 1 || A > (1 << 20) || Tm < 1 || G < 0 || stride_home < A || (logits_opp && stride_opp < A) ||
+        (legal_player_stride != 0 && legal_player_stride != A) || !(temperature_home >= 0.0) ||
+        !(temperature_opp >= 0.0) || opening < 0 || (ntrace != 0 && ntrace != 4))
+        return HRL_EINVAL;
+    constexpr int64_t kLimit = 0x40000000;
+    if (P >= kLimit || E >= kLimit || P * E >= kLimit || P * ((A + 3) / 4) >= kLimit) return HRL_EINVAL;
+    if (E == 0) return HRL_OK;
+    const float inv_home = temperature_home > 0.0 ? (float)(1.0 / temperature_home) : 0.0f;
+    const float inv_opp = temperature_opp > 0.0 ? (float)(1.0 / temperature_opp) : 0.0f;
+    PlayersTrace tr{trace_action, trace_picked, trace_policy, trace_alive};
+    const int blocks = (int)((E * P + kSlotsPerBlock - 1) / kSlotsPerBlock);
+    hipLaunchKernelGGL(players_act_kernel, dim3(blocks), dim3(kWave * kSlotsPerBlock), 0,
+                       static_cast<hipStream_t>(stream), logits_home, stride_home, logits_opp, stride_opp, legal,
+                       legal_player_stride, turns, (uint32_t)seed, (uint32_t)(seed >> 32), inv_home, inv_opp, opening,
+                       game, ply, active, seat, forced, E, (int)P, (int)A, Tm, G, action, usel, tr);
     const hipError_t err = hipGetLastError();
     return err == hipSuccess ? HRL_OK : HRL_ELAUNCH_BASE - (int)err;
 }

@@ -15,6 +15,7 @@
 //   observe_at  the same views for the streaming per-player generator: the record is uint8 (a quarter of the bytes),
 //            addressed by a per-game ply, and every player's slot of an active game is written -- zeros where the
 //            player does not infer.  A 1309-byte view starts at any byte phase: bytes, 16-byte stores, bytes.
+//   observe_seats  the evaluator's rows: K waves per game, wave k = the view of goose (seat + k) mod 4, no record.
 // Every value is written with ordinary vector stores in plain C++.
 
 #include <hip/hip_runtime.h>
@@ -316,6 +317,21 @@ observe_at_kernel(const uint8_t *body, const uint8_t *hd, const uint8_t *len, co
     store_view_u8(record + ((e * Tm + tt) * kGeese + p) * kView, pm, lane, infer[e * kGeese + p] ? 1u : 0u);
 }
 
+// observe_kernel for the evaluator (evaluation.PlayerEvaluator): K waves per game, wave k = the view of goose
+// (seat[e] + k) mod 4 into row k * E + e -- the forward's rows in relative-seat order, and nothing else.
+__global__ void __launch_bounds__(256)
+observe_seats_kernel(const uint8_t *body, const uint8_t *hd, const uint8_t *len, const int8_t *food,
+                     const int8_t *prev, const int64_t *seat, float *rows, int64_t E) {
+    __shared__ uint64_t planes[kGeese][kPlanes][2];
+    const int64_t e = blockIdx.x;                     // grid = E blocks of K waves: no thread is out of range
+    const int k = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+    const int p = (int)((seat[e] + k) & (kGeese - 1));   // two's complement: in [0, 4) for any seat
+    uint64_t (*pm)[2] = planes[k];
+    build_planes(body, hd, len, food, prev, e, p, lane, pm);
+    __syncthreads();
+    store_view(rows + ((int64_t)k * E + e) * kView, pm, lane);
+}
+
 inline int grid_for(int64_t n) { return (int)((n + 255) / 256); }
 
 inline int launched() {
@@ -372,6 +388,18 @@ int hrl_geese_observe_at(const uint8_t *body, const uint8_t *hd, const uint8_t *
     if (E == 0) return HRL_OK;
     hipLaunchKernelGGL(observe_at_kernel, dim3((unsigned)E), dim3(256), 0, static_cast<hipStream_t>(stream), body, hd,
                        len, food, prev, views, record, ply, infer, active, E, Tm);
+    return launched();
+}
+
+int hrl_geese_observe_seats(const uint8_t *body, const uint8_t *hd, const uint8_t *len, const int8_t *food,
+                            const int8_t *prev, const int64_t *seat, float *rows, int64_t E, int64_t P, int64_t K,
+                            void *stream) {
+    if (!body || !hd || !len || !food || !prev || !seat || !rows || E < 0 || E > 0x7fffffff || P != kGeese || K < 1 ||
+        K > kGeese)
+        return HRL_EINVAL;
+    if (E == 0) return HRL_OK;
+    hipLaunchKernelGGL(observe_seats_kernel, dim3((unsigned)E), dim3((unsigned)(kWave * K)), 0,
+                       static_cast<hipStream_t>(stream), body, hd, len, food, prev, seat, rows, E);
     return launched();
 }
 

@@ -319,6 +319,7 @@ class HungryGeeseBatch:
     OBS_SHAPE = (PLANES, ROWS, COLS)
     SIMULTANEOUS = True
     ALTERNATING = False
+    PLAYER_EVAL = True     # evaluation.player_eval_env: the entry points evaluate it with PlayerEvaluator
 
     def __init__(self, E, device, seed=0):
         self.E, self.device = E, device
@@ -462,6 +463,23 @@ class HungryGeeseBatch:
     def observation(self, player):
         """(E, 17, 7, 11): game e seen by goose player[e]."""
         return self._views()[player.long(), torch.arange(self.E, device=self.device)]
+
+    def observe_seats(self, seat, K):
+        """The evaluator's forward rows (K * E, 17, 7, 11), relative-seat-major: row k * E + e is game e seen by goose
+        (seat[e] + k) mod 4, k < K (``evaluation.PlayerEvaluator``: K = 1 forwards the home seat only, K = 4 feeds
+        rows[:E] to the home net and rows[E:] to the opponent).  One launch, nothing recorded."""
+        E, K = self.E, int(K)
+        seat = seat.to(torch.long).contiguous()
+        assert seat.shape == (E,) and 1 <= K <= GEESE
+        if self._hip():
+            self._state_ok()
+            rows = torch.empty(K, E, *self.OBS_SHAPE, device=self.device)
+            self._native('hrl_geese_observe_seats', self.body, self.head, self.length, self.food, self.prev, seat,
+                         rows, E, self.P, K)
+            return rows.view(K * E, *self.OBS_SHAPE)
+        rows = np.stack([np.stack([observation_of(g, (int(s) + k) % GEESE) for g, s in zip(self._games, seat.tolist())])
+                         for k in range(K)]) if E else np.zeros((K, 0, *self.OBS_SHAPE), dtype=np.float32)
+        return torch.from_numpy(rows).view(K * E, *self.OBS_SHAPE)
 
     def observe_players_record(self, rec, t, infer):
         """All four views of every game as the forward's (4 * E, 17, 7, 11) input rows, player-major, and in the

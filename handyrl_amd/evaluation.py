@@ -27,6 +27,11 @@ A league (``LeagueEvaluator``, ``main.py --eval-league``) plays a round robin of
 those of the match above, with each net forwarded only over the rows where it moves, and rates the agents with
 ``bradley_terry``; include/hrl_env.h has its rules.
 
+A simultaneous-move env (Hungry Geese; ParallelTicTacToe at class level) has no mover: ``PlayerEvaluator`` seats the
+home net on ``g mod P`` and random agents (``eval_pick_player``) or a second net on ALL other seats, decides for every
+player in one launch (hrl_players_act) and restarts a finished slot on the very next step; include/hrl_env.h has its
+rules.
+
 ``FUSED_EVAL``: on a GPU the ply's decision and bookkeeping are the launches of hrl_match_act (the one decision
 kernel; hrl_eval_act is its form without an opponent and opening plies), hrl_eval_finish and hrl_masked_rows_fill
 (csrc/hrl_eval.hip); the torch formulation below is the CPU path and the form the kernels are tested against.
@@ -40,15 +45,20 @@ import os
 import numpy as np
 import torch
 
-from .rollout import (_M32, _PHILOX_M, _PHILOX_W, _leaves, capture_graphs, eval_mode, graph_wanted, params_key,
-                      philox4x32, stream_uniforms_torch)
+from .rollout import (_M32, _PHILOX_M, _PHILOX_W, _leaves, _philox_torch, _player_blocks, _stack_views,
+                      capture_graphs, eval_mode, graph_wanted, params_key, philox4x32, stream_player_uniforms_torch,
+                      stream_select_uniform_torch, stream_uniforms_torch)
 from .util import map_r
 
 __all__ = ['DeviceEvaluator', 'eval_pick', 'eval_pick_torch', 'eval_main', 'eval_match_main', 'wp_func', 'eval_games',
-           'batched_env', 'LeagueEvaluator', 'bradley_terry', 'eval_league_main']
+           'batched_env', 'LeagueEvaluator', 'bradley_terry', 'eval_league_main', 'PlayerEvaluator', 'eval_pick_player',
+           'eval_pick_player_torch', 'player_eval_env']
 
 # True: on a GPU the three steps are HIP launches; False (or a CPU env): the torch ops below, bit-identical.
 FUSED_EVAL = True
+# PlayerEvaluator's decision (hrl_players_act; the finish is hrl_eval_finish): True: HIP launches on a GPU; False (or a
+# CPU env): players_act_torch and finish_torch.
+FUSED_PLAYER_EVAL = True
 # The league's own two steps (hrl_league_finish, hrl_rows_permute; csrc/hrl_league.hip) and its use of hrl_match_act
 # and hrl_masked_rows_fill: True: HIP launches on a GPU; False (or a CPU env): league_finish_torch, rows_permute_torch.
 FUSED_LEAGUE = True
@@ -90,6 +100,40 @@ def eval_pick_torch(seed, game, ply, legal):
     return hit.long().argmax(-1)
 
 
+def eval_pick_player(seed, game, ply, player, legal):
+    """The random agent's move for ``player`` at ply ``ply`` of game number ``game`` in a simultaneous-move env, where
+    every player needs a word of its own at one (game, ply): ``eval_pick``'s integer rule on output word
+    ``player & 3`` of the Philox call with last counter word ``0xffffffff - (player >> 2)``.  Player 0 is ``eval_pick``
+    itself; the words stay apart from the Geese picks (0, 1), ``rollout.stream_player_uniforms`` [0x40000000,
+    0x80000000) and ``rollout.stream_select_uniform`` (0x80000000)."""
+    seed = int(seed) & 0xffffffffffffffff
+    game = int(game) & 0xffffffffffffffff
+    player = int(player)
+    labels = [a for a, ok in enumerate(legal) if ok]
+    x = int(philox4x32((game & _M32, game >> 32, int(ply) & _M32, _PICK_WORD - (player >> 2)),
+                       (seed & _M32, seed >> 32))[player & 3])
+    return labels[((x >> 9) * len(labels)) >> 23]
+
+
+def eval_pick_player_torch(seed, game, ply, P, legal):
+    """``eval_pick_player`` for E slots and P players as torch ops: game, ply (E,) int64, legal (E, A) or (E, P, A)
+    bool -> (E, P) int64 (0 for a row without a legal label)."""
+    seed = int(seed) & 0xffffffffffffffff
+    E, A = game.shape[0], legal.shape[-1]
+    p = torch.arange(P, device=game.device).view(1, P)
+    shape = (E, P)
+    c = _philox_torch(seed, (game & _M32).view(E, 1).expand(shape), ((game >> 32) & _M32).view(E, 1).expand(shape),
+                      (ply & _M32).view(E, 1).expand(shape), (_PICK_WORD - (p >> 2)).expand(shape))
+    w = p & 3
+    x = torch.where(w == 0, c[0], torch.where(w == 1, c[1], torch.where(w == 2, c[2], c[3])))
+    if legal.dim() == 2:
+        legal = legal.view(E, 1, A).expand(E, P, A)
+    n = legal.sum(-1)
+    k = ((x >> 9) * n) >> 23
+    hit = legal & (torch.cumsum(legal.long(), -1) == (k + 1).unsqueeze(-1))
+    return hit.long().argmax(-1)
+
+
 def wp_func(results):
     """The reference's win rate of a {outcome: count} table (evaluation.py:139-144): sum (o + 1) / 2 over games."""
     games = sum(v for k, v in results.items() if k is not None)
@@ -112,13 +156,24 @@ def batched_env(module):
     return cls
 
 
+def player_eval_env(module):
+    """The batched twin ``PlayerEvaluator`` plays at the entry points (``eval_rate``, ``--eval``, ``--eval-match``)
+    for the env module ``module``: the class marked ``PLAYER_EVAL`` (Hungry Geese), or None -- every other env goes
+    through ``batched_env`` and the alternating evaluators."""
+    from .main import _batched_envs
+    cls = _batched_envs().get(module)
+    return cls if getattr(cls, 'PLAYER_EVAL', False) else None
+
+
 def _check_env(cls, name=None):
     if cls is None:
         raise ValueError('device evaluation needs a batched (device) form of the env; %r has none' % (name,))
     if getattr(cls, 'SIMULTANEOUS', False) or not getattr(cls, 'ALTERNATING', False):
         raise ValueError('device evaluation plays alternating-move envs (TicTacToe, Geister, CIGeister): %s is a '
-                         'simultaneous-move env, where every player moves at every ply'
-                         % (getattr(cls, '__name__', None) or type(cls).__name__))
+                         'simultaneous-move env, where every player moves at every ply%s'
+                         % (getattr(cls, '__name__', None) or type(cls).__name__,
+                            ' (PlayerEvaluator plays it: eval_simultaneous: true in train_args, --eval, --eval-match)'
+                            if getattr(cls, 'PLAYER_EVAL', False) else ''))
 
 
 # ---- the three steps as torch ops (the CPU path; the kernels equal them bit for bit) ----
@@ -280,6 +335,103 @@ def finish_hip(st, terminal, outcome, G, outcome_out, length_out):
         _native.stream_of(terminal.device)), 'hrl_eval_finish')
 
 
+def players_act_torch(st, logits_home, logits_opp, legal, turns, seed, temperature_home, temperature_opp, opening, G,
+                      forced=None, trace=None):
+    """hrl_players_act, the decision of ``PlayerEvaluator``: every player of every slot in one go.  ``logits_home``
+    (E, >= A) and ``logits_opp`` ((P - 1) * E, >= A) or None are relative-seat-major: row (k - 1) * E + e of the
+    opponent belongs to player (seat[e] + k) mod P; ``legal`` (E, A) or (E, P, A); ``turns`` (E, P) bool.  Returns the
+    actions (E, P) (0 for an inactive slot and for a player that does not move) and the select uniforms (E,);
+    ``trace`` (dict or None) gets the records."""
+    game, ply, active, seat = st['game'], st['ply'], st['active'], st['seat']
+    E, P = turns.shape
+    A, Tm, dev = legal.shape[-1], st['Tm'], turns.device
+    ok = active & (ply >= 0) & (ply < Tm) & (game >= 0) & (game < G)
+    if legal.dim() == 2:
+        legal = legal.view(E, 1, A).expand(E, P, A)
+    m = torch.where(legal, 0.0, 1e32)
+    players = torch.arange(P, device=dev).view(1, P).expand(E, P)
+    k = (players - seat.view(E, 1)) % P                                      # the relative seat, >= 0
+    home = k == 0
+    lg = logits_home[:, :A].float().view(E, 1, A).expand(E, P, A)
+    has_net = home
+    if logits_opp is not None:
+        opp = logits_opp[:, :A].float().reshape(P - 1, E, A)
+        rows = torch.arange(E, device=dev).view(E, 1).expand(E, P)
+        lg = torch.where(home.unsqueeze(-1), lg, opp[(k - 1).clamp(min=0), rows])
+        has_net = torch.ones_like(home)
+    p = lg - m
+    u = None
+    if temperature_home > 0 or (logits_opp is not None and temperature_opp > 0):
+        u = stream_player_uniforms_torch(seed, game, ply, P, A)
+
+    def net(temperature):
+        v = p
+        if temperature > 0:
+            v = p * float(np.float32(1.0 / temperature)) - torch.log(-torch.log(u))
+        return torch.argmax(v, dim=-1)
+
+    pick = net(temperature_home)
+    if logits_opp is not None and temperature_opp != temperature_home:
+        pick = torch.where(home, pick, net(temperature_opp))
+    rand = eval_pick_player_torch(seed, game, ply, P, legal)
+    pick = torch.where(has_net & (ply >= opening).view(E, 1), pick, rand)
+    moves = turns & ok.view(E, 1)
+    g = torch.where(ok, game, G)
+    t = torch.where(ok, ply, 0)
+    a = pick
+    if forced is not None:
+        f = forced[g, t]
+        a = torch.where(f >= 0, f, pick)
+    a = torch.where(moves, a, 0)
+    if trace is not None:
+        trace['action'][g, t] = torch.where(moves, a, -1)
+        trace['picked'][g, t] = torch.where(moves, pick, -1)
+        trace['alive'][g, t] = moves
+        trace['policy'][torch.where(moves & has_net, g.view(E, 1), G), t.view(E, 1).expand(E, P), players] = p
+    return a, stream_select_uniform_torch(seed, game, ply)
+
+
+def players_act_hip(st, logits_home, logits_opp, legal, turns, seed, temperature_home, temperature_opp, opening, G,
+                    forced=None, trace=None):
+    """players_act_torch as ONE launch (hrl_players_act, one wave per (slot, player))."""
+    from . import _native
+    E, P = turns.shape
+    A, Tm = legal.shape[-1], st['Tm']
+    _player_blocks(P, A)
+    legal, turns = legal.contiguous(), turns.contiguous()
+    assert legal.dtype == torch.bool and legal.shape in ((E, A), (E, P, A)) and turns.dtype == torch.bool
+    rows = [logits_home, logits_opp]
+    for i, (logits, n) in enumerate(zip(rows, (E, (P - 1) * E))):
+        if logits is not None:
+            logits = logits.float()
+            if logits.stride(1) != 1:
+                logits = logits.contiguous()
+            assert logits.shape[0] == n and logits.shape[1] >= A
+            rows[i] = logits
+    for key in ('game', 'ply', 'seat'):
+        assert st[key].shape == (E,) and st[key].dtype == torch.long and st[key].is_contiguous()
+    assert st['active'].shape == (E,) and st['active'].dtype == torch.bool and st['P'] == P
+    if forced is not None:
+        assert forced.dtype == torch.long and forced.is_contiguous() and forced.shape[0] >= G
+        assert forced.shape[1:] == (Tm, P)
+    tr = [None] * 4
+    if trace is not None:
+        tr = [trace[key] for key in ('action', 'picked', 'policy', 'alive')]
+        assert all(x.is_contiguous() and x.shape[0] >= G and x.shape[1:3] == (Tm, P) for x in tr)
+        assert tr[0].dtype == tr[1].dtype == torch.long and tr[2].dtype == torch.float32 and tr[2].shape[3] == A
+        assert tr[3].dtype == torch.bool
+    home, opp = rows
+    a = torch.empty(E, P, dtype=torch.long, device=legal.device)
+    usel = torch.empty(E, device=legal.device)
+    _native.check(_native.load().hrl_players_act(
+        _native.ptr(home), home.stride(0), _native.ptr(opp), 0 if opp is None else opp.stride(0), _native.ptr(legal),
+        A if legal.dim() == 3 else 0, _native.ptr(turns), int(seed) & 0xffffffffffffffff, float(temperature_home),
+        float(temperature_opp), int(opening), _native.ptr(st['game']), _native.ptr(st['ply']),
+        _native.ptr(st['active']), _native.ptr(st['seat']), _native.ptr(forced), E, P, A, Tm, G, _native.ptr(a),
+        _native.ptr(usel), *[_native.ptr(x) for x in tr], _native.stream_of(legal.device)), 'hrl_players_act')
+    return a, usel
+
+
 def rows_fill_torch(leaves, mask):
     """Rows e with mask[e] of every leaf (E, ...) become 0."""
     for h in leaves:
@@ -387,10 +539,17 @@ class _PlyEvaluator:
     (``rollout.capture_graphs``), the replay loop that reads the device state every ``check_every`` steps, and the
     nets' eval mode and inference sessions around a call.  A subclass has ``_state()``, ``_begin(st, run)`` (every
     buffer as at the start of a call) and ``_ply(st, run, mover)`` (one global step), and keeps its run in
-    ``_run``: {'key', 'G', 'graphs', ...}."""
+    ``_run``: {'key', 'G', 'graphs', ...}.  ``_movers(st)`` is the period of the mover (P; 1 where every player moves
+    every ply: one graph) and ``_check_env_batch`` what the class can play."""
+
+    _check_env_batch = staticmethod(lambda env_batch: _check_env(type(env_batch)))
+
+    @staticmethod
+    def _movers(st):
+        return st['P']
 
     def __init__(self, env_batch, observation, temperature, opening_plies, seed, check_every, graph):
-        _check_env(type(env_batch))
+        self._check_env_batch(env_batch)
         if not temperature >= 0:
             raise ValueError('temperature must be >= 0, not %r' % (temperature,))
         if int(opening_plies) < 0:
@@ -413,12 +572,12 @@ class _PlyEvaluator:
         warm-up and capture leave no trace."""
         self._begin(st, run)
         return capture_graphs(self.env.device,
-                              {m: functools.partial(self._ply, st, run, m) for m in range(st['P'])})
+                              {m: functools.partial(self._ply, st, run, m) for m in range(self._movers(st))})
 
     def _play(self, st, run, slots, target, unfinished):
         """Global steps until ``target`` games are finished; ``slots``: the slots one stream of game numbers 0 .. G-1
         is played on; ``unfinished``: the error's text for (target, steps)."""
-        G, P = run['G'], st['P']
+        G, P, M = run['G'], st['P'], self._movers(st)
         if G == 0:
             return 0
         self._begin(st, run)
@@ -428,9 +587,9 @@ class _PlyEvaluator:
         while True:
             for _ in range(self.check_every):
                 if graphs is not None:
-                    graphs[s % P].replay()
+                    graphs[s % M].replay()
                 else:
-                    self._ply(st, run, s % P)
+                    self._ply(st, run, s % M)
                 s += 1
             if int(st['state'][0]) >= target:
                 return s
@@ -632,6 +791,198 @@ class DeviceEvaluator(_PlyEvaluator):
     def set_opponent_state(self, state_dict):
         """Copy weights and buffers into the opponent IN PLACE (no tensor is replaced), so the captured graphs, which
         address them, stay valid."""
+        self.opponent.load_state_dict(state_dict)
+
+
+def _check_player_env(env_batch):
+    if not getattr(env_batch, 'SIMULTANEOUS', False):
+        raise ValueError('PlayerEvaluator plays simultaneous-move envs (Hungry Geese, ParallelTicTacToe), where every '
+                         'player moves at every ply: %s is played by DeviceEvaluator' % type(env_batch).__name__)
+
+
+class PlayerEvaluator(_PlyEvaluator):
+    """``DeviceEvaluator`` for simultaneous-move envs (``SIMULTANEOUS``: HungryGeeseBatch, ParallelTicTacToeBatch):
+    plays game numbers 0 .. ``games`` - 1, each exactly once, on the E slots of ``env_batch`` by the public rules of
+    include/hrl_env.h.  The home net sits on ``seat(g) = g mod P``; every other seat is a uniform random agent
+    (``eval_pick_player``; the reference's ``Evaluator.execute`` with ``RandomAgent`` as the default agent,
+    evaluation.py:119-136) or, with ``opponent``, a second net (``exec_match`` with one ``Agent`` per seat,
+    evaluation.py:64-87) at ``opponent_temperature``; the first ``opening_plies`` plies are random picks on every seat.
+
+    What differs from ``DeviceEvaluator``: every player moves every ply, so the ply has no mover and is ONE captured
+    graph; a finished slot restarts on the very next step -- through ``env.restart_games(pending, game)`` where the env
+    has it (game g IS Geese game number g under the env's seed, so a game depends on (seed, g, actions) only, never on
+    the slot), else ``reset_where``; a game runs until the env is terminal, also after the home player is out, and the
+    outcome is the env's (Geese: a rank over the final rewards).  One launch (hrl_players_act) decides for every
+    player from relative-seat-major logits.  The forward's rows are in relative-seat order too
+    (``env.observe_seats(seat, K)``, else ``env.observation`` per relative seat): against random agents K = 1 and only
+    the home seat is forwarded (E rows); in a match K = P, rows[:E] feed the home net and rows[E:] the opponent.
+    The finish is hrl_eval_finish unchanged.
+
+    A net with recurrent state raises ``ValueError`` (the scope of ``rollout.PlayerStreamGenerator``); there is no
+    ``observation`` argument: for a net without state the reference's ``Agent.observe`` does nothing.  Eval mode and
+    training modes are put back; no torch generator is drawn from; the host reads the two-word device state every
+    ``check_every`` steps and nothing else."""
+
+    _check_env_batch = staticmethod(_check_player_env)
+
+    @staticmethod
+    def _movers(st):
+        return 1
+
+    def __init__(self, env_batch, net, temperature=0.0, seed=0, check_every=16, graph=None, opponent=None,
+                 opponent_temperature=None, opening_plies=0):
+        super().__init__(env_batch, False, temperature, opening_plies, seed, check_every, graph)
+        if opponent_temperature is None:
+            opponent_temperature = temperature
+        if not opponent_temperature >= 0:
+            raise ValueError('opponent_temperature must be >= 0, not %r' % (opponent_temperature,))
+        if opponent is net:
+            raise ValueError('the opponent must be a module of its own (a copy of the net plays a self-match)')
+        for n in (net, opponent):
+            if hasattr(n, 'init_hidden'):
+                raise ValueError('PlayerEvaluator plays nets without recurrent state; %s has init_hidden'
+                                 % type(n).__name__)
+        _player_blocks(env_batch.P, env_batch.A)
+        self.net, self.opponent, self.opponent_temperature = net, opponent, float(opponent_temperature)
+
+    def _nets(self):
+        return [self.net] + ([] if self.opponent is None else [self.opponent])
+
+    def _state(self):
+        if self._st is not None:
+            return self._st
+        env, E, dev = self.env, self.env.E, self.env.device
+        self._st = {'Tm': env.MAX_PLIES, 'P': env.P, 'cuda': torch.device(dev).type == 'cuda',
+                    'game': torch.zeros(E, dtype=torch.long, device=dev),
+                    'ply': torch.zeros(E, dtype=torch.long, device=dev),
+                    'seat': torch.zeros(E, dtype=torch.long, device=dev),
+                    'active': torch.zeros(E, dtype=torch.bool, device=dev),
+                    'pending': torch.zeros(E, dtype=torch.bool, device=dev),
+                    'state': torch.zeros(2, dtype=torch.long, device=dev), 'rows': torch.arange(E, device=dev)}
+        return self._st
+
+    def _begin(self, st, run):
+        """Every buffer as at the start of a call: slot e waits to start game e (e < G) or is retired; the first step
+        starts the games like any later restart."""
+        E, G, P = self.env.E, run['G'], st['P']
+        rows = st['rows']
+        st['game'].copy_(torch.clamp(rows, max=G))
+        st['seat'].copy_(torch.where(rows < G, rows % P, 0))
+        st['active'].zero_()
+        st['pending'].copy_(rows < G)
+        st['ply'].zero_()
+        st['state'].copy_(torch.tensor([0, min(E, G)], dtype=torch.long))
+        run['outcome'].zero_()
+        run['length'].zero_()
+        if run['trace'] is not None:
+            run['trace']['action'].fill_(-1)
+            run['trace']['picked'].fill_(-1)
+            run['trace']['policy'].zero_()
+            run['trace']['alive'].zero_()
+
+    def _rows(self, st, K):
+        """The forward's input rows (K * E, ...), relative-seat-major: row k * E + e is the view of player
+        (seat[e] + k) mod P."""
+        env = self.env
+        if hasattr(env, 'observe_seats'):
+            return env.observe_seats(st['seat'], K)
+        return _stack_views([env.observation((st['seat'] + k) % st['P']) for k in range(K)])
+
+    def _ply(self, st, run, mover=0):
+        """One global step: every player of every active slot moves."""
+        env, E, P = self.env, self.env.E, st['P']
+        fused = FUSED_PLAYER_EVAL and st['cuda']
+        active, pending = st['active'], st['pending']
+        if hasattr(env, 'restart_games'):
+            env.restart_games(pending, st['game'])
+        else:
+            env.reset_where(pending)
+        active.logical_or_(pending)
+        pending.zero_()
+        turns = (env.turns_mask() & active.view(E, 1)).contiguous()
+        out_opp = None
+        if self.opponent is None:
+            out = self.net(self._rows(st, 1), None)
+        else:
+            rows = self._rows(st, P)
+            out = self.net(map_r(rows, lambda x: x[:E]), None)
+            out_opp = self.opponent(map_r(rows, lambda x: x[E:]), None)
+        legal = env.legal_players() if hasattr(env, 'legal_players') else env.legal()
+        act = players_act_hip if fused else players_act_torch
+        a, usel = act(st, out['policy'], None if out_opp is None else out_opp['policy'], legal, turns, self.seed,
+                      self.temperature, self.opponent_temperature, self.opening_plies, run['G'], run['forced'],
+                      run['trace'])
+        env.step_players(a, turns, active, usel)
+        finish = finish_hip if fused else finish_torch
+        finish(st, env.terminal(), env.outcome(), run['G'], run['outcome'], run['length'])
+
+    def _prepare(self, st, G, forced, trace):
+        """The buffers that depend on G (the captured ply addresses them) and the graph, kept for the next call with
+        the same G, forced / trace choice and parameter addresses."""
+        dev = self.env.device
+        key = (G, forced is not None, bool(trace), FUSED_PLAYER_EVAL, self._use_graph(), self.opponent is not None,
+               self.opening_plies) + params_key(*self._nets())
+        if self._run is None or self._run['key'] != key:
+            Tm, P, A = st['Tm'], st['P'], self.env.A
+            run = {'key': key, 'G': G, 'graphs': None, 'forced': None, 'trace': None,
+                   'outcome': torch.zeros(G + 1, P, device=dev),
+                   'length': torch.zeros(G + 1, dtype=torch.long, device=dev)}
+            if forced is not None:
+                run['forced'] = torch.full((G + 1, Tm, P), -1, dtype=torch.long, device=dev)
+            if trace:
+                run['trace'] = {'action': torch.empty(G + 1, Tm, P, dtype=torch.long, device=dev),
+                                'picked': torch.empty(G + 1, Tm, P, dtype=torch.long, device=dev),
+                                'policy': torch.empty(G + 1, Tm, P, A, device=dev),
+                                'alive': torch.empty(G + 1, Tm, P, dtype=torch.bool, device=dev)}
+            self._run = run
+            if self._use_graph() and G > 0:
+                run['graphs'] = self._capture(st, run)
+        run = self._run
+        if forced is not None:
+            forced = torch.as_tensor(forced, dtype=torch.long)
+            if (forced.dim() != 3 or forced.shape[0] != G or forced.shape[1] > st['Tm']
+                    or forced.shape[2] != st['P']):
+                raise ValueError('forced is (games, <= MAX_PLIES, players) int64, not %s' % (tuple(forced.shape),))
+            run['forced'].fill_(-1)
+            run['forced'][:G, :forced.shape[1]].copy_(forced)
+        return run
+
+    @torch.no_grad()
+    def evaluate(self, games, forced=None, trace=False):
+        """Play game numbers 0 .. games-1.  Returns ``DeviceEvaluator.evaluate``'s dict: 'outcome' (G, P) fp32,
+        'length' (G,), 'seat' (G,), 'results' ({the home seat's outcome: count}), 'win_rate', 'games', 'plies' (global
+        steps run), 'env_steps'; with an opponent 'opponent_results' / 'opponent_win_rate' over all P - 1 other seats
+        of every game; with ``trace`` the records of include/hrl_env.h under 'trace' ('action', 'picked' (G, Tm, P),
+        'policy' (G, Tm, P, A), 'alive' (G, Tm, P)).  ``forced`` (G, <= Tm, P) int64: moves >= 0 are played as given,
+        -1 leaves the decision here."""
+        G = int(games)
+        if G < 0:
+            raise ValueError('games must be >= 0')
+        st = self._state()
+        nets = self._nets()
+        with self._sessions(nets, [False] * len(nets)):
+            run = self._prepare(st, G, forced, trace)
+            plies = self._play(st, run, self.env.E, G, 'evaluation did not finish %d games in %d steps')
+        dev = self.env.device
+        P = st['P']
+        outcome, length = run['outcome'][:G].clone(), run['length'][:G].clone()
+        seat = torch.arange(G, device=dev) % P
+        mine = outcome[torch.arange(G, device=dev), seat].tolist() if G else []
+        results = _tally(mine)
+        res = {'outcome': outcome, 'length': length, 'seat': seat, 'results': results, 'win_rate': wp_func(results),
+               'games': G, 'plies': plies, 'env_steps': int(length.sum())}
+        if self.opponent is not None:
+            others = outcome[(torch.arange(P, device=dev) != seat.view(-1, 1))].tolist() if G else []
+            res['opponent_results'] = _tally(others)
+            res['opponent_win_rate'] = wp_func(res['opponent_results'])
+        if run['trace'] is not None:
+            res['trace'] = {k: v[:G].clone() for k, v in run['trace'].items()}
+        return res
+
+    @torch.no_grad()
+    def set_opponent_state(self, state_dict):
+        """Copy weights and buffers into the opponent IN PLACE (no tensor is replaced), so the captured graph, which
+        addresses them, stays valid."""
         self.opponent.load_state_dict(state_dict)
 
 
@@ -1019,12 +1370,14 @@ def eval_league_main(args, argv, device=None, log=print):
 def eval_main(args, argv, device=None, log=print):
     """``main.py --eval MODEL_PATH [NUM_GAMES=100] [SLOTS]`` (evaluation.py:291-312): the checkpoint in ``env.net()``
     against random agents; logs the result table and win rate in the reference's ``total`` form and returns the
-    evaluator's result."""
+    evaluator's result.  ``env: Geese`` is played by ``PlayerEvaluator`` (the net on seat g mod 4, three random
+    agents), env and evaluator under train_args' ``seed``."""
     from .environment import make_env, prepare_env
     env_args = args['env_args']
     prepare_env(env_args)
     env = make_env(env_args)
-    cls = batched_env(type(env).__module__)
+    players_cls = player_eval_env(type(env).__module__)       # Hungry Geese: every player moves every ply
+    cls = players_cls or batched_env(type(env).__module__)
     targs = args.get('train_args') or {}
     model_path = argv[0] if len(argv) >= 1 else os.path.join('models', 'latest.pth')
     games = int(argv[1]) if len(argv) >= 2 else 100
@@ -1037,11 +1390,24 @@ def eval_main(args, argv, device=None, log=print):
     net = configured_inference(targs.get('inference'), [load_net(env, model_path, device)], device)[0]
     E = max(1, min(slots, games))
     log('%d slots, %d games' % (E, games))
-    ev = DeviceEvaluator(cls(E, device), net, observation=bool(targs.get('observation', False)),
-                         temperature=float(targs.get('eval_temperature', 0.0)), seed=int(targs.get('seed', 0)))
+    if players_cls is not None:
+        ev = _player_evaluator(cls, E, device, net, targs)
+    else:
+        ev = DeviceEvaluator(cls(E, device), net, observation=bool(targs.get('observation', False)),
+                             temperature=float(targs.get('eval_temperature', 0.0)), seed=int(targs.get('seed', 0)))
     res = ev.evaluate(games)
     log('total %s %s' % (res['results'], res['win_rate']))
     return res
+
+
+def _player_evaluator(cls, E, device, net, targs, **match):
+    """``PlayerEvaluator`` over ``cls(E, device)`` as the command-line entry points build it: the env's own picks
+    (Geese's food) and the evaluator's under train_args' ``seed``, ``eval_temperature`` for every net."""
+    seed = int(targs.get('seed', 0))
+    env_batch = cls(E, device)
+    if hasattr(env_batch, 'seed'):
+        env_batch.seed(seed)
+    return PlayerEvaluator(env_batch, net, temperature=float(targs.get('eval_temperature', 0.0)), seed=seed, **match)
 
 
 def load_net(env, model_path, device):
@@ -1068,13 +1434,16 @@ def eval_match_main(args, argv, device=None, log=print):
     ``g mod 2`` of game g.  train_args gives ``observation``, ``eval_temperature`` (both agents), ``eval_opening_plies``
     and ``seed``.  Logs the reference's ``evaluate_mp`` tables (evaluation.py:233-248) -- per agent the games where
     agent 0 moves first (``default-F``: the even game numbers, (NUM_GAMES + 1) // 2 of them), those where it moves
-    second (``default-S``) and the total, each with its win rate -- and returns the evaluator's result."""
+    second (``default-S``) and the total, each with its win rate -- and returns the evaluator's result.  ``env: Geese``
+    (``PlayerEvaluator``): agent 0 sits on seat ``g mod 4`` and agent 1 on the three other seats; per agent one
+    ``default`` line and the ``total`` line (the reference splits -F / -S for two-player games only)."""
     from .environment import make_env, prepare_env
     env_args = args['env_args']
     prepare_env(env_args)
     env = make_env(env_args)
-    cls = batched_env(type(env).__module__)
-    if cls.P != 2:
+    players_cls = player_eval_env(type(env).__module__)       # Hungry Geese: agent 1 sits on the three other seats
+    cls = players_cls or batched_env(type(env).__module__)
+    if players_cls is None and cls.P != 2:
         raise ValueError('--eval-match seats two models: %s has %d players' % (cls.__name__, cls.P))
     targs = args.get('train_args') or {}
     if len(argv) < 2:
@@ -1091,6 +1460,15 @@ def eval_match_main(args, argv, device=None, log=print):
                                      device))
     E = max(1, min(slots, games))
     log('%d slots, %d games' % (E, games))
+    if players_cls is not None:
+        # more than two players: one `default` pattern per agent, no -F / -S split (evaluation.py:188-192)
+        res = _player_evaluator(cls, E, device, nets[0], targs, opponent=nets[1],
+                                opening_plies=opening_plies(targs)).evaluate(games)
+        for agent, key in enumerate(('results', 'opponent_results')):
+            log('---agent %d---' % agent)
+            log('default %s %s' % (res[key], wp_func(res[key])))
+            log('total %s %s' % (res[key], wp_func(res[key])))
+        return res
     ev = DeviceEvaluator(cls(E, device), nets[0], observation=bool(targs.get('observation', False)),
                          temperature=float(targs.get('eval_temperature', 0.0)), seed=int(targs.get('seed', 0)),
                          opponent=nets[1], opening_plies=opening_plies(targs))

@@ -56,7 +56,12 @@ written) with the actors and the learner on the GPU:
 * evaluation: ``eval_rate`` > 0 in train_args makes rank 0 play the reference's per-epoch evaluation after each
   epoch's training -- the greedy model against random agents on the device (``evaluation.DeviceEvaluator``,
   ``eval_slots`` slots, ``eval_temperature``) -- and append its win rate to the epoch's log line;
-  ``--eval MODEL_PATH [NUM_GAMES] [SLOTS]`` evaluates a checkpoint (evaluation.py:291-312);
+  ``--eval MODEL_PATH [NUM_GAMES] [SLOTS]`` evaluates a checkpoint (evaluation.py:291-312).  ``env: Geese`` is
+  evaluated by ``evaluation.PlayerEvaluator`` (every goose moves every ply: the net on seat ``g mod 4``, random
+  agents or the ``eval_opponent`` net on the three others; ``--eval-match`` seats MODEL_B there and prints one
+  ``default`` table per agent); for the per-epoch evaluation that takes ``eval_simultaneous: true`` beside
+  ``eval_rate`` -- ``eval_rate`` alone on a simultaneous-move env raises at start-up as it always has;
+  ParallelTicTacToe and ``--eval-league`` on Geese stay refused;
 * matches: the win rate against random agents saturates within a few epochs, so ``eval_opponent`` in train_args
   seats a second net on the other seats of the per-epoch evaluation instead (the reference's match of one ``Agent``
   per model, evaluation.py:64-116): a path to a ``.pth`` is a fixed anchor loaded once, ``previous`` is the model
@@ -222,8 +227,12 @@ def train_main(args, device=None, loss_fn=None, model_dir='models', log=print):
     eval_vs = targs.get('eval_opponent')
     if float(targs.get('eval_rate') or 0) > 0:
         # the reference's per-epoch evaluation (train.py:519-526); an env it cannot play raises here, at start-up
-        from .evaluation import DeviceEvaluator, batched_env, eval_games, opening_plies
-        eval_cls = batched_env(module)
+        from .evaluation import (DeviceEvaluator, PlayerEvaluator, batched_env, eval_games, opening_plies,
+                                 player_eval_env)
+        # Hungry Geese (every player moves every ply) is evaluated by PlayerEvaluator once `eval_simultaneous` says so;
+        # without that key a simultaneous-move env raises here as it always has
+        eval_players = player_eval_env(module) if targs.get('eval_simultaneous') else None
+        eval_cls = eval_players or batched_env(module)
         eval_n = eval_games(targs['eval_rate'], targs['update_episodes'])
         # a second net on the other seats: a checkpoint (a fixed anchor) or `previous`; a bad path raises here
         if eval_vs not in (None, 'random', 'previous') and not os.path.isfile(str(eval_vs)):
@@ -236,8 +245,14 @@ def train_main(args, device=None, loss_fn=None, model_dir='models', log=print):
                 opponent = _eval_opponent(env, net, eval_vs, device)
                 match = {'opponent': configured_inference(infer_mode, [opponent], device)[0],
                          'opening_plies': opening_plies(targs)}
-            evaluator = DeviceEvaluator(eval_cls(eval_slots, device), play_net, observation=observe,
-                                        temperature=float(targs.get('eval_temperature', 0.0)), seed=seed, **match)
+            if eval_players is not None:
+                eval_batch = eval_cls(eval_slots, device)
+                eval_batch.seed(seed)               # game g of an evaluation is Geese game number g under this seed
+                evaluator = PlayerEvaluator(eval_batch, play_net,
+                                            temperature=float(targs.get('eval_temperature', 0.0)), seed=seed, **match)
+            else:
+                evaluator = DeviceEvaluator(eval_cls(eval_slots, device), play_net, observation=observe,
+                                            temperature=float(targs.get('eval_temperature', 0.0)), seed=seed, **match)
     played = None   # a generator that reports what it emitted (stream): episodes of the last play()
     if use_device and self_play == 'stream' and stream_players:
         slots = int(targs.get('stream_slots') or games)

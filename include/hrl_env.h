@@ -330,6 +330,53 @@ int hrl_eval_finish(const uint8_t *terminal, const float *outcome, int64_t E, in
 int hrl_masked_rows_fill(int nleaves, float *const *dst, const int64_t *dst_stride, const int64_t *F,
                          const uint8_t *mask, int64_t E, void *stream);
 
+/* ---- The evaluator of simultaneous-move envs (evaluation.PlayerEvaluator: Hungry Geese; ParallelTicTacToe at class
+ * level): the home net on one seat, uniform random agents -- or a second net -- on all the others, every player
+ * moving every ply (handyrl/evaluation.py:64-87, 119-136).
+ *
+ * Public rules (pure-Python and torch twins in handyrl_amd/evaluation.py).  Games are counted by number and seated as
+ * above (seat(g) = g mod P); the finish is hrl_eval_finish unchanged.  There is no mover: one launch per ply decides
+ * for every player, and a finished slot restarts on the very next step as game number `game[e]` (for Hungry Geese:
+ * Geese game number g under the env's seed, so a game depends on (seed, g, actions) only, never on the slot).  A game
+ * runs until the env is terminal, also after the home player is out.  For an active slot with game g in [0, G), ply t
+ * in [0, Tm) and a player p with turns[e][p] set:
+ *   Relative seat: k = (p - seat[e]) mod P.  k == 0 is the home net; k >= 1 the opponent net when one is given, else
+ *     no net.
+ *   Random pick, eval_pick_player(seed, g, t, p, legal): eval_pick's integer rule on output word p & 3 of the Philox
+ *     call with last counter word 0xffffffff - (p >> 2).  Player 0 is eval_pick itself.  These words stay apart from
+ *     the Geese picks (0, 1), the player uniforms [0x40000000, 0x80000000) and the select uniform 0x80000000.
+ *   Where t < opening or the player has no net, pick = the random pick.  Otherwise pick comes from the player's own
+ *     logits row at its agent's temperature: at 0 the argmax of p = logits - (legal ? 0 : 1e32), ties to the lowest
+ *     label, NaN first; above 0 the argmax of p * (float)(1.0 / temperature) - log(-log(u)) in fp32 with
+ *     u = stream_player_uniforms(seed, g, t, P, A)[p].
+ *   forced (G, Tm, P) int64 or NULL: forced[g][t][p] >= 0 overrides the move played, not `picked`.
+ *   usel[e] = stream_select_uniform(seed, game[e], ply[e]) (ParallelTicTacToe's step_players takes it, Geese does not).
+ *   Trace (all four buffers or none): action, picked (G, Tm, P) int64, policy (G, Tm, P, A) fp32, alive (G, Tm, P)
+ *     bytes.  Every player of such a slot stores alive = turns; a player that moves stores action = the move played and
+ *     picked = its own decision, one that does not stores -1 in both; policy = p is stored where the player moves and
+ *     has a net, opening plies included.
+ *
+ * The decision in ONE launch, one wave per (slot, player), lanes striding over the A labels (A may exceed 64).
+ * Logits are relative-seat-major: logits_home (E, >= A) fp32 rows of stride stride_home; logits_opp ((P - 1) * E, >= A)
+ * rows of stride stride_opp, or NULL: row (k - 1) * E + e belongs to player (seat[e] + k) mod P.  legal: bytes,
+ * legal_player_stride == 0: (E, A), the same for every player; == A: (E, P, A).  turns (E, P) bytes; game, ply, seat
+ * (E,) int64; active (E,) bytes.
+ * action (E, P) int64 and usel (E,) fp32 are written for EVERY slot: they are the step's inputs.  An inactive, retired
+ * or out-of-range slot (active[e] == 0, ply outside [0, Tm), game outside [0, G)) gets action[e][:] = 0 and no other
+ * store; a player of an active slot that does not move gets action 0.
+ * Asynchronous on `stream`, allocates nothing, reads nothing on the host (graph-capturable).  HRL_EINVAL (before any
+ * HIP call) for a NULL required pointer (all but logits_opp, forced and the trace), E < 0, P, A or Tm < 1, A > 2^20,
+ * G < 0, stride_home < A, stride_opp < A when logits_opp is given, legal_player_stride other than 0 or A, a temperature
+ * < 0 or NaN, opening < 0, some but not all trace buffers, P * E or P * ceil(A / 4) of 0x40000000 or more; E == 0:
+ * HRL_OK, no launch. */
+int hrl_players_act(const float *logits_home, int64_t stride_home, const float *logits_opp, int64_t stride_opp,
+                    const uint8_t *legal, int64_t legal_player_stride, const uint8_t *turns, uint64_t seed,
+                    double temperature_home, double temperature_opp, int64_t opening, const int64_t *game,
+                    const int64_t *ply, const uint8_t *active, const int64_t *seat, const int64_t *forced, int64_t E,
+                    int64_t P, int64_t A, int64_t Tm, int64_t G, int64_t *action, float *usel,
+                    int64_t *trace_action, int64_t *trace_picked, float *trace_policy, uint8_t *trace_alive,
+                    void *stream);
+
 /* ---- The league evaluator (evaluation.LeagueEvaluator): a round robin of K >= 2 nets on the device.
  *
  * Public rules (torch twins in handyrl_amd/evaluation.py):

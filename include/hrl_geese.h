@@ -71,6 +71,17 @@ int hrl_geese_observe_at(const uint8_t *body, const uint8_t *hd, const uint8_t *
                          const int8_t *prev, float *views, uint8_t *record, const int64_t *ply, const uint8_t *infer,
                          const uint8_t *active, int64_t E, int64_t P, int64_t Tm, void *stream);
 
+/* The forward's input rows of the evaluator (evaluation.PlayerEvaluator) in RELATIVE-SEAT order, no record:
+ * rows (K, E, 17, 7, 11) float, row k * E + e = the view of goose (seat[e] + k) mod 4 of game e (the planes of
+ * hrl_geese_observe), for k < K.  seat (E,) int64 in device memory.  K = 1 writes the home seat's view only (E rows
+ * instead of 4 * E: the evaluation against random agents forwards nothing else); with K = 4, rows[:E] feeds the home
+ * net and rows[E:] a second net on the three other seats, both as contiguous slices.  K waves per game, the stores of
+ * hrl_geese_observe (a 1309-float row starts at any 4-byte phase of a 16-byte line).  HRL_EINVAL (before any HIP
+ * call) for a NULL pointer, E < 0, P != 4 or K outside [1, 4]; E == 0: HRL_OK, no launch. */
+int hrl_geese_observe_seats(const uint8_t *body, const uint8_t *hd, const uint8_t *len, const int8_t *food,
+                            const int8_t *prev, const int64_t *seat, float *rows, int64_t E, int64_t P, int64_t K,
+                            void *stream);
+
 #ifdef __cplusplus
 }
 #endif
