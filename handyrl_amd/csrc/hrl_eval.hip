@@ -17,7 +17,8 @@
 // evaluation.PlayerEvaluator plays a simultaneous-move env (Hungry Geese) the same way with
 //   players_act_kernel   one wave per (slot, player): every player decides in the one launch -- the home net on
 //                        seat(g), a second net or eval_pick_player on the others -- from relative-seat-major logits;
-// the finish is eval_finish_kernel unchanged.
+// the finish is eval_finish_kernel unchanged.  With a rule pointer (hrl_players_act_rule) the seats without a net play a
+// rule-based agent's label (Hungry Geese: hrl_geese_greedy) where it is legal, else eval_pick_player as before.
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -153,15 +154,16 @@ struct PlayersTrace {   // all four or none (action NULL: no trace)
 };
 
 // One wave per (slot, player), lanes over the A labels.  Player p of slot e sits k = (p - seat[e]) mod P seats after the
-// home net: k = 0 reads row e of home, k >= 1 row (k - 1) * E + e of opp (or has no net: opp NULL).  Everything that
+// home net: k = 0 reads row e of home, k >= 1 row (k - 1) * E + e of opp (or has no net: opp NULL).  A player without
+// a net plays rule[e * P + p] where a rule is given and that label is legal (hrl_players_act_rule).  Everything that
 // branches is wave-uniform.
 __global__ __launch_bounds__(kWave *kSlotsPerBlock) void players_act_kernel(
     const float *__restrict__ home, int64_t hstride, const float *__restrict__ opp, int64_t ostride,
     const uint8_t *__restrict__ legal, int64_t lpstride, const uint8_t *__restrict__ turns, uint32_t k0, uint32_t k1,
     float inv_t_home, float inv_t_opp, int64_t opening, const int64_t *__restrict__ game,
     const int64_t *__restrict__ ply, const uint8_t *__restrict__ active, const int64_t *__restrict__ seat,
-    const int64_t *__restrict__ forced, int64_t E, int P, int A, int64_t Tm, int64_t G, int64_t *__restrict__ action,
-    float *__restrict__ usel, PlayersTrace tr) {
+    const int64_t *__restrict__ forced, const int64_t *__restrict__ rule, int64_t E, int P, int A, int64_t Tm,
+    int64_t G, int64_t *__restrict__ action, float *__restrict__ usel, PlayersTrace tr) {
     const int lane = threadIdx.x % kWave;
     const int64_t w = (int64_t)blockIdx.x * kSlotsPerBlock + threadIdx.x / kWave;   // the pair e * P + p
     if (w >= E * P) return;
@@ -199,6 +201,10 @@ __global__ __launch_bounds__(kWave *kSlotsPerBlock) void players_act_kernel(
     }
     if (!lg || t < opening)
         pick = random_pick(lm, A, k0, k1, g0, g1, tw, 0xffffffffu - (uint32_t)(p >> 2), p & 3, lane);
+    if (rule && !lg && t >= opening) {   // a rule-based agent on a seat without a net: its label where legal
+        const int64_t r = rule[w];
+        if (r >= 0 && r < A && lm[r]) pick = (int)r;
+    }
     if (lane == 0) {
         const int64_t f = forced ? forced[s] : -1;
         const int64_t a = f >= 0 ? f : pick;
@@ -328,12 +334,26 @@ int hrl_players_act(const float *logits_home, int64_t stride_home, const float *
                     int64_t P, int64_t A, int64_t Tm, int64_t G, int64_t *action, float *usel,
                     int64_t *trace_action, int64_t *trace_picked, float *trace_policy, uint8_t *trace_alive,
                     void *stream) {
+    // no rule-based agent: the same kernel, and for these arguments the same argument checks
+    return hrl_players_act_rule(logits_home, stride_home, logits_opp, stride_opp, legal, legal_player_stride, turns,
+                                seed, temperature_home, temperature_opp, opening, game, ply, active, seat, forced,
+                                nullptr, E, P, A, Tm, G, action, usel, trace_action, trace_picked, trace_policy,
+                                trace_alive, stream);
+}
+
+int hrl_players_act_rule(const float *logits_home, int64_t stride_home, const float *logits_opp, int64_t stride_opp,
+                         const uint8_t *legal, int64_t legal_player_stride, const uint8_t *turns, uint64_t seed,
+                         double temperature_home, double temperature_opp, int64_t opening, const int64_t *game,
+                         const int64_t *ply, const uint8_t *active, const int64_t *seat, const int64_t *forced,
+                         const int64_t *rule, int64_t E, int64_t P, int64_t A, int64_t Tm, int64_t G, int64_t *action,
+                         float *usel, int64_t *trace_action, int64_t *trace_picked, float *trace_policy,
+                         uint8_t *trace_alive, void *stream) {
     const int ntrace = (trace_action != nullptr) + (trace_picked != nullptr) + (trace_policy != nullptr) +
                        (trace_alive != nullptr);
     if (!logits_home || !legal || !turns || !game || !ply || !active || !seat || !action || !usel || E < 0 || P < 1 ||
         A < 1 || A > (1 << 20) || Tm < 1 || G < 0 || stride_home < A || (logits_opp && stride_opp < A) ||
         (legal_player_stride != 0 && legal_player_stride != A) || !(temperature_home >= 0.0) ||
-        !(temperature_opp >= 0.0) || opening < 0 || (ntrace != 0 && ntrace != 4))
+        !(temperature_opp >= 0.0) || opening < 0 || (ntrace != 0 && ntrace != 4) || (rule && logits_opp))
         return HRL_EINVAL;
     constexpr int64_t kLimit = 0x40000000;
     if (P >= kLimit || E >= kLimit || P * E >= kLimit || P * ((A + 3) / 4) >= kLimit) return HRL_EINVAL;
@@ -345,7 +365,7 @@ int hrl_players_act(const float *logits_home, int64_t stride_home, const float *
     hipLaunchKernelGGL(players_act_kernel, dim3(blocks), dim3(kWave * kSlotsPerBlock), 0,
                        static_cast<hipStream_t>(stream), logits_home, stride_home, logits_opp, stride_opp, legal,
                        legal_player_stride, turns, (uint32_t)seed, (uint32_t)(seed >> 32), inv_home, inv_opp, opening,
-                       game, ply, active, seat, forced, E, (int)P, (int)A, Tm, G, action, usel, tr);
+                       game, ply, active, seat, forced, rule, E, (int)P, (int)A, Tm, G, action, usel, tr);
     const hipError_t err = hipGetLastError();
     return err == hipSuccess ? HRL_OK : HRL_ELAUNCH_BASE - (int)err;
 }

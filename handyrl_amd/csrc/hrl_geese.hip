@@ -16,6 +16,8 @@
 //            addressed by a per-game ply, and every player's slot of an active game is written -- zeros where the
 //            player does not infer.  A 1309-byte view starts at any byte phase: bytes, 16-byte stores, bytes.
 //   observe_seats  the evaluator's rows: K waves per game, wave k = the view of goose (seat + k) mod 4, no record.
+//   greedy   the rule-based goose for the evaluator's other seats: one wave per game, the occupancy mask by a wave
+//            OR-reduction, lanes 0-15 the (goose, candidate) pairs, a 4-lane minimum over (distance, order).
 // Every value is written with ordinary vector stores in plain C++.
 
 #include <hip/hip_runtime.h>
@@ -332,6 +334,86 @@ observe_seats_kernel(const uint8_t *body, const uint8_t *hd, const uint8_t *len,
     store_view(rows + ((int64_t)k * E + e) * kView, pm, lane);
 }
 
+// ---- the greedy rule-based goose (include/hrl_geese.h; geese.greedy_action_of is the specification) ----
+constexpr int kGamesPerBlock = 4;       // one wave per game
+constexpr int kOrder = 0x2130;          // nibble j: the j-th label of the order NORTH, EAST, SOUTH, WEST (0, 3, 1, 2)
+constexpr int kNoCandidate = 0x7fff;
+
+// translate() as selects: lanes of one wave ask for different directions
+__device__ __forceinline__ int neighbour(int cell, int a) {
+    const int r = cell / kCols, c = cell - r * kCols;
+    const int r1 = r + (a == 0 ? kRows - 1 : a == 1 ? 1 : 0), c1 = c + (a == 2 ? kCols - 1 : a == 3 ? 1 : 0);
+    return (r1 >= kRows ? r1 - kRows : r1) * kCols + (c1 >= kCols ? c1 - kCols : c1);
+}
+
+// the one-cell mask of c; empty when !on or c is no cell
+__device__ __forceinline__ Mask cell_bit(int c, bool on) {
+    const uint64_t b = 1ull << (c & 63);
+    return Mask{on && c >= 0 && c < 64 ? b : 0ull, on && c >= 64 && c < kCells ? b : 0ull};
+}
+
+__device__ __forceinline__ uint64_t or_lanes(uint64_t x, int from, int below) {   // OR over lane ^ off, off in [from, below)
+    for (int off = from; off < below; off <<= 1) x |= (uint64_t)__shfl_xor((unsigned long long)x, off);
+    return x;
+}
+
+// One wave per game; the only branch is the wave's range test.  The 320 (goose, ring offset) pairs go five to a lane
+// into the occupancy mask; lane 4 p + j (the lanes from 16 on repeat lanes 0-15) is goose p's j-th candidate.
+__global__ void __launch_bounds__(kWave *kGamesPerBlock)
+greedy_kernel(const uint8_t *__restrict__ body, const uint8_t *__restrict__ hd, const uint8_t *__restrict__ len,
+              const int8_t *__restrict__ food, const int8_t *__restrict__ last, int64_t *__restrict__ rule, int64_t E) {
+    const int lane = threadIdx.x % kWave;
+    const int64_t e = (int64_t)blockIdx.x * kGamesPerBlock + threadIdx.x / kWave;
+    if (e >= E) return;
+    Mask occ{0, 0};
+#pragma unroll
+    for (int i = lane; i < kGeese * kRing; i += kWave) {
+        const int q = i / kRing, k = i - q * kRing;
+        const int64_t gq = e * kGeese + q;
+        const Mask b = cell_bit(body[gq * kRing + (hd[gq] + k) % kRing], k < len[gq]);
+        occ.lo |= b.lo;
+        occ.hi |= b.hi;
+    }
+    occ.lo = or_lanes(occ.lo, 1, kWave);
+    occ.hi = or_lanes(occ.hi, 1, kWave);
+    const int p = (lane >> 2) & (kGeese - 1), j = lane & 3, a = (kOrder >> (4 * j)) & 3;
+    const int64_t gp = e * kGeese + p;
+    const bool alive = len[gp] > 0;
+    const int head = body[gp * kRing + hd[gp] % kRing];
+    const int c = neighbour(head < kCells ? head : 0, a);
+    // the neighbours of goose p's head: the OR over its four lanes; blocked = occupied or next to ANOTHER living head
+    Mask adj = cell_bit(c, alive);
+    adj.lo = or_lanes(adj.lo, 1, 4);
+    adj.hi = or_lanes(adj.hi, 1, 4);
+    Mask blocked = occ;
+#pragma unroll
+    for (int q = 0; q < kGeese; ++q) {
+        const uint64_t lo = (uint64_t)__shfl((unsigned long long)adj.lo, 4 * q);
+        const uint64_t hi = (uint64_t)__shfl((unsigned long long)adj.hi, 4 * q);
+        blocked.lo |= q != p ? lo : 0ull;
+        blocked.hi |= q != p ? hi : 0ull;
+    }
+    const int la = last[gp];                             // read by every lane: the test below is a select, no branch
+    const bool open = !blocked.has(c), forward = la < 0 || a != (la ^ 1);
+    const bool candidate = alive & open & forward;
+    const int cr = c / kCols, cc = c - cr * kCols;
+    int d = kNoCandidate;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const int f = food[e * 2 + s];
+        const int fr = f / kCols, fc = f - fr * kCols;
+        const int dist = (cr > fr ? cr - fr : fr - cr) + (cc > fc ? cc - fc : fc - cc);
+        d = f >= 0 && f < kCells && dist < d ? dist : d;
+    }
+    d = d == kNoCandidate ? 0 : d;                       // no food on the board
+    int key = candidate ? d * 4 + j : kNoCandidate;      // (d, order index), d <= 16
+    for (int off = 1; off < 4; off <<= 1) {
+        const int other = __shfl_xor(key, off);
+        key = other < key ? other : key;
+    }
+    if (lane < kGeese * 4 && j == 0) rule[gp] = key == kNoCandidate ? -1 : (kOrder >> (4 * (key & 3))) & 3;
+}
+
 inline int grid_for(int64_t n) { return (int)((n + 255) / 256); }
 
 inline int launched() {
@@ -400,6 +482,16 @@ int hrl_geese_observe_seats(const uint8_t *body, const uint8_t *hd, const uint8_
     if (E == 0) return HRL_OK;
     hipLaunchKernelGGL(observe_seats_kernel, dim3((unsigned)E), dim3((unsigned)(kWave * K)), 0,
                        static_cast<hipStream_t>(stream), body, hd, len, food, prev, seat, rows, E);
+    return launched();
+}
+
+int hrl_geese_greedy(const uint8_t *body, const uint8_t *hd, const uint8_t *len, const int8_t *food,
+                     const int8_t *last, int64_t *rule, int64_t E, int64_t P, void *stream) {
+    if (!body || !hd || !len || !food || !last || !rule || E < 0 || E > 0x7fffffff || P != kGeese) return HRL_EINVAL;
+    if (E == 0) return HRL_OK;
+    hipLaunchKernelGGL(greedy_kernel, dim3((unsigned)((E + kGamesPerBlock - 1) / kGamesPerBlock)),
+                       dim3(kWave * kGamesPerBlock), 0, static_cast<hipStream_t>(stream), body, hd, len, food, last,
+                       rule, E);
     return launched();
 }
 

@@ -20,10 +20,15 @@ A game state is a dict: ``geese`` four lists of cells, head first (empty = dead)
 ``last`` / ``prev`` per goose the last action and the head cell in the previous state (-1 = none); ``reward`` per
 goose; ``step``; ``game`` (the game number); ``live``.
 
+``greedy_action_of`` is a rule-based goose of this project's own (modelled on the published behaviour of Kaggle's
+``GreedyAgent``, which was not consulted either: no move-for-move parity is claimed), the evaluator's rule-based
+opponent; ``rule_based_action``, which names Kaggle's agent, keeps raising.
+
 ``envs/hungry_geese.py`` keeps GeeseNet and its ``Environment`` that points to the reference plugin.
 """
 
 import copy
+import random
 
 import numpy as np
 import torch
@@ -196,6 +201,45 @@ def turns_of(state):
     return [i for i, goose in enumerate(state['geese']) if goose] if state['live'] else []
 
 
+GREEDY_ORDER = (0, 3, 1, 2)     # NORTH, EAST, SOUTH, WEST
+
+
+def greedy_action_of(state, player):
+    """The greedy rule-based goose: the label ``player`` plays in ``state``, or -1 (no candidate, or the goose is
+    dead; the caller then plays a uniform random label).
+
+    Provenance.  This is THIS PROJECT'S statement of a greedy goose, modelled on the published behaviour of Kaggle's
+    ``GreedyAgent`` (what the reference plugin's ``rule_based_action`` calls); ``kaggle_environments`` is not available
+    to this project and was not consulted, no move-for-move parity with it is claimed and none can be tested.  The
+    function is the specification of ``HungryGeeseBatch.greedy_players`` and of hrl_geese_greedy (csrc/hrl_geese.hip).
+
+    * Blocked cells: every cell of every goose (own cells and tails included) and the four torus neighbours of the
+      head of every OTHER living goose.
+    * Candidates: the labels in the order NORTH, EAST, SOUTH, WEST (0, 3, 1, 2) whose cell ``translate(head, a)`` is
+      not blocked and, once the goose has moved (``last >= 0``), that do not reverse its last action.
+    * ``d(a)``: the smallest ``|row - row| + |col - col|`` from that cell to a food cell -- the plain distance on the
+      7 x 11 grid, not the torus distance; 0 with no food on the board.
+    * The candidate of smallest d, ties to the earliest in the order."""
+    geese = state['geese']
+    if not geese[player]:
+        return -1
+    head, last = geese[player][0], state['last'][player]
+    blocked = {c for goose in geese for c in goose}
+    for i, goose in enumerate(geese):
+        if i != player and goose:
+            blocked.update(translate(goose[0], a) for a in range(4))
+    food = [f for f in state['food'] if f >= 0]
+    best, best_d = -1, None
+    for a in GREEDY_ORDER:
+        c = translate(head, a)
+        if c in blocked or (last >= 0 and a == OPPOSITE[last]):
+            continue
+        d = min((abs(c // COLS - f // COLS) + abs(c % COLS - f % COLS) for f in food), default=0)
+        if best_d is None or d < best_d:
+            best, best_d = a, d
+    return best
+
+
 class Environment(BaseEnvironment):
     """The host plugin env over ``step_game``.  ``Environment(args)`` takes ``args.get('seed', 0)`` and numbers its
     games 0, 1, ... per instance; there is no ``reward()`` (the base class's empty dict, as in the reference)."""
@@ -251,6 +295,12 @@ class Environment(BaseEnvironment):
     def rule_based_action(self, player):
         raise NotImplementedError('the rule-based Hungry Geese agent is GreedyAgent of kaggle_environments '
                                   '(kaggle_environments.envs.hungry_geese), which this package does not have')
+
+    def greedy_action(self, player):
+        """This project's greedy goose (``greedy_action_of``; not Kaggle's GreedyAgent move for move): the rule's
+        label, or a uniform random legal label where the rule has no candidate."""
+        a = greedy_action_of(self.state, player)
+        return a if a >= 0 else random.choice(self.legal_actions(player))
 
     def net(self):
         return GeeseNet
@@ -320,6 +370,7 @@ class HungryGeeseBatch:
     SIMULTANEOUS = True
     ALTERNATING = False
     PLAYER_EVAL = True     # evaluation.player_eval_env: the entry points evaluate it with PlayerEvaluator
+    RULE_AGENT = 'greedy_players'     # PlayerEvaluator(opponent='rule'): the method that gives every player's label
 
     def __init__(self, E, device, seed=0):
         self.E, self.device = E, device
@@ -480,6 +531,18 @@ class HungryGeeseBatch:
         rows = np.stack([np.stack([observation_of(g, (int(s) + k) % GEESE) for g, s in zip(self._games, seat.tolist())])
                          for k in range(K)]) if E else np.zeros((K, 0, *self.OBS_SHAPE), dtype=np.float32)
         return torch.from_numpy(rows).view(K * E, *self.OBS_SHAPE)
+
+    def greedy_players(self):
+        """(E, 4) int64: ``greedy_action_of`` for every goose of every slot (-1: no candidate, or the goose is dead);
+        the evaluator's rule-based opponent (``RULE_AGENT``).  One launch of hrl_geese_greedy on a CUDA batch."""
+        if self._hip():
+            self._state_ok()
+            rule = torch.empty(self.E, GEESE, dtype=torch.long, device=self.device)
+            self._native('hrl_geese_greedy', self.body, self.head, self.length, self.food, self.last, rule, self.E,
+                         self.P)
+            return rule
+        return torch.tensor([[greedy_action_of(g, p) for p in range(GEESE)] for g in self._games],
+                            dtype=torch.long).view(self.E, GEESE)
 
     def observe_players_record(self, rec, t, infer):
         """All four views of every game as the forward's (4 * E, 17, 7, 11) input rows, player-major, and in the

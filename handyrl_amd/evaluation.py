@@ -30,7 +30,10 @@ those of the match above, with each net forwarded only over the rows where it mo
 A simultaneous-move env (Hungry Geese; ParallelTicTacToe at class level) has no mover: ``PlayerEvaluator`` seats the
 home net on ``g mod P`` and random agents (``eval_pick_player``) or a second net on ALL other seats, decides for every
 player in one launch (hrl_players_act) and restarts a finished slot on the very next step; include/hrl_env.h has its
-rules.
+rules.  ``PlayerEvaluator(..., opponent='rule')``, ``eval_opponent: rulebase`` and ``main.py --eval-rulebase`` seat the
+env's rule-based agent on the other seats instead (Hungry Geese: this project's greedy goose,
+``envs.geese.greedy_action_of`` -- one more launch per step, hrl_geese_greedy, and the decision through
+hrl_players_act_rule): the vs-random win rate on Geese is saturated before training starts.
 
 ``FUSED_EVAL``: on a GPU the ply's decision and bookkeeping are the launches of hrl_match_act (the one decision
 kernel; hrl_eval_act is its form without an opponent and opening plies), hrl_eval_finish and hrl_masked_rows_fill
@@ -52,7 +55,7 @@ from .util import map_r
 
 __all__ = ['DeviceEvaluator', 'eval_pick', 'eval_pick_torch', 'eval_main', 'eval_match_main', 'wp_func', 'eval_games',
            'batched_env', 'LeagueEvaluator', 'bradley_terry', 'eval_league_main', 'PlayerEvaluator', 'eval_pick_player',
-           'eval_pick_player_torch', 'player_eval_env']
+           'eval_pick_player_torch', 'player_eval_env', 'rule_eval_env', 'eval_rulebase_main']
 
 # True: on a GPU the three steps are HIP launches; False (or a CPU env): the torch ops below, bit-identical.
 FUSED_EVAL = True
@@ -336,15 +339,19 @@ def finish_hip(st, terminal, outcome, G, outcome_out, length_out):
 
 
 def players_act_torch(st, logits_home, logits_opp, legal, turns, seed, temperature_home, temperature_opp, opening, G,
-                      forced=None, trace=None):
+                      forced=None, trace=None, rule=None):
     """hrl_players_act, the decision of ``PlayerEvaluator``: every player of every slot in one go.  ``logits_home``
     (E, >= A) and ``logits_opp`` ((P - 1) * E, >= A) or None are relative-seat-major: row (k - 1) * E + e of the
     opponent belongs to player (seat[e] + k) mod P; ``legal`` (E, A) or (E, P, A); ``turns`` (E, P) bool.  Returns the
     actions (E, P) (0 for an inactive slot and for a player that does not move) and the select uniforms (E,);
-    ``trace`` (dict or None) gets the records."""
+    ``trace`` (dict or None) gets the records.  ``rule`` (E, P) int64 or None (hrl_players_act_rule; not together with
+    ``logits_opp``): a player without a net at ``ply >= opening`` picks rule[e, p] where that is a legal label in
+    [0, A), else the random pick as without a rule."""
     game, ply, active, seat = st['game'], st['ply'], st['active'], st['seat']
     E, P = turns.shape
     A, Tm, dev = legal.shape[-1], st['Tm'], turns.device
+    if rule is not None and logits_opp is not None:
+        raise ValueError('players_act: a rule and a second net are not seated together')
     ok = active & (ply >= 0) & (ply < Tm) & (game >= 0) & (game < G)
     if legal.dim() == 2:
         legal = legal.view(E, 1, A).expand(E, P, A)
@@ -375,6 +382,11 @@ def players_act_torch(st, logits_home, logits_opp, legal, turns, seed, temperatu
         pick = torch.where(home, pick, net(temperature_opp))
     rand = eval_pick_player_torch(seed, game, ply, P, legal)
     pick = torch.where(has_net & (ply >= opening).view(E, 1), pick, rand)
+    if rule is not None:
+        in_range = (rule >= 0) & (rule < A)
+        r = torch.where(in_range, rule, 0)
+        use = in_range & legal.gather(-1, r.unsqueeze(-1)).squeeze(-1) & ~has_net & (ply >= opening).view(E, 1)
+        pick = torch.where(use, r, pick)
     moves = turns & ok.view(E, 1)
     g = torch.where(ok, game, G)
     t = torch.where(ok, ply, 0)
@@ -392,8 +404,9 @@ def players_act_torch(st, logits_home, logits_opp, legal, turns, seed, temperatu
 
 
 def players_act_hip(st, logits_home, logits_opp, legal, turns, seed, temperature_home, temperature_opp, opening, G,
-                    forced=None, trace=None):
-    """players_act_torch as ONE launch (hrl_players_act, one wave per (slot, player))."""
+                    forced=None, trace=None, rule=None, rule_entry=False):
+    """players_act_torch as ONE launch (hrl_players_act, one wave per (slot, player); with ``rule``, or with
+    ``rule_entry`` and a NULL rule, the same kernel through hrl_players_act_rule)."""
     from . import _native
     E, P = turns.shape
     A, Tm = legal.shape[-1], st['Tm']
@@ -421,14 +434,19 @@ def players_act_hip(st, logits_home, logits_opp, legal, turns, seed, temperature
         assert tr[0].dtype == tr[1].dtype == torch.long and tr[2].dtype == torch.float32 and tr[2].shape[3] == A
         assert tr[3].dtype == torch.bool
     home, opp = rows
+    entry, extra = ('hrl_players_act_rule', [None]) if rule_entry else ('hrl_players_act', [])
+    if rule is not None:
+        assert rule.shape == (E, P) and rule.dtype == torch.long and rule.is_contiguous()
+        assert rule.device == legal.device
+        entry, extra = 'hrl_players_act_rule', [_native.ptr(rule)]
     a = torch.empty(E, P, dtype=torch.long, device=legal.device)
     usel = torch.empty(E, device=legal.device)
-    _native.check(_native.load().hrl_players_act(
+    _native.check(getattr(_native.load(), entry)(
         _native.ptr(home), home.stride(0), _native.ptr(opp), 0 if opp is None else opp.stride(0), _native.ptr(legal),
         A if legal.dim() == 3 else 0, _native.ptr(turns), int(seed) & 0xffffffffffffffff, float(temperature_home),
         float(temperature_opp), int(opening), _native.ptr(st['game']), _native.ptr(st['ply']),
-        _native.ptr(st['active']), _native.ptr(st['seat']), _native.ptr(forced), E, P, A, Tm, G, _native.ptr(a),
-        _native.ptr(usel), *[_native.ptr(x) for x in tr], _native.stream_of(legal.device)), 'hrl_players_act')
+        _native.ptr(st['active']), _native.ptr(st['seat']), _native.ptr(forced), *extra, E, P, A, Tm, G,
+        _native.ptr(a), _native.ptr(usel), *[_native.ptr(x) for x in tr], _native.stream_of(legal.device)), entry)
     return a, usel
 
 
@@ -807,6 +825,11 @@ class PlayerEvaluator(_PlyEvaluator):
     (``eval_pick_player``; the reference's ``Evaluator.execute`` with ``RandomAgent`` as the default agent,
     evaluation.py:119-136) or, with ``opponent``, a second net (``exec_match`` with one ``Agent`` per seat,
     evaluation.py:64-87) at ``opponent_temperature``; the first ``opening_plies`` plies are random picks on every seat.
+    ``opponent='rule'`` seats the env's rule-based agent there instead (``RULE_AGENT``: Hungry Geese's greedy goose,
+    ``geese.greedy_action_of``; the reference's ``Evaluator.default_agent`` names a RuleBasedAgent as the other choice):
+    only the home seat is forwarded, as against random agents, ``env.greedy_players()`` is one more launch and the
+    decision (hrl_players_act_rule) plays its label, or the random agent's pick where the rule has none;
+    ``opponent_temperature`` is ignored and an env without ``RULE_AGENT`` raises ``ValueError``.
 
     What differs from ``DeviceEvaluator``: every player moves every ply, so the ply has no mover and is ONE captured
     graph; a finished slot restarts on the very next step -- through ``env.restart_games(pending, game)`` where the env
@@ -836,6 +859,16 @@ class PlayerEvaluator(_PlyEvaluator):
             opponent_temperature = temperature
         if not opponent_temperature >= 0:
             raise ValueError('opponent_temperature must be >= 0, not %r' % (opponent_temperature,))
+        self.rule = None
+        if isinstance(opponent, str):
+            # a rule-based agent of the env's own on the other seats (Hungry Geese: the greedy goose)
+            if opponent != 'rule':
+                raise ValueError("opponent is a module, None or 'rule', not %r" % (opponent,))
+            self.rule = getattr(env_batch, 'RULE_AGENT', None)
+            if self.rule is None:
+                raise ValueError("opponent='rule' needs an env with a rule-based agent (RULE_AGENT: Hungry Geese's "
+                                 "greedy goose); %s has none" % type(env_batch).__name__)
+            opponent = None
         if opponent is net:
             raise ValueError('the opponent must be a module of its own (a copy of the net plays a self-match)')
         for n in (net, opponent):
@@ -909,9 +942,11 @@ class PlayerEvaluator(_PlyEvaluator):
             out_opp = self.opponent(map_r(rows, lambda x: x[E:]), None)
         legal = env.legal_players() if hasattr(env, 'legal_players') else env.legal()
         act = players_act_hip if fused else players_act_torch
+        # a rule-based opponent: the env's label for every player, one launch; the decision seats it where no net sits
+        rule = {} if self.rule is None else {'rule': getattr(env, self.rule)()}
         a, usel = act(st, out['policy'], None if out_opp is None else out_opp['policy'], legal, turns, self.seed,
                       self.temperature, self.opponent_temperature, self.opening_plies, run['G'], run['forced'],
-                      run['trace'])
+                      run['trace'], **rule)
         env.step_players(a, turns, active, usel)
         finish = finish_hip if fused else finish_torch
         finish(st, env.terminal(), env.outcome(), run['G'], run['outcome'], run['length'])
@@ -920,7 +955,8 @@ class PlayerEvaluator(_PlyEvaluator):
         """The buffers that depend on G (the captured ply addresses them) and the graph, kept for the next call with
         the same G, forced / trace choice and parameter addresses."""
         dev = self.env.device
-        key = (G, forced is not None, bool(trace), FUSED_PLAYER_EVAL, self._use_graph(), self.opponent is not None,
+        key = (G, forced is not None, bool(trace), FUSED_PLAYER_EVAL, self._use_graph(),
+               'rule' if self.rule is not None else self.opponent is not None,
                self.opening_plies) + params_key(*self._nets())
         if self._run is None or self._run['key'] != key:
             Tm, P, A = st['Tm'], st['P'], self.env.A
@@ -971,7 +1007,7 @@ class PlayerEvaluator(_PlyEvaluator):
         results = _tally(mine)
         res = {'outcome': outcome, 'length': length, 'seat': seat, 'results': results, 'win_rate': wp_func(results),
                'games': G, 'plies': plies, 'env_steps': int(length.sum())}
-        if self.opponent is not None:
+        if self.opponent is not None or self.rule is not None:
             others = outcome[(torch.arange(P, device=dev) != seat.view(-1, 1))].tolist() if G else []
             res['opponent_results'] = _tally(others)
             res['opponent_win_rate'] = wp_func(res['opponent_results'])
@@ -982,7 +1018,10 @@ class PlayerEvaluator(_PlyEvaluator):
     @torch.no_grad()
     def set_opponent_state(self, state_dict):
         """Copy weights and buffers into the opponent IN PLACE (no tensor is replaced), so the captured graph, which
-        addresses them, stays valid."""
+        addresses them, stays valid.  A rule-based opponent has no state: ValueError."""
+        if self.opponent is None:
+            raise ValueError('set_opponent_state needs a net on the other seats; this evaluator seats %s there'
+                             % ('the env\'s rule-based agent' if self.rule is not None else 'random agents'))
         self.opponent.load_state_dict(state_dict)
 
 
@@ -1408,6 +1447,53 @@ def _player_evaluator(cls, E, device, net, targs, **match):
     if hasattr(env_batch, 'seed'):
         env_batch.seed(seed)
     return PlayerEvaluator(env_batch, net, temperature=float(targs.get('eval_temperature', 0.0)), seed=seed, **match)
+
+
+def rule_eval_env(module):
+    """The batched twin ``PlayerEvaluator(opponent='rule')`` plays for the env module ``module`` (``eval_opponent:
+    rulebase``, ``--eval-rulebase``): the ``PLAYER_EVAL`` class with a ``RULE_AGENT`` (Hungry Geese).  An env without
+    a rule-based agent raises ValueError, naming it."""
+    from .main import _batched_envs
+    cls = _batched_envs().get(module)
+    if not getattr(cls, 'PLAYER_EVAL', False) or getattr(cls, 'RULE_AGENT', None) is None:
+        raise ValueError('a rule-based opponent (eval_opponent: rulebase, --eval-rulebase) needs an env with a '
+                         'rule-based agent on the device (RULE_AGENT: Hungry Geese, env: Geese); %s has none'
+                         % (getattr(cls, '__name__', None) or module,))
+    return cls
+
+
+def eval_rulebase_main(args, argv, device=None, log=print):
+    """``main.py --eval-rulebase MODEL_PATH [NUM_GAMES=100] [SLOTS]``: the checkpoint in ``env.net()`` on seat
+    ``g mod 4`` against the env's rule-based agent on the three other seats (Hungry Geese: this project's greedy
+    goose, ``geese.greedy_action_of`` -- not Kaggle's GreedyAgent move for move).  Logs ``--eval-match``'s tables on
+    Geese: per agent ``---agent N---``, a ``default`` line and the ``total`` line; agent 0 is the model, agent 1 the
+    rule's three seats.  train_args gives ``eval_temperature``, ``eval_opening_plies`` (default 0 here: the games
+    already differ by game number) and ``seed``.  Returns the evaluator's result."""
+    from .environment import make_env, prepare_env
+    env_args = args['env_args']
+    prepare_env(env_args)
+    env = make_env(env_args)
+    cls = rule_eval_env(type(env).__module__)
+    targs = args.get('train_args') or {}
+    if len(argv) < 1:
+        raise ValueError('--eval-rulebase needs a checkpoint: MODEL_PATH [NUM_GAMES] [SLOTS]')
+    games = int(argv[1]) if len(argv) >= 2 else 100
+    slots = int(argv[2]) if len(argv) >= 3 else int(targs.get('eval_slots') or 1024)
+    if device is None:
+        if not torch.cuda.is_available():
+            raise RuntimeError('handyrl_amd.main evaluates on the GPU (HIP kernels); no GPU is visible')
+        device = torch.device('cuda', 0)
+    from .nn import configured_inference
+    net = configured_inference(targs.get('inference'), [load_net(env, argv[0], device)], device)[0]
+    E = max(1, min(slots, games))
+    log('%d slots, %d games' % (E, games))
+    res = _player_evaluator(cls, E, device, net, targs, opponent='rule',
+                            opening_plies=int(targs.get('eval_opening_plies') or 0)).evaluate(games)
+    for agent, key in enumerate(('results', 'opponent_results')):
+        log('---agent %d---' % agent)
+        log('default %s %s' % (res[key], wp_func(res[key])))
+        log('total %s %s' % (res[key], wp_func(res[key])))
+    return res
 
 
 def load_net(env, model_path, device):

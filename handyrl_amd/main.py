@@ -3,6 +3,7 @@
     python -m handyrl_amd.main --train [config.yaml]
     python -m handyrl_amd.main --eval MODEL_PATH [NUM_GAMES] [SLOTS]
     python -m handyrl_amd.main --eval-match MODEL_A MODEL_B [NUM_GAMES] [SLOTS]
+    python -m handyrl_amd.main --eval-rulebase MODEL_PATH [NUM_GAMES] [SLOTS]
     python -m handyrl_amd.main --eval-league MODEL_OR_DIR [MODEL_OR_DIR ...] [NUM_GAMES] [SLOTS]
     python -m torch.distributed.run --nproc-per-node N -m handyrl_amd.main --train [config.yaml]
 
@@ -72,6 +73,12 @@ written) with the actors and the learner on the GPU:
   ``vs <path>``.  ``--eval-match MODEL_A MODEL_B [NUM_GAMES] [SLOTS]`` plays two checkpoints against each other
   and prints the reference's per-agent tables (evaluation.py:233-248).  Training is bit-identical with and
   without the key.
+* a rule-based opponent: ``eval_opponent: rulebase`` (``env: Geese`` with ``eval_simultaneous: true``) seats the env's
+  rule-based agent on the three other seats -- this project's greedy goose, ``envs.geese.greedy_action_of``, modelled
+  on the published behaviour of Kaggle's GreedyAgent, not that agent move for move -- and the epoch line ends
+  ``vs rulebase``; no net is constructed and ``eval_opening_plies`` defaults to 0 (the games differ by game number).
+  ``--eval-rulebase MODEL_PATH [NUM_GAMES] [SLOTS]`` evaluates a checkpoint that way and prints ``--eval-match``'s
+  per-agent tables (agent 1: the rule's three seats).  An env without a rule-based agent raises at start-up.
 * leagues: ``--eval-league MODEL_OR_DIR [MODEL_OR_DIR ...] [NUM_GAMES] [SLOTS]`` plays a round robin of checkpoints
   (a directory expands to its ``<epoch>.pth`` files in epoch order) in one run on the device
   (``evaluation.LeagueEvaluator``): NUM_GAMES games per pairing, each game the one ``--eval-match`` would play, every
@@ -228,20 +235,26 @@ def train_main(args, device=None, loss_fn=None, model_dir='models', log=print):
     if float(targs.get('eval_rate') or 0) > 0:
         # the reference's per-epoch evaluation (train.py:519-526); an env it cannot play raises here, at start-up
         from .evaluation import (DeviceEvaluator, PlayerEvaluator, batched_env, eval_games, opening_plies,
-                                 player_eval_env)
+                                 player_eval_env, rule_eval_env)
         # Hungry Geese (every player moves every ply) is evaluated by PlayerEvaluator once `eval_simultaneous` says so;
         # without that key a simultaneous-move env raises here as it always has
         eval_players = player_eval_env(module) if targs.get('eval_simultaneous') else None
         eval_cls = eval_players or batched_env(module)
         eval_n = eval_games(targs['eval_rate'], targs['update_episodes'])
+        # `rulebase`: the env's rule-based agent on the other seats (Hungry Geese's greedy goose); an env without one
+        # raises here.  No net is constructed and no generator drawn from
+        if eval_vs == 'rulebase':
+            rule_eval_env(module)
         # a second net on the other seats: a checkpoint (a fixed anchor) or `previous`; a bad path raises here
-        if eval_vs not in (None, 'random', 'previous') and not os.path.isfile(str(eval_vs)):
-            raise FileNotFoundError("train_args['eval_opponent'] is random, previous or a checkpoint: no file %r"
-                                    % (eval_vs,))
+        elif eval_vs not in (None, 'random', 'previous') and not os.path.isfile(str(eval_vs)):
+            raise FileNotFoundError("train_args['eval_opponent'] is random, previous, rulebase or a checkpoint: no "
+                                    "file %r" % (eval_vs,))
         if rank == 0:
             eval_slots = max(1, min(int(targs.get('eval_slots') or eval_n), eval_n))
             match = {}
-            if eval_vs not in (None, 'random'):
+            if eval_vs == 'rulebase':
+                match = {'opponent': 'rule', 'opening_plies': int(targs.get('eval_opening_plies') or 0)}
+            elif eval_vs not in (None, 'random'):
                 opponent = _eval_opponent(env, net, eval_vs, device)
                 match = {'opponent': configured_inference(infer_mode, [opponent], device)[0],
                          'opening_plies': opening_plies(targs)}
@@ -357,7 +370,7 @@ def train_main(args, device=None, loss_fn=None, model_dir='models', log=print):
             if evaluator is not None:
                 res = evaluator.evaluate(eval_n)
                 line += ', win rate %.3f (%.1f / %d)' % (res['win_rate'], res['win_rate'] * eval_n, eval_n)
-                if evaluator.opponent is not None:
+                if evaluator.opponent is not None or eval_vs == 'rulebase':
                     line += ' vs %s' % (eval_vs,)
                     if eval_vs == 'previous':     # the next epoch's opponent: the model as it is now, in place
                         evaluator.set_opponent_state(model.state_dict())
@@ -379,6 +392,12 @@ def main(argv=None):
         print(args)
         eval_match_main(args, argv[1:])
         return 0
+    if argv and argv[0] == '--eval-rulebase':
+        from .evaluation import eval_rulebase_main
+        args = load_config('config.yaml')
+        print(args)
+        eval_rulebase_main(args, argv[1:])
+        return 0
     if argv and argv[0] == '--eval-league':
         from .evaluation import eval_league_main
         args = load_config('config.yaml')
@@ -388,6 +407,7 @@ def main(argv=None):
     if not argv or argv[0] not in ('--train', '-t'):
         print('usage: python -m handyrl_amd.main --train [config.yaml] | --eval MODEL_PATH [NUM_GAMES] [SLOTS] | '
               '--eval-match MODEL_A MODEL_B [NUM_GAMES] [SLOTS] | '
+              '--eval-rulebase MODEL_PATH [NUM_GAMES] [SLOTS] | '
               '--eval-league MODEL_OR_DIR [MODEL_OR_DIR ...] [NUM_GAMES] [SLOTS]')
         return 1
     args = load_config(argv[1] if len(argv) > 1 else 'config.yaml')

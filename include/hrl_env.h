@@ -377,6 +377,22 @@ int hrl_players_act(const float *logits_home, int64_t stride_home, const float *
                     int64_t *trace_action, int64_t *trace_picked, float *trace_policy, uint8_t *trace_alive,
                     void *stream);
 
+/* hrl_players_act with a rule-based agent on the seats without a net (PlayerEvaluator(opponent='rule'): Hungry Geese's
+ * greedy goose, hrl_geese.h).  rule (E, P) int64 in device memory, or NULL.  A player of an active slot that moves,
+ * has NO net (k >= 1; logits_opp must be NULL) and is at t >= opening picks rule[e][p] when that is in [0, A) and a
+ * legal label for the player, and otherwise the random pick, unchanged (eval_pick_player(seed, g, t, p, legal): no
+ * new counter word).  `picked` records that decision, `forced` still overrides the move played and no policy is
+ * stored for such a player.  Everything else is hrl_players_act's rule word for word -- it is the same kernel with
+ * one more pointer -- and with rule == NULL every output equals hrl_players_act's bit for bit.  HRL_EINVAL when both
+ * rule and logits_opp are given (one meaning per call), and for every reason hrl_players_act has. */
+int hrl_players_act_rule(const float *logits_home, int64_t stride_home, const float *logits_opp, int64_t stride_opp,
+                         const uint8_t *legal, int64_t legal_player_stride, const uint8_t *turns, uint64_t seed,
+                         double temperature_home, double temperature_opp, int64_t opening, const int64_t *game,
+                         const int64_t *ply, const uint8_t *active, const int64_t *seat, const int64_t *forced,
+                         const int64_t *rule, int64_t E, int64_t P, int64_t A, int64_t Tm, int64_t G, int64_t *action,
+                         float *usel, int64_t *trace_action, int64_t *trace_picked, float *trace_policy,
+                         uint8_t *trace_alive, void *stream);
+
 /* ---- The league evaluator (evaluation.LeagueEvaluator): a round robin of K >= 2 nets on the device.
  *
  * Public rules (torch twins in handyrl_amd/evaluation.py):

@@ -82,6 +82,28 @@ int hrl_geese_observe_seats(const uint8_t *body, const uint8_t *hd, const uint8_
                             const int8_t *prev, const int64_t *seat, float *rows, int64_t E, int64_t P, int64_t K,
                             void *stream);
 
+/* The greedy rule-based goose (geese.greedy_action_of is the specification; HungryGeeseBatch.greedy_players the
+ * batch form).  The rule is THIS PROJECT'S statement of a greedy goose, modelled on the published behaviour of
+ * Kaggle's GreedyAgent; kaggle_environments was not consulted and no move-for-move parity with it is claimed.
+ *
+ * rule (E, 4) int64: rule[e][p] is the label goose p of game e plays, or -1 (the caller then plays a uniform random
+ * label).  For a goose that is alive (len > 0), with head its head cell and last its last action:
+ *   Blocked cells: every cell of every goose (own cells and tails included), and the four torus neighbours of the
+ *     head of every OTHER living goose.
+ *   Candidates: the labels in the fixed order NORTH, EAST, SOUTH, WEST (0, 3, 1, 2) whose cell c = translate(head, a)
+ *     is not blocked and, when last >= 0, for which a is not the opposite of last.
+ *   Distance: d(a) = min over the food cells f >= 0 of |row(c) - row(f)| + |col(c) - col(f)| -- the plain distance on
+ *     the 7 x 11 grid, NOT the torus distance; with no food on the board d = 0.
+ *   Result: the candidate of smallest d, ties to the earliest in the order above; -1 without a candidate and for a
+ *     dead goose.
+ * Every slot is written, whatever `live` says (the state of a finished game is still a state).  One wave per game,
+ * four games per workgroup: the lanes walk the four rings into the occupancy mask (a wave OR-reduction of two 64-bit
+ * words), lanes 0-15 are the (goose, candidate) pairs, a 4-lane minimum over (d, order index) picks the label and
+ * one lane per goose stores it.  Nothing else is stored.  HRL_EINVAL (before any HIP call) for a NULL pointer, E < 0
+ * or P != 4; E == 0: HRL_OK, no launch. */
+int hrl_geese_greedy(const uint8_t *body, const uint8_t *hd, const uint8_t *len, const int8_t *food,
+                     const int8_t *last, int64_t *rule, int64_t E, int64_t P, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
