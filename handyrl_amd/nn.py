@@ -39,7 +39,7 @@ import torch.nn.functional as F
 from . import _native
 
 __all__ = ['BatchNorm2d', 'BoardConv2d', 'Linear', 'accelerate', 'batch_norm_train', 'fuse_bn_relu', 'unfuse',
-           'BoardInference', 'board_inference_group', 'board_inference_ok']
+           'BoardInference', 'board_inference_group', 'board_inference_ok', 'GeeseInference', 'geese_inference_ok']
 
 _MAX_ROW = 3072        # float4 path (row width a multiple of 4)
 _MAX_ROW_SCALAR = 1024  # scalar path
@@ -2803,10 +2803,155 @@ def board_inference_group(nets):
     return BoardInferenceGroup(nets)
 
 
+# ---------------------------------------------------------------- GeeseNet inference tower
+def _geese_infer_parts(net):
+    """The units of a GeeseNet-shaped net (envs/hungry_geese.py) that csrc/hrl_geesenet.hip forwards, or None:
+    ``conv0`` a TorusConv2d(17, 32, 3x3) and ``blocks`` 1..16 TorusConv2d(32, 32, 3x3), each a biased 3x3
+    nn.Conv2d without padding (the wrap is the module's) followed by an affine, stat-tracking BatchNorm2d(32);
+    bias-free ``head_p`` Linear(32, 4) and ``head_v`` Linear(64, 1); no ``init_hidden``.  Checked by structure:
+    the same before and after ``accelerate`` (which sets ``use_hip`` and swaps in subclasses)."""
+    def unit_ok(u, cin):
+        c, bn = getattr(u, 'conv', None), getattr(u, 'bn', None)
+        return (tuple(getattr(u, 'edge_size', ())) == (1, 1) and callable(getattr(u, 'wrap', None))
+                and isinstance(c, nn.Conv2d) and c.in_channels == cin and c.out_channels == 32
+                and tuple(c.kernel_size) == (3, 3) and tuple(c.stride) == (1, 1) and tuple(c.dilation) == (1, 1)
+                and c.groups == 1 and isinstance(c.padding, tuple) and tuple(c.padding) == (0, 0)
+                and c.bias is not None and isinstance(bn, nn.BatchNorm2d) and bn.num_features == 32 and bn.affine
+                and bn.track_running_stats and bn.running_mean is not None and bn.running_var is not None)
+
+    def linear_ok(m, nin, nout):
+        return isinstance(m, nn.Linear) and m.in_features == nin and m.out_features == nout and m.bias is None
+
+    blocks = getattr(net, 'blocks', None)
+    if hasattr(net, 'init_hidden') or not unit_ok(getattr(net, 'conv0', None), 17):
+        return None
+    if not isinstance(blocks, nn.ModuleList) or not 1 <= len(blocks) <= 16:
+        return None
+    if not all(unit_ok(b, 32) for b in blocks):
+        return None
+    if not (linear_ok(getattr(net, 'head_p', None), 32, 4) and linear_ok(getattr(net, 'head_v', None), 64, 1)):
+        return None
+    return [net.conv0, *blocks], net.head_p, net.head_v
+
+
+def geese_inference_ok(net):
+    """True for a net ``GeeseInference`` can forward (a GeeseNet-shaped module with 32 filters and 1..16 blocks)."""
+    return _geese_infer_parts(net) is not None
+
+
+class GeeseInference:
+    """GeeseNet as the generators and evaluators use one, its eval forward ``layers + 1`` launches
+    (hrl_geesenet_infer): one per unit, BatchNorm folded, the weights packed once per session.
+
+    The surface is ``BoardInference``'s.  ``net`` is referred to, not registered: ``training``, ``eval``,
+    ``train``, ``parameters``, ``buffers``, ``state_dict``, ``load_state_dict`` and ``to`` are its own.
+    ``inference_session`` packs the net's current tensors (one hrl_geesenet_infer_pack launch) into a buffer that
+    keeps its address, so a captured ply stays valid and a later session refreshes the weights in place.  Inside a
+    session a CUDA fp32 observation batch (N, 17, H, W) with H*W <= 80 is the native forward; a CPU batch runs
+    ``net``'s own forward.  Training mode, or the GPU outside a session, raises: there is no other GPU path.
+    """
+
+    stateless_session = True   # nothing to advance in place: generators may enter the session in any mode
+
+    def __init__(self, net):
+        if not geese_inference_ok(net):
+            raise ValueError('GeeseInference: not a GeeseNet-shaped net (geese_inference_ok)')
+        self.net = net
+        self.layers = len(net.blocks)
+        self._buf = None
+        self._live = 0
+
+    training = property(lambda self: self.net.training)
+
+    def eval(self):
+        self.net.eval()
+        return self
+
+    def train(self, mode=True):
+        self.net.train(mode)
+        return self
+
+    def parameters(self, *args, **kwargs):
+        return self.net.parameters(*args, **kwargs)
+
+    def buffers(self, *args, **kwargs):
+        return self.net.buffers(*args, **kwargs)
+
+    def state_dict(self, *args, **kwargs):
+        return self.net.state_dict(*args, **kwargs)
+
+    def load_state_dict(self, *args, **kwargs):
+        return self.net.load_state_dict(*args, **kwargs)
+
+    def to(self, *args, **kwargs):
+        self.net = self.net.to(*args, **kwargs)
+        return self
+
+    def pack(self, device=None):
+        """The pack buffer (pack_bytes uint8) on ``device``: allocated once, the same storage ever after."""
+        if self._buf is None or (device is not None and self._buf.device != torch.device(device)):
+            nbytes = _native.load().hrl_geesenet_infer_pack_bytes(self.layers)
+            self._buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        return self._buf
+
+    def _refresh(self, dev):
+        """hrl_geesenet_infer_pack from the net's tensors into the pack."""
+        units, hp, hv = _geese_infer_parts(self.net)
+        per = [[u.conv.weight for u in units], [u.conv.bias for u in units], [u.bn.weight for u in units],
+               [u.bn.bias for u in units], [u.bn.running_mean for u in units], [u.bn.running_var for u in units]]
+        for t in [hp.weight, hv.weight] + [t for ts in per for t in ts]:
+            if not (t.device == dev and t.dtype == torch.float32 and t.is_contiguous()):
+                raise ValueError('GeeseInference: the net\'s tensors must be contiguous fp32 on one device')
+        eps = (ctypes.c_double * len(units))(*[float(u.bn.eps) for u in units])
+        _native.check(_native.load().hrl_geesenet_infer_pack(
+            *[_native.ptr_array(ts) for ts in per], eps, self.layers, _native.ptr(hp.weight), _native.ptr(hv.weight),
+            _native.ptr(self.pack(dev)), _native.stream_of(dev)), 'hrl_geesenet_infer_pack')
+
+    @contextlib.contextmanager
+    def inference_session(self, inplace_state=False):
+        """Pack the net's current weights (one launch, in place); ``inplace_state`` is accepted and ignored (the
+        net has no state).  On a CPU net there is nothing to prepare."""
+        dev = next(self.net.parameters()).device
+        if dev.type == 'cuda':
+            with torch.no_grad():
+                self._refresh(dev)
+        self._live += 1
+        try:
+            yield self
+        finally:
+            self._live -= 1
+
+    def __call__(self, obs, hidden=None):
+        if self.net.training:
+            raise RuntimeError('GeeseInference is the eval forward: the net is in training mode')
+        if not obs.is_cuda:
+            return self.net(obs, hidden)
+        if not self._live:
+            raise RuntimeError('GeeseInference on the GPU runs inside inference_session()')
+        if obs.dtype != torch.float32 or obs.dim() != 4 or obs.shape[1] != 17 or obs.shape[2] * obs.shape[3] > 80 \
+                or obs.shape[2] * obs.shape[3] < 1:
+            raise ValueError('GeeseInference: observations are (N, 17, H, W) fp32 with H*W <= 80, not %s %s'
+                             % (tuple(obs.shape), obs.dtype))
+        lib = _native.load()
+        N, _, H, W = obs.shape
+        o = obs if obs.is_contiguous() else obs.contiguous()
+        policy = torch.empty(N, 4, device=obs.device)
+        value = torch.empty(N, 1, device=obs.device)
+        if N == 0:
+            return {'policy': policy, 'value': value}
+        nbytes = lib.hrl_geesenet_infer_workspace_bytes(N, H, W)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=obs.device)
+        _native.check(lib.hrl_geesenet_infer(
+            _native.ptr(self.pack(obs.device)), self.layers, _native.ptr(o), N, H, W, _native.ptr(policy),
+            _native.ptr(value), _native.ptr(ws), nbytes, _native.stream_of(obs.device)), 'hrl_geesenet_infer')
+        return {'policy': policy, 'value': value}
+
+
 def configured_inference(mode, nets, device):
     """``train_args['inference']`` applied to the nets that play: absent / None leaves them as they are; ``fused``
-    wraps each in ``BoardInference`` (several: one ``board_inference_group``).  Anything the fused forward cannot
-    run raises here, at start-up, by the key's name."""
+    wraps each TicTacToe net in ``BoardInference`` (several: one ``board_inference_group``) and each GeeseNet in
+    ``GeeseInference`` (each on its own).  Anything the fused forward cannot run, or a list mixing the two kinds,
+    raises here, at start-up, by the key's name."""
     if mode is None:
         return nets
     if mode != 'fused':
@@ -2814,8 +2959,14 @@ def configured_inference(mode, nets, device):
     if torch.device(device).type != 'cuda':
         raise ValueError("train_args['inference']: 'fused' is the one-launch forward on the GPU; the device is %s"
                          % (device,))
+    if nets and all(geese_inference_ok(net) for net in nets):
+        return [GeeseInference(net) for net in nets]
     for net in nets:
+        if geese_inference_ok(net):
+            raise ValueError("train_args['inference']: 'fused' forwards nets of one kind; %s is a GeeseNet among "
+                             "nets that are not" % type(net).__name__)
         if not board_inference_ok(net):
             raise ValueError("train_args['inference']: 'fused' forwards the TicTacToe net (SimpleConv2dModel with 32 "
-                             "filters and 1..8 blocks); %s is not one (board_inference_ok)" % type(net).__name__)
+                             "filters and 1..8 blocks) or GeeseNet (32 filters, 1..16 blocks); %s is not one "
+                             "(board_inference_ok, geese_inference_ok)" % type(net).__name__)
     return board_inference_group(nets) if len(nets) > 1 else [BoardInference(nets[0])]

@@ -637,6 +637,41 @@ int hrl_board_infer_pack(const float *stem_w, const float *stem_b, const float *
 int hrl_board_infer(const void *pack, int64_t pack_stride_bytes, int64_t K, const int64_t *span, const float *obs,
                     int64_t N, int64_t layers, float *policy, float *value, void *stream);
 
+/* GeeseNet's eval forward with BatchNorm folded and the weights packed once (envs/hungry_geese.py GeeseNet: stem
+ * TorusConv2d(17, 32) + BN + ReLU, `layers` residual units h = relu(h + bn(conv(h))), pooled heads;
+ * csrc/hrl_geesenet.hip).  32 filters, 4 actions, a torus board of H*W <= 80 cells; layers in 1..16.  Every entry
+ * is asynchronous, allocates nothing, never synchronises and is capturable; arguments are validated (HRL_EINVAL)
+ * before any HIP call.
+ * hrl_geesenet_infer_pack_bytes: the bytes of one packed net (a multiple of 16; 0 for layers outside 1..16).
+ * hrl_geesenet_infer_pack: ONE launch that reads the net's tensors where they lie -- host arrays of layers + 1
+ *   device pointers (entry 0 the stem, then the blocks): conv weight (32, 17 | 32, 3, 3), conv bias, BatchNorm
+ *   weight, bias, running_mean, running_var, and bn_eps[u] (host doubles); head_p (4, 32) and head_v (1, 64) -- and
+ *   writes the pack (16-byte aligned): per unit the fp32 MFMA operands in hrl_torus_conv_forward's packed layout
+ *   (the stem's input channels 17..31 zero), alpha = weight * (float)(1/sqrt((double)var + eps)),
+ *   beta = bias - mean*alpha as hrl_bn_forward_eval forms them, and the conv bias; then the head weights.
+ * hrl_geesenet_infer_workspace_bytes: N*32*H*W*4 (one h buffer, updated in place; 0 for N = 0); -1 for N < 0, a
+ *   board of more than 80 cells or H, W < 1.
+ * hrl_geesenet_infer: layers + 1 launches, nothing else.  x (N, 17, H, W) fp32 contiguous; policy (N, 4) gets the
+ *   raw logits, value (N, 1) the tanh; ws 16-byte aligned.  Unit u writes h = relu([h +] (conv(h) + b)*alpha + beta)
+ *   straight from the conv's accumulators (no conv output reaches memory); the last unit keeps its h on chip,
+ *   pools it (h_head = sum_q h*x[:, 0], h_avg = sum_q h / (H*W), hrl_torus_head_pool's sums) and applies both
+ *   heads.  Arithmetic: hrl_torus_conv_forward's exact bf16 split (fp32-accurate).  A row's result does not depend
+ *   on N or on its place in the batch.  Deterministic.  N == 0: HRL_OK, no launch.  HRL_EINVAL for a NULL pack, x,
+ *   policy or value, a pack or ws that is not 16-byte aligned, layers outside 1..16, N < 0, H*W > 80, and (N > 0)
+ *   a NULL ws or ws_bytes below hrl_geesenet_infer_workspace_bytes.
+ * hrl_geesenet_infer_set_form: the launch shape: 0 (default) by batch size -- N <= 1024 runs workgroups of 2 waves
+ *   (two per CU), larger N workgroups of 8 (one per CU); 1 / 2 force the 8- / 2-wave shape.  The results are
+ *   bit-identical.  Any other value only queries.  Process-wide; returns the previous setting. */
+int64_t hrl_geesenet_infer_pack_bytes(int64_t layers);
+int hrl_geesenet_infer_pack(const float *const *conv_w, const float *const *conv_b, const float *const *bn_w,
+                            const float *const *bn_b, const float *const *bn_mean, const float *const *bn_var,
+                            const double *bn_eps, int64_t layers, const float *head_p, const float *head_v, void *pack,
+                            void *stream);
+int64_t hrl_geesenet_infer_workspace_bytes(int64_t N, int64_t H, int64_t W);
+int hrl_geesenet_infer(const void *pack, int64_t layers, const float *x, int64_t N, int64_t H, int64_t W,
+                       float *policy, float *value, void *ws, int64_t ws_bytes, void *stream);
+int hrl_geesenet_infer_set_form(int form);
+
 #ifdef __cplusplus
 }
 #endif
