@@ -913,12 +913,12 @@ def sample_record_stream_hip(st, seed, logits, legal, value, active, player, rew
     return a
 
 
-def harvest_torch(st, done, outcome, gamma, replay, ring_game, has_reward=True):
-    """The streaming generator's harvest as torch ops, without a host read (graph-capturable): the episodes of the
+def _harvest_torch(keys, st, done, outcome, gamma, replay, ring_game, has_reward):
+    """The streaming generators' harvest as torch ops, without a host read (graph-capturable): the episodes of the
     ``done`` slots go to the ring rows (ring_ptr + r) mod N, r = the number of done slots below, and their slots
-    restart (the contract of hrl_selfplay_harvest, include/hrl_env.h, which equals this bit for bit).  Formed over
-    the W = min(E, N) rows the call can write: row k of them is written when k < c (the done count), by the last
-    done slot that claims it.  ``st``: the slot records and 'ply', 'game', 'pending', 'state', 'rows'."""
+    restart.  Formed over the W = min(E, N) rows the call can write: row k of them is written when k < c (the done
+    count), by the last done slot that claims it.  ``keys``: the per-ply records besides obs, policy and amask;
+    an observation leaf is converted as ``src.to(dst.dtype)``."""
     E, N, Tm = done.shape[0], replay.N, replay.Tm
     dev = done.device
     if dev.type == 'cpu' and not bool(done.any()):
@@ -945,12 +945,11 @@ def harvest_torch(st, done, outcome, gamma, replay, ring_game, has_reward=True):
     def plies(src, fill=0):
         v = valid.view(W, Tm, *([1] * (src.dim() - 2)))
         return torch.where(v, src.index_select(0, slot), fill)
-    bimap_r(replay.obs, st['obs'], lambda dst, src: put(dst, plies(src.to(dst.dtype))))
+    bimap_r(replay.obs, st['obs'], lambda dst, src: put(dst, plies(src)))
     put(replay.policy, plies(st['policy']))
     put(replay.amask, plies(st['amask'], 1e32))
-    put(replay.action, plies(st['action']))
-    put(replay.value, plies(st['value']))
-    put(replay.turn, plies(st['turn']))
+    for key in keys:
+        put(getattr(replay, key), plies(st[key]))
     rew = plies(st['reward']) if has_reward else torch.zeros(W, Tm, replay.P, dtype=torch.float64, device=dev)
     put(replay.reward, rew.float())
     ret = torch.zeros(W, Tm, replay.P, device=dev)
@@ -969,20 +968,52 @@ def harvest_torch(st, done, outcome, gamma, replay, ring_game, has_reward=True):
     state[1:3].add_(c)
 
 
+def harvest_torch(st, done, outcome, gamma, replay, ring_game, has_reward=True):
+    """``_harvest_torch`` for the mover records into a ``DeviceReplay`` (the contract of hrl_selfplay_harvest,
+    include/hrl_env.h, which equals this bit for bit).  ``st``: the slot records and 'ply', 'game', 'pending',
+    'state', 'rows'."""
+    _harvest_torch(('action', 'value', 'turn'), st, done, outcome, gamma, replay, ring_game, has_reward)
+
+
+def harvest_players_torch(st, done, outcome, gamma, replay, ring_game, has_reward=False):
+    """``_harvest_torch`` for per-player records into a ``PlayerReplay`` (the contract of
+    hrl_selfplay_harvest_players, which equals this bit for bit): the records carry a player axis and ``tmask`` /
+    ``omask`` take the place of ``turn``."""
+    _harvest_torch(('action', 'value', 'tmask', 'omask'), st, done, outcome, gamma, replay, ring_game, has_reward)
+
+
+def _obs_type(t):
+    from . import _native
+    if t.dtype not in (torch.uint8, torch.float32):
+        raise ValueError('observation records are uint8 or float32, not %s' % t.dtype)
+    return _native.REPLAY_F32 if t.dtype == torch.float32 else _native.REPLAY_U8
+
+
+def _obs_leaves(struct, obs, lead, typed=True):
+    """The observation fields of a slots or ring struct from the leaves of ``obs``, each ``lead`` + its own shape;
+    ``typed``: the struct names each leaf's type, else every leaf is fp32.  Returns the leaves."""
+    from . import _native
+    src = _leaves(obs)
+    if len(src) > _native.REPLAY_MAX_LEAVES:
+        raise ValueError('at most %d observation leaves' % _native.REPLAY_MAX_LEAVES)
+    struct.nleaves = len(src)
+    for l, o in enumerate(src):
+        assert o.is_contiguous() and o.shape[:len(lead)] == lead
+        struct.obs[l] = o.data_ptr()
+        struct.obs_width[l] = int(np.prod(o.shape[len(lead):], dtype=np.int64))
+        if typed:
+            struct.obs_type[l] = _obs_type(o)
+        else:
+            assert o.dtype == torch.float32
+    return src
+
+
 def _ring_struct(replay):
     """struct hrl_replay_ring of a DeviceReplay / PlayerReplay (the struct keeps no tensor alive)."""
     from . import _native
-    src = _leaves(replay.obs)
-    if len(src) > _native.REPLAY_MAX_LEAVES:
-        raise ValueError('at most %d observation leaves' % _native.REPLAY_MAX_LEAVES)
     ring = _native.ReplayRing()
-    ring.N, ring.Tm, ring.P, ring.A, ring.nleaves = replay.N, replay.Tm, replay.P, replay.policy.shape[-1], len(src)
-    for l, o in enumerate(src):
-        if o.dtype not in (torch.uint8, torch.float32):
-            raise ValueError('observation records are uint8 or float32, not %s' % o.dtype)
-        ring.obs[l] = o.data_ptr()
-        ring.obs_type[l] = _native.REPLAY_F32 if o.dtype == torch.float32 else _native.REPLAY_U8
-        ring.obs_width[l] = int(np.prod(o.shape[replay._lead:], dtype=np.int64))
+    ring.N, ring.Tm, ring.P, ring.A = replay.N, replay.Tm, replay.P, replay.policy.shape[-1]
+    _obs_leaves(ring, replay.obs, tuple(replay.policy.shape[:replay._lead]))
     for k in ('policy', 'amask', 'action', 'value', 'reward', 'ret', 'length', 'outcome'):
         setattr(ring, k, getattr(replay, k).data_ptr())
     if replay._lead == 3:      # PlayerReplay: the PLAYERS layouts
@@ -992,18 +1023,14 @@ def _ring_struct(replay):
     return ring
 
 
-def harvest_hip(st, done, outcome, gamma, replay, ring_game, has_reward=True):
-    """harvest_torch as the two launches of hrl_selfplay_harvest."""
+def _harvest_hip(entry, slots, lead, typed, keys, st, done, outcome, gamma, replay, ring_game, has_reward):
+    """The two launches of ``entry`` (hrl_selfplay_harvest / hrl_selfplay_harvest_players) on the slot records
+    ``keys`` of ``st``; ``slots``: the entry's struct with E, Tm, P, A set; ``lead``: the records' leading dims;
+    ``typed``: the struct names each observation leaf's type (else every leaf is fp32)."""
     from . import _native
-    E, Tm, A = st['policy'].shape
-    src = _leaves(st['obs'])
-    slots = _native.SelfplaySlots()
-    slots.E, slots.Tm, slots.P, slots.A, slots.nleaves = E, Tm, st['reward'].shape[2], A, len(src)
-    for l, o in enumerate(src):
-        assert o.dtype == torch.float32 and o.is_contiguous() and o.shape[:2] == (E, Tm)
-        slots.obs[l] = o.data_ptr()
-        slots.obs_width[l] = int(np.prod(o.shape[2:], dtype=np.int64))
-    for k in ('policy', 'amask', 'action', 'value', 'turn'):
+    E = slots.E
+    _obs_leaves(slots, st['obs'], lead, typed)
+    for k in ('policy', 'amask') + keys:
         assert st[k].is_contiguous()
         setattr(slots, k, st[k].data_ptr())
     slots.reward = st['reward'].data_ptr() if has_reward else None
@@ -1012,13 +1039,111 @@ def harvest_hip(st, done, outcome, gamma, replay, ring_game, has_reward=True):
     assert st['pending'].dtype == torch.bool and st['state'].shape == (3,) and st['state'].dtype == torch.long
     assert ring_game.shape == (replay.N,) and ring_game.dtype == torch.long and ring_game.is_contiguous()
     ring = _ring_struct(replay)
-    _native.check(_native.load().hrl_selfplay_harvest(
+    _native.check(getattr(_native.load(), entry)(
         _native.ptr(done), ctypes.byref(slots), _native.ptr(st['ply']), _native.ptr(outcome), float(gamma),
         ctypes.byref(ring), _native.ptr(ring_game), _native.ptr(st['game']), _native.ptr(st['pending']),
-        _native.ptr(st['state']), _native.stream_of(done.device)), 'hrl_selfplay_harvest')
+        _native.ptr(st['state']), _native.stream_of(done.device)), entry)
 
 
-class StreamGenerator:
+def harvest_hip(st, done, outcome, gamma, replay, ring_game, has_reward=True):
+    """harvest_torch as the two launches of hrl_selfplay_harvest."""
+    from . import _native
+    slots = _native.SelfplaySlots()
+    slots.E, slots.Tm, slots.A = st['policy'].shape
+    slots.P = st['reward'].shape[2]
+    _harvest_hip('hrl_selfplay_harvest', slots, (slots.E, slots.Tm), False, ('action', 'value', 'turn'), st, done,
+                 outcome, gamma, replay, ring_game, has_reward)
+
+
+def harvest_players_hip(st, done, outcome, gamma, replay, ring_game, has_reward=False):
+    """harvest_players_torch as the two launches of hrl_selfplay_harvest_players."""
+    from . import _native
+    slots = _native.SelfplayPlayerSlots()
+    slots.E, slots.Tm, slots.P, slots.A = st['policy'].shape
+    assert st['tmask'].dtype == st['omask'].dtype == torch.bool and st['action'].dtype == torch.long
+    _harvest_hip('hrl_selfplay_harvest_players', slots, (slots.E, slots.Tm, slots.P), True,
+                 ('action', 'value', 'tmask', 'omask'), st, done, outcome, gamma, replay, ring_game, has_reward)
+
+
+class _StreamDriver:
+    """What ``StreamGenerator`` and ``PlayerStreamGenerator`` share: the bookkeeping of a stream of games, the
+    capture of the step's graphs with the games put back afterwards, and the loop that replays them until enough
+    episodes are in the ring, with one host read of the device ring state per ``check_every`` steps.  A subclass
+    checks its scope before it calls ``__init__`` and has ``_state()``, ``_persistent(st)`` (everything a step
+    changes besides the slot records and the ring), ``_bodies(st, dry=False)`` (the ordered {m: callable} of one
+    global step each, step s running body s % len; ``dry``: nothing is harvested) and ``_session(st)`` (the context a
+    call runs in: the net's inference session, if it has one)."""
+
+    def __init__(self, env_batch, net, replay, gamma, seed, check_every, graph, shape_error):
+        if (replay.Tm, replay.P, replay.policy.shape[-1]) != (env_batch.MAX_PLIES, env_batch.P, env_batch.A):
+            raise ValueError(shape_error)
+        self.env, self.net, self.replay = env_batch, net, replay
+        self.gamma, self.seed = float(gamma), int(seed) & 0xffffffffffffffff
+        self.check_every = max(1, int(check_every or 1))
+        self.graph = graph
+        self.s = 0                         # global steps run
+        self.games_started = env_batch.E
+        self._emitted = 0
+        self._steps = 0                    # env-steps of the emitted episodes
+        self._st = None
+        self._graphs = None
+        self.ring_game = torch.full((replay.N,), -1, dtype=torch.long, device=env_batch.device)
+
+    def _use_graph(self):
+        return graph_wanted(self.env.device, self.graph)
+
+    def _capture(self, st):
+        """One graph per body.  Dry steps run first on a side stream (library workspaces) and harvest nothing; the
+        games, the ring state and the recurrent state are then put back, so that warm-up and capture leave no trace
+        (a slot record the warm-up wrote is written again by the ply that owns it)."""
+        keep = [t.clone() for t in self._persistent(st)]
+        dry = self._bodies(st, dry=True)
+
+        def warm():
+            for body in dry.values():
+                body()
+        graphs = capture_graphs(self.env.device, self._bodies(st), warm)
+        for t, k in zip(self._persistent(st), keep):
+            t.copy_(k)
+        return graphs
+
+    @torch.no_grad()
+    def generate(self, episodes):
+        """Run global steps until ``episodes`` more games have been emitted into the ring (checked every
+        ``check_every`` steps, so a call may overshoot).  Returns {'episodes': emitted by this call, 'env_steps':
+        the sum of their lengths, 'plies': global steps run}."""
+        st = self._state()
+        with eval_mode(self.net), self._session(st):
+            return self._generate(st, int(episodes))
+
+    def _generate(self, st, episodes):
+        N = self.replay.N
+        bodies = self._bodies(st)
+        if self._use_graph():
+            # a captured step reads the net's parameters and buffers where they live: recapture if any moved (the
+            # games stay); the switch between the kernels and their torch formulation is part of the capture too
+            key = (FUSED_STREAM,) + params_key(self.net)
+            if self._graphs is None or self._graphs[0] != key:
+                self._graphs = (key, self._capture(st))
+            bodies = {m: g.replay for m, g in self._graphs[1].items()}
+        emitted0, steps0, s0 = self._emitted, self._steps, self.s
+        target = emitted0 + episodes
+        emitted = emitted0
+        M = len(bodies)
+        while emitted < target:
+            for _ in range(self.check_every):
+                bodies[self.s % M]()
+                self.s += 1
+            emitted = int(st['state'][1])
+        ring_ptr, emitted, next_game = (int(v) for v in st['state'].tolist())
+        self._steps = int(st['played'].sum()) - int(st['ply'].sum())   # all plies played less the games in flight
+        self.replay.ptr = ring_ptr
+        self.replay.count = min(self.replay.count + emitted - emitted0, N)
+        self._emitted, self.games_started = emitted, next_game
+        return {'episodes': emitted - emitted0, 'env_steps': self._steps - steps0, 'plies': self.s - s0}
+
+
+class StreamGenerator(_StreamDriver):
     """Continuous batched self-play: E slots, each at its own ply; a finished game goes straight into the replay
     ring and its slot starts a new game (the reference's workers start an episode the moment one ends,
     generation.py:20-88, worker.py:58-77).  ``DeviceGenerator`` plays its E games in lockstep instead, and a
@@ -1054,22 +1179,8 @@ class StreamGenerator:
             raise ValueError('StreamGenerator plays the mover-only ply of an alternating env into a DeviceReplay; '
                              'per-player records, observation=True and simultaneous envs are played by the lockstep '
                              'generator (rollout.DeviceGenerator)')
-        if (replay.Tm, replay.P, replay.policy.shape[-1]) != (env_batch.MAX_PLIES, env_batch.P, env_batch.A):
-            raise ValueError('the replay does not have the env\'s MAX_PLIES, P and A')
-        self.env, self.net, self.replay = env_batch, net, replay
-        self.gamma, self.seed = float(gamma), int(seed) & 0xffffffffffffffff
-        self.check_every = max(1, int(check_every or 1))
-        self.graph = graph
-        self.s = 0                         # global steps run: the mover of step s is s % P
-        self.games_started = env_batch.E
-        self._emitted = 0
-        self._steps = 0                    # env-steps of the emitted episodes
-        self._st = None
-        self._graphs = None
-        self.ring_game = torch.full((replay.N,), -1, dtype=torch.long, device=env_batch.device)
-
-    def _use_graph(self):
-        return graph_wanted(self.env.device, self.graph)
+        super().__init__(env_batch, net, replay, gamma, seed, check_every, graph,
+                         'the replay does not have the env\'s MAX_PLIES, P and A')
 
     def _state(self):
         """The slots' buffers, allocated once: the games live in them across calls."""
@@ -1161,70 +1272,16 @@ class StreamGenerator:
         harvest = harvest_hip if fused else harvest_torch
         harvest(st, done, env.outcome(), self.gamma, self.replay, self.ring_game, has_reward)
 
-    def _capture(self, st):
-        """One graph per mover.  Warm-up plies run first on a side stream (library workspaces) and harvest
-        nothing; the games, the ring state and the recurrent state are then put back, so that warm-up and capture
-        leave no trace (a slot record the warm-up wrote is written again by the ply that owns it)."""
-        P = self.env.P
-        keep = [t.clone() for t in self._persistent(st)]
+    def _bodies(self, st, dry=False):
+        """One body per mover: step s runs the ply of mover s % P."""
+        return {m: functools.partial(self._ply, st, m, dry) for m in range(self.env.P)}
 
-        def warm():
-            for m in range(P):
-                self._ply(st, m, dry=True)
-        graphs = capture_graphs(self.env.device, {m: functools.partial(self._ply, st, m) for m in range(P)}, warm)
-        for t, k in zip(self._persistent(st), keep):
-            t.copy_(k)
-        return graphs
-
-    @torch.no_grad()
-    def generate(self, episodes):
-        """Run global steps until ``episodes`` more games have been emitted into the ring (checked every
-        ``check_every`` steps, so a call may overshoot).  Returns {'episodes': emitted by this call, 'env_steps':
-        the sum of their lengths, 'plies': global steps run}."""
-        st = self._state()
+    def _session(self, st):
         session = getattr(self.net, 'inference_session', None)
-        with eval_mode(self.net), \
-                session(inplace_state=st['pmajor']) if session is not None else contextlib.nullcontext():
-            return self._generate(st, int(episodes))
-
-    def _generate(self, st, episodes):
-        P, N = self.env.P, self.replay.N
-        graphs = None
-        if self._use_graph():
-            # a captured ply reads the net's parameters and buffers where they live: recapture if any moved (the
-            # games stay); the switch between the kernels and their torch formulation is part of the capture too
-            key = (FUSED_STREAM,) + params_key(self.net)
-            if self._graphs is None or self._graphs[0] != key:
-                self._graphs = (key, self._capture(st))
-            graphs = self._graphs[1]
-        emitted0, steps0, s0 = self._emitted, self._steps, self.s
-        target = emitted0 + episodes
-        emitted = emitted0
-        while emitted < target:
-            for _ in range(self.check_every):
-                if graphs is not None:
-                    graphs[self.s % P].replay()
-                else:
-                    self._ply(st, self.s % P)
-                self.s += 1
-            emitted = int(st['state'][1])
-        ring_ptr, emitted, next_game = (int(v) for v in st['state'].tolist())
-        self._steps = int(st['played'].sum()) - int(st['ply'].sum())   # all plies played less the games in flight
-        self.replay.ptr = ring_ptr
-        self.replay.count = min(self.replay.count + emitted - emitted0, N)
-        self._emitted, self.games_started = emitted, next_game
-        return {'episodes': emitted - emitted0, 'env_steps': self._steps - steps0, 'plies': self.s - s0}
+        return session(inplace_state=st['pmajor']) if session is not None else contextlib.nullcontext()
 
 
 # ---- streaming self-play of simultaneous-move envs: per-player records (PlayerStreamGenerator) ----
-
-def _record_players_at(buf, rows, ply, x, played):
-    """Slot (e, ply[e]) of ``buf`` (E, Tm, P, ...) becomes x[e] (P, ...) where played[e]; other games store nothing
-    (the index is clamped and the old value written back)."""
-    idx = ply.clamp(0, buf.shape[1] - 1)
-    keep = played.view(-1, *([1] * (x.dim() - 1)))
-    buf[rows, idx] = torch.where(keep, x.to(buf.dtype), buf[rows, idx])
-
 
 def sample_record_players_stream_torch(st, seed, logits, legal, value, turns, infer, active):
     """The per-player streaming ply's sampling and recording tail as torch ops (the contract of
@@ -1249,12 +1306,12 @@ def sample_record_players_stream_torch(st, seed, logits, legal, value, turns, in
     sampled = turns & played.view(E, 1)
     a = torch.where(sampled, a, torch.zeros_like(a))
     t3 = turns.view(E, P, 1)
-    _record_players_at(st['policy'], rows, ply, torch.where(t3, p, 0.0), played)
-    _record_players_at(st['amask'], rows, ply, torch.where(t3, m, 1e32), played)
-    _record_players_at(st['action'], rows, ply, a, played)
-    _record_players_at(st['tmask'], rows, ply, turns, played)
-    _record_players_at(st['value'], rows, ply, torch.where(infer, val, 0.0), played)
-    _record_players_at(st['omask'], rows, ply, infer, played)
+    _record_at(st['policy'], rows, ply, torch.where(t3, p, 0.0), played)
+    _record_at(st['amask'], rows, ply, torch.where(t3, m, 1e32), played)
+    _record_at(st['action'], rows, ply, a, played)
+    _record_at(st['tmask'], rows, ply, turns, played)
+    _record_at(st['value'], rows, ply, torch.where(infer, val, 0.0), played)
+    _record_at(st['omask'], rows, ply, infer, played)
     return a, stream_select_uniform_torch(seed, game, ply)
 
 
@@ -1291,98 +1348,7 @@ def sample_record_players_stream_hip(st, seed, logits, legal, value, turns, infe
     return a, usel
 
 
-def harvest_players_torch(st, done, outcome, gamma, replay, ring_game, has_reward=False):
-    """``harvest_torch`` for per-player records into a ``PlayerReplay`` (the contract of
-    hrl_selfplay_harvest_players, which equals this bit for bit): the same rows, the same order and restart; the
-    records carry a player axis, ``tmask`` / ``omask`` take the place of ``turn``, and an observation leaf is
-    converted as ``src.to(dst.dtype)``.  ``st``: the slot records and 'ply', 'game', 'pending', 'state', 'rows'."""
-    E, N, Tm = done.shape[0], replay.N, replay.Tm
-    dev = done.device
-    if dev.type == 'cpu' and not bool(done.any()):
-        return      # nothing changes; on the CPU the look costs nothing (a GPU call must not read the device)
-    state, ply, game = st['state'], st['ply'], st['game']
-    W = min(E, N)
-    d = done.long()
-    r = torch.cumsum(d, 0) - d
-    c = d.sum()
-    e_idx = st['rows']
-    order = torch.empty_like(e_idx).scatter_(0, torch.where(done, r, c + (e_idx - r)), e_idx)   # done slots first
-    k = torch.arange(W, device=dev)
-    written = k < c
-    last = k + N * torch.div(torch.clamp(c - 1 - k, min=0), N, rounding_mode='floor')
-    slot = order[torch.where(written, last, k)]
-    rows = (state[0] + k) % N
-    L = ply[slot].clamp(0, Tm)
-    valid = torch.arange(Tm, device=dev).view(1, Tm) < L.view(W, 1)
-
-    def put(dst, new):
-        w = written.view(W, *([1] * (new.dim() - 1)))
-        dst.index_copy_(0, rows, torch.where(w, new.to(dst.dtype), dst.index_select(0, rows)))
-
-    def plies(src, fill=0):
-        v = valid.view(W, Tm, *([1] * (src.dim() - 2)))
-        return torch.where(v, src.index_select(0, slot), fill)
-    bimap_r(replay.obs, st['obs'], lambda dst, src: put(dst, plies(src).to(dst.dtype)))
-    put(replay.policy, plies(st['policy']))
-    put(replay.amask, plies(st['amask'], 1e32))
-    for key in ('action', 'value', 'tmask', 'omask'):
-        put(getattr(replay, key), plies(st[key]))
-    rew = plies(st['reward']) if has_reward else torch.zeros(W, Tm, replay.P, dtype=torch.float64, device=dev)
-    put(replay.reward, rew.float())
-    ret = torch.zeros(W, Tm, replay.P, device=dev)
-    acc = torch.zeros_like(rew[:, 0])
-    for t in range(Tm - 1, -1, -1):       # DeviceGenerator._returns: fp64 from the top
-        acc = rew[:, t] + gamma * acc
-        ret[:, t].copy_(acc)
-    put(replay.ret, ret)
-    put(replay.length, L)
-    put(replay.outcome, outcome.index_select(0, slot))
-    put(ring_game, game.index_select(0, slot))
-    game.copy_(torch.where(done, state[2] + r, game))
-    ply.masked_fill_(done, 0)
-    st['pending'].logical_or_(done)
-    state[0:1].copy_(((state[0] + c) % N).view(1))
-    state[1:3].add_(c)
-
-
-def _obs_type(t):
-    from . import _native
-    if t.dtype not in (torch.uint8, torch.float32):
-        raise ValueError('observation records are uint8 or float32, not %s' % t.dtype)
-    return _native.REPLAY_F32 if t.dtype == torch.float32 else _native.REPLAY_U8
-
-
-def harvest_players_hip(st, done, outcome, gamma, replay, ring_game, has_reward=False):
-    """harvest_players_torch as the two launches of hrl_selfplay_harvest_players."""
-    from . import _native
-    E, Tm, P, A = st['policy'].shape
-    src = _leaves(st['obs'])
-    slots = _native.SelfplayPlayerSlots()
-    slots.E, slots.Tm, slots.P, slots.A, slots.nleaves = E, Tm, P, A, len(src)
-    if len(src) > _native.REPLAY_MAX_LEAVES:
-        raise ValueError('at most %d observation leaves' % _native.REPLAY_MAX_LEAVES)
-    for l, o in enumerate(src):
-        assert o.is_contiguous() and o.shape[:3] == (E, Tm, P)
-        slots.obs[l] = o.data_ptr()
-        slots.obs_type[l] = _obs_type(o)
-        slots.obs_width[l] = int(np.prod(o.shape[3:], dtype=np.int64))
-    for k in ('policy', 'amask', 'action', 'value', 'tmask', 'omask'):
-        assert st[k].is_contiguous()
-        setattr(slots, k, st[k].data_ptr())
-    slots.reward = st['reward'].data_ptr() if has_reward else None
-    done, outcome = done.contiguous(), outcome.float().contiguous()
-    assert done.shape == (E,) and done.dtype == torch.bool and outcome.shape == (E, replay.P)
-    assert st['tmask'].dtype == st['omask'].dtype == torch.bool and st['action'].dtype == torch.long
-    assert st['pending'].dtype == torch.bool and st['state'].shape == (3,) and st['state'].dtype == torch.long
-    assert ring_game.shape == (replay.N,) and ring_game.dtype == torch.long and ring_game.is_contiguous()
-    ring = _ring_struct(replay)
-    _native.check(_native.load().hrl_selfplay_harvest_players(
-        _native.ptr(done), ctypes.byref(slots), _native.ptr(st['ply']), _native.ptr(outcome), float(gamma),
-        ctypes.byref(ring), _native.ptr(ring_game), _native.ptr(st['game']), _native.ptr(st['pending']),
-        _native.ptr(st['state']), _native.stream_of(done.device)), 'hrl_selfplay_harvest_players')
-
-
-class PlayerStreamGenerator:
+class PlayerStreamGenerator(_StreamDriver):
     """``StreamGenerator`` for simultaneous-move envs (``SIMULTANEOUS``: Hungry Geese, ParallelTicTacToe): E slots,
     each at its own ply, every player moving every ply; a finished game goes straight into a ``PlayerReplay`` ring
     and its slot starts the next game on the very next step (a simultaneous env has no mover parity to wait for).
@@ -1412,25 +1378,11 @@ class PlayerStreamGenerator:
             raise ValueError('PlayerStreamGenerator plays a simultaneous-move env with a net without recurrent state '
                              'into a PlayerReplay; alternating envs stream through rollout.StreamGenerator, and '
                              'everything else is played by the lockstep generator (rollout.DeviceGenerator)')
-        if (replay.Tm, replay.P, replay.policy.shape[-1]) != (env_batch.MAX_PLIES, env_batch.P, env_batch.A):
-            raise ValueError('the replay does not have the env\'s MAX_PLIES, P and A; the lockstep generator '
-                             '(rollout.DeviceGenerator) returns episodes of any replay\'s shape')
+        super().__init__(env_batch, net, replay, gamma, seed, check_every, graph,
+                         'the replay does not have the env\'s MAX_PLIES, P and A; the lockstep generator '
+                         '(rollout.DeviceGenerator) returns episodes of any replay\'s shape')
         _player_blocks(env_batch.P, env_batch.A)
-        self.env, self.net, self.replay = env_batch, net, replay
-        self.gamma, self.seed = float(gamma), int(seed) & 0xffffffffffffffff
-        self.check_every = max(1, int(check_every or 1))
-        self.graph = graph
         self.observation = bool(observation)
-        self.s = 0                         # global steps run
-        self.games_started = env_batch.E
-        self._emitted = 0
-        self._steps = 0                    # env-steps of the emitted episodes
-        self._st = None
-        self._graphs = None
-        self.ring_game = torch.full((replay.N,), -1, dtype=torch.long, device=env_batch.device)
-
-    def _use_graph(self):
-        return graph_wanted(self.env.device, self.graph)
 
     def _state(self):
         """The slots' buffers, allocated once: the games live in them across calls.  Every slot starts ``pending``
@@ -1487,7 +1439,7 @@ class PlayerStreamGenerator:
 
             def record(buf, v):
                 keep = infer.view(E, P, *([1] * (v.dim() - 2)))
-                _record_players_at(buf, rows, ply, torch.where(keep, v, 0.0), played)
+                _record_at(buf, rows, ply, torch.where(keep, v, 0.0), played)
             bimap_r(st['obs'], _stack_views(views, batch_first=True), record)
         out = self.net(o, None)
         legal = env.legal_players() if hasattr(env, 'legal_players') else env.legal()
@@ -1496,7 +1448,7 @@ class PlayerStreamGenerator:
         env.step_players(a, turns, active, usel)
         has_reward = 'reward' in st
         if has_reward:
-            _record_players_at(st['reward'], rows, ply, env.reward().to(st['reward'].dtype), active & (ply < Tm))
+            _record_at(st['reward'], rows, ply, env.reward().to(st['reward'].dtype), active & (ply < Tm))
         ply.add_(active)
         st['played'].add_(active)
         done = active & (env.terminal() | (ply >= Tm))
@@ -1505,57 +1457,20 @@ class PlayerStreamGenerator:
         harvest = harvest_players_hip if fused else harvest_players_torch
         harvest(st, done, env.outcome(), self.gamma, self.replay, self.ring_game, has_reward)
 
-    def _capture(self, st):
-        """The step as one graph.  A warm-up step runs first on a side stream (library workspaces) and harvests
-        nothing; the games and the ring state are then put back, so that warm-up and capture leave no trace (a slot
-        record the warm-up wrote is written again by the ply that owns it)."""
-        keep = [t.clone() for t in self._persistent(st)]
-        graphs = capture_graphs(self.env.device, {None: functools.partial(self._ply, st)},
-                                functools.partial(self._ply, st, True))
-        for t, k in zip(self._persistent(st), keep):
-            t.copy_(k)
-        return graphs
+    def _bodies(self, st, dry=False):
+        """Every player moves every ply: one body."""
+        return {0: functools.partial(self._ply, st, dry)}
 
-    @torch.no_grad()
-    def generate(self, episodes):
-        """Run global steps until ``episodes`` more games have been emitted into the ring (checked every
-        ``check_every`` steps, so a call may overshoot).  Returns {'episodes': emitted by this call, 'env_steps':
-        the sum of their lengths, 'plies': global steps run}."""
-        st = self._state()
-        session = (getattr(self.net, 'inference_session', None)
-                   if getattr(self.net, 'stateless_session', False) else None)
-        with eval_mode(self.net), session() if session is not None else contextlib.nullcontext():
-            return self._generate(st, int(episodes))
+    def _session(self, st):
+        stateless = getattr(self.net, 'stateless_session', False)
+        session = getattr(self.net, 'inference_session', None) if stateless else None
+        return session() if session is not None else contextlib.nullcontext()
 
     def _generate(self, st, episodes):
-        N = self.replay.N
-        graph = None
-        if self._use_graph():
-            # a captured step reads the net's parameters and buffers where they live: recapture if any moved (the
-            # games stay); the switch between the kernels and their torch formulation is part of the capture too
-            key = (FUSED_STREAM,) + params_key(self.net)
-            if self._graphs is None or self._graphs[0] != key:
-                self._graphs = (key, self._capture(st))
-            graph = self._graphs[1][None]
-        emitted0, steps0, s0 = self._emitted, self._steps, self.s
-        target = emitted0 + episodes
-        emitted = emitted0
-        while emitted < target:
-            for _ in range(self.check_every):
-                if graph is not None:
-                    graph.replay()
-                else:
-                    self._ply(st)
-                self.s += 1
-            emitted = int(st['state'][1])
-        ring_ptr, emitted, next_game = (int(v) for v in st['state'].tolist())
-        self._steps = int(st['played'].sum()) - int(st['ply'].sum())   # all plies played less the games in flight
-        self.replay.ptr = ring_ptr
-        self.replay.count = min(self.replay.count + emitted - emitted0, N)
-        self._emitted, self.games_started = emitted, next_game
+        out = super()._generate(st, episodes)
         if hasattr(self.env, 'next_game'):
-            self.env.next_game = next_game
-        return {'episodes': emitted - emitted0, 'env_steps': self._steps - steps0, 'plies': self.s - s0}
+            self.env.next_game = self.games_started
+        return out
 
 
 # True: on a GPU ``gather`` is the one launch of hrl_replay_gather (include/hrl_replay.h) instead of the torch ops

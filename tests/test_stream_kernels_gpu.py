@@ -106,6 +106,7 @@ def _harvest_case(dev, obs_dtype, pattern, reward, N=7, ring_ptr=5):
 def _run_harvest(case, dev, maker, fn, obs_dtype):
     keep = (lambda t: t.clone().to(dev)) if maker is None else maker.inout
     rec = case['rec']
+    E, TM = rec['action'].shape
     st = {k: v.to(dev) for k, v in rec.items() if k != 'obs'}
     st['obs'] = {k: v.to(dev) for k, v in rec['obs'].items()}
     st.update(ply=keep(case['ply']), game=keep(case['game']), pending=keep(case['pending']),
@@ -180,6 +181,48 @@ def test_harvest_matches_a_sequential_emission(cuda):
     for k, v in want.items():
         _eq(got[k], v.to(cuda), k)
     _eq(got['ring_game'], want_game.to(cuda), 'ring_game')
+
+
+@pytest.mark.parametrize('reward', [True, False])
+@pytest.mark.parametrize('obs_dtype', [torch.uint8, torch.float32])
+def test_harvest_copy_units_and_an_empty_episode(cuda, obs_dtype, reward):
+    """The mover harvest at the smallest shape that has every kind of record and length: Tm = 6 with leaves of widths
+    2, 6 and 1 gives records of 12 and 36 elements per slot (16 bytes per lane, and L * width = 2, 6, 10, 18, 30 is
+    no multiple of four for L = 1, 3, 5, so the validity bound falls inside a lane's four elements) and one of 6
+    (element by element); policy and amask have 12, value 6.  Every slot is done, with lengths 0 (the whole row is
+    reset values), 1, 3, 5 and Tm; five rows from ring_ptr = 6 of N = 8 wrap, rows 3..5 keep their prefill.  Against
+    harvest_torch, bit for bit."""
+    n, Tm, P, A, N = 5, 6, 2, 2, 8
+    g = torch.Generator().manual_seed(12 + reward)
+    shape = {'pair': (2,), 'six': (2, 3), 'one': (1,)}
+    rec = {'obs': {k: torch.randint(0, 256, (n, Tm) + s, generator=g).float() for k, s in shape.items()},
+           'policy': torch.randn(n, Tm, A, generator=g), 'amask': torch.randn(n, Tm, A, generator=g),
+           'action': torch.randint(0, A, (n, Tm), generator=g), 'value': torch.randn(n, Tm, generator=g),
+           'turn': torch.randint(0, P, (n, Tm), generator=g),
+           'reward': torch.randn(n, Tm, P, generator=g, dtype=torch.float64)}
+    replay = DeviceReplay(N, Tm, shape, A, P, 'cpu', obs_dtype=obs_dtype)
+    ring = {k: torch.randn(getattr(replay, k).shape, generator=g) for k in ('policy', 'amask', 'value', 'reward',
+                                                                             'ret', 'outcome')}
+    ring.update({k: torch.randint(0, 5, getattr(replay, k).shape, generator=g) for k in ('action', 'turn', 'length')})
+    ring['obs'] = {k: torch.randint(0, 256, v.shape, generator=g).to(obs_dtype) for k, v in replay.obs.items()}
+    case = dict(rec=rec, done=torch.ones(n, dtype=torch.bool), ply=torch.tensor([3, 0, Tm, 1, 5]),
+                state=torch.tensor([6, 100, 1000]), game=torch.arange(n) * 3 + 50,
+                pending=torch.zeros(n, dtype=torch.bool), outcome=torch.randn(n, P, generator=g), ring=ring,
+                ring_game=torch.randint(0, 40, (N,), generator=g), shape=shape, A=A, P=P, N=N, reward=reward)
+    ref = _run_harvest(case, cuda, None, rollout.harvest_torch, obs_dtype)
+    for maker in (Arena(cuda), Plain(cuda)):
+        got = _run_harvest(case, cuda, maker, rollout.harvest_hip, obs_dtype)
+        for k in ref:
+            _eq(got[k], ref[k], k)
+    assert ref['state'].tolist() == [3, 105, 1005]
+    assert ref['length'][[6, 7, 0, 1, 2]].tolist() == [3, 0, Tm, 1, 5]
+    assert ref['ring_game'][[6, 7, 0, 1, 2]].tolist() == [50, 53, 56, 59, 62]
+    for k, v in ring.items():                     # the rows the call does not claim keep their prefill
+        for kk, vv in (v.items() if k == 'obs' else [(None, v)]):
+            _eq(ref[k if kk is None else 'obs.' + kk][3:6], vv[3:6].to(cuda), (k, kk))
+    for k in ('policy', 'value', 'action', 'turn', 'reward', 'ret', 'obs.pair', 'obs.six', 'obs.one'):
+        assert not bool(ref[k][7].any()), k        # the empty episode's row: reset values only
+    assert bool((ref['amask'][7] == 1e32).all())
 
 
 @pytest.mark.parametrize('Tm,P', [(1100, 2), (3, 300), (700, 3)])
