@@ -28,6 +28,11 @@ ARCH = os.environ.get('HRL_OFFLOAD_ARCH', 'gfx950')
 HIPCC_FLAGS = ['--offload-arch=%s' % ARCH, '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off',
                '-Wall', '-Wno-unused-function', '-I', INCLUDE]
 
+# per-source additions: hrl_geesenet_bf16.hip's fp32 epilogue is written operation by operation on float4 values;
+# its device code is compiled without the packed fp32 VALU forms (v_pk_*_f32), one scalar instruction per operation
+# (the host pass does not know the feature and ignores it)
+EXTRA_FLAGS = {'hrl_geesenet_bf16.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']}
+
 
 def hipcc():
     exe = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
@@ -70,7 +75,7 @@ def _compile(src):
     hdr_mtime = max(os.path.getmtime(h) for h in hdrs)
     if os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(src), hdr_mtime):
         return obj
-    cmd = [hipcc()] + HIPCC_FLAGS + ['-c', src, '-o', obj]
+    cmd = [hipcc()] + HIPCC_FLAGS + EXTRA_FLAGS.get(os.path.basename(src), []) + ['-c', src, '-o', obj]
     res = subprocess.run(cmd, capture_output=True, text=True)
     if res.returncode != 0:
         raise RuntimeError('hipcc failed for %s:\n%s\n%s' % (src, ' '.join(cmd), res.stderr))

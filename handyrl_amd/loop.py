@@ -18,7 +18,7 @@ import time
 
 import torch
 
-from .nn import BoardInference
+from .nn import BoardInference, configured_inference
 from .rollout import DeviceGenerator, DeviceReplay, StreamGenerator, TicTacToeBatch
 from .trainer import LearnerStep
 from .util import map_r
@@ -32,7 +32,8 @@ class SelfPlayTrainer:
     ``rollout.StreamGenerator`` (``games_per_round`` slots that restart in place; a round plays until that many
     more games are in the ring) instead of the lockstep ``DeviceGenerator``.  ``fused_inference``: self-play runs
     ``nn.BoardInference(net)`` (``play_net``, also the net to hand to ``evaluate_vs_random``); the learner trains
-    ``net`` itself.  ``fused_game`` (with ``fused_inference``, without ``stream``): the lockstep generator plays a whole
+    ``net`` itself; ``fused_inference='fused_bf16'`` (a GeeseNet on a CUDA device) runs
+    ``nn.GeeseInference(net, precision='bf16')`` instead.  ``fused_game`` (with ``fused_inference``, without ``stream``): the lockstep generator plays a whole
     round in one launch (``DeviceGenerator(fused_game=True)``), the same episodes bit for bit."""
 
     def __init__(self, net, args, device, games_per_round=4096, capacity=65536, graph=False, seed=0,
@@ -49,7 +50,10 @@ class SelfPlayTrainer:
                                    maximum_episodes=args.get('maximum_episodes', capacity), obs_dtype=obs_dtype)
         self.stream = bool(stream)
         # the net as self-play runs it: itself, or its one-launch eval forward (the learner trains `net` itself)
-        self.play_net = BoardInference(net) if fused_inference else net
+        if fused_inference == 'fused_bf16':   # GeeseNet's bf16 one-launch forward (nn.configured_inference's rules)
+            self.play_net = configured_inference('fused_bf16', [net], device)[0]
+        else:
+            self.play_net = BoardInference(net) if fused_inference else net
         if self.stream:
             self.gen = StreamGenerator(self.env, self.play_net, self.replay, gamma=args['gamma'], seed=seed)
         else:

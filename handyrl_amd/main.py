@@ -205,7 +205,8 @@ def train_main(args, device=None, loss_fn=None, model_dir='models', log=print):
                                        weights_only=True))
     net = net.to(device)
     # train_args['inference']: fused -- self-play and the per-epoch evaluation run the net's one-launch eval forward
-    # (nn.BoardInference, which refers to `net`); the learner trains `net` itself.  Absent: `net` plays as it is
+    # (nn.BoardInference / nn.GeeseInference, which refer to `net`; fused_bf16: GeeseNet's bf16 form); the learner
+    # trains `net` itself.  Absent: `net` plays as it is
     from .nn import configured_inference
     infer_mode = targs.get('inference')
     play_net = configured_inference(infer_mode, [net], device)[0]

@@ -2849,13 +2849,21 @@ class GeeseInference:
     keeps its address, so a captured ply stays valid and a later session refreshes the weights in place.  Inside a
     session a CUDA fp32 observation batch (N, 17, H, W) with H*W <= 80 is the native forward; a CPU batch runs
     ``net``'s own forward.  Training mode, or the GPU outside a session, raises: there is no other GPU path.
+
+    ``precision='bf16'`` is the actor's form (hrl_geesenet_infer_bf16, csrc/hrl_geesenet_bf16.hip): ONE launch per
+    forward and no workspace; the conv weights and conv inputs are bf16, everything else fp32 (include/hrl_nn.h has
+    the contract).  Sessions, the pack's fixed address and the CPU path are the same.
     """
 
     stateless_session = True   # nothing to advance in place: generators may enter the session in any mode
 
-    def __init__(self, net):
+    def __init__(self, net, precision='fp32'):
         if not geese_inference_ok(net):
             raise ValueError('GeeseInference: not a GeeseNet-shaped net (geese_inference_ok)')
+        if precision not in ('fp32', 'bf16'):
+            raise ValueError("GeeseInference: precision is 'fp32' or 'bf16', not %r" % (precision,))
+        self.precision = precision
+        self._entry = 'hrl_geesenet_infer' if precision == 'fp32' else 'hrl_geesenet_infer_bf16'
         self.net = net
         self.layers = len(net.blocks)
         self._buf = None
@@ -2890,12 +2898,12 @@ class GeeseInference:
     def pack(self, device=None):
         """The pack buffer (pack_bytes uint8) on ``device``: allocated once, the same storage ever after."""
         if self._buf is None or (device is not None and self._buf.device != torch.device(device)):
-            nbytes = _native.load().hrl_geesenet_infer_pack_bytes(self.layers)
+            nbytes = getattr(_native.load(), self._entry + '_pack_bytes')(self.layers)
             self._buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
         return self._buf
 
     def _refresh(self, dev):
-        """hrl_geesenet_infer_pack from the net's tensors into the pack."""
+        """hrl_geesenet_infer_pack (or the bf16 form's) from the net's tensors into the pack."""
         units, hp, hv = _geese_infer_parts(self.net)
         per = [[u.conv.weight for u in units], [u.conv.bias for u in units], [u.bn.weight for u in units],
                [u.bn.bias for u in units], [u.bn.running_mean for u in units], [u.bn.running_var for u in units]]
@@ -2903,9 +2911,9 @@ class GeeseInference:
             if not (t.device == dev and t.dtype == torch.float32 and t.is_contiguous()):
                 raise ValueError('GeeseInference: the net\'s tensors must be contiguous fp32 on one device')
         eps = (ctypes.c_double * len(units))(*[float(u.bn.eps) for u in units])
-        _native.check(_native.load().hrl_geesenet_infer_pack(
+        _native.check(getattr(_native.load(), self._entry + '_pack')(
             *[_native.ptr_array(ts) for ts in per], eps, self.layers, _native.ptr(hp.weight), _native.ptr(hv.weight),
-            _native.ptr(self.pack(dev)), _native.stream_of(dev)), 'hrl_geesenet_infer_pack')
+            _native.ptr(self.pack(dev)), _native.stream_of(dev)), self._entry + '_pack')
 
     @contextlib.contextmanager
     def inference_session(self, inplace_state=False):
@@ -2939,6 +2947,11 @@ class GeeseInference:
         value = torch.empty(N, 1, device=obs.device)
         if N == 0:
             return {'policy': policy, 'value': value}
+        if self.precision == 'bf16':
+            _native.check(lib.hrl_geesenet_infer_bf16(
+                _native.ptr(self.pack(obs.device)), self.layers, _native.ptr(o), N, H, W, _native.ptr(policy),
+                _native.ptr(value), _native.stream_of(obs.device)), 'hrl_geesenet_infer_bf16')
+            return {'policy': policy, 'value': value}
         nbytes = lib.hrl_geesenet_infer_workspace_bytes(N, H, W)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=obs.device)
         _native.check(lib.hrl_geesenet_infer(
@@ -2950,15 +2963,22 @@ class GeeseInference:
 def configured_inference(mode, nets, device):
     """``train_args['inference']`` applied to the nets that play: absent / None leaves them as they are; ``fused``
     wraps each TicTacToe net in ``BoardInference`` (several: one ``board_inference_group``) and each GeeseNet in
-    ``GeeseInference`` (each on its own).  Anything the fused forward cannot run, or a list mixing the two kinds,
-    raises here, at start-up, by the key's name."""
+    ``GeeseInference`` (each on its own); ``fused_bf16`` is GeeseNets only, each in
+    ``GeeseInference(net, precision='bf16')``.  Anything the fused forward cannot run, or a list mixing the two
+    kinds, raises here, at start-up, by the key's name."""
     if mode is None:
         return nets
-    if mode != 'fused':
-        raise ValueError("train_args['inference'] must be fused (or absent), not %r" % (mode,))
+    if mode not in ('fused', 'fused_bf16'):
+        raise ValueError("train_args['inference'] must be fused or fused_bf16 (or absent), not %r" % (mode,))
     if torch.device(device).type != 'cuda':
-        raise ValueError("train_args['inference']: 'fused' is the one-launch forward on the GPU; the device is %s"
-                         % (device,))
+        raise ValueError("train_args['inference']: %r is the one-launch forward on the GPU; the device is %s"
+                         % (mode, device))
+    if mode == 'fused_bf16':
+        for net in nets:
+            if not geese_inference_ok(net):
+                raise ValueError("train_args['inference']: 'fused_bf16' forwards GeeseNet (32 filters, 1..16 blocks); "
+                                 "%s is not one (geese_inference_ok)" % type(net).__name__)
+        return [GeeseInference(net, precision='bf16') for net in nets]
     if nets and all(geese_inference_ok(net) for net in nets):
         return [GeeseInference(net) for net in nets]
     for net in nets:

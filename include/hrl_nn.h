@@ -672,6 +672,32 @@ int hrl_geesenet_infer(const void *pack, int64_t layers, const float *x, int64_t
                        float *policy, float *value, void *ws, int64_t ws_bytes, void *stream);
 int hrl_geesenet_infer_set_form(int form);
 
+/* GeeseNet's eval forward with bf16 conv operands, ONE launch per forward (csrc/hrl_geesenet_bf16.hip): the actor's
+ * form of the tower above.  Same nets, boards and calling rules (asynchronous, no allocation, capturable, arguments
+ * validated before any HIP call).
+ * Numerics: the conv weights are rounded once, at pack time, fp32 -> bf16 (round to nearest even); the conv input of
+ *   unit u is bf16(h_u) (the observation's 0/1 planes are exact); the MFMA accumulates in fp32; alpha, beta and the
+ *   conv bias are the tower's, and h_{u+1} = relu([h_u +] (acc + bias)*alpha + beta) in fp32, in the tower's
+ *   operation order.  The residual stream h is fp32 and is never rounded: only the copy that feeds the next conv is
+ *   bf16.  Pool, heads and tanhf run on the last unit's fp32 h.
+ * hrl_geesenet_infer_bf16_pack_bytes: the bytes of one packed net (a multiple of 16; 0 for layers outside 1..16).
+ * hrl_geesenet_infer_bf16_pack: hrl_geesenet_infer_pack's arguments; ONE launch that writes, per unit, the bf16
+ *   MFMA row operands in the order the forward reads them (18,432 B) and alpha | beta | bias fp32 (384 B), then
+ *   head_p | head_v fp32.  HRL_EINVAL as hrl_geesenet_infer_pack.
+ * hrl_geesenet_infer_bf16: x (N, 17, H, W) fp32 contiguous; policy (N, 4) raw logits, value (N, 1) the tanh.  No
+ *   workspace: a wave keeps its sample's bf16 conv input in LDS and its fp32 h in registers through every unit, the
+ *   workgroup's 8 waves share each unit's weights, and a row's only memory traffic is x in and 5 floats out.
+ *   Nothing is shared or awaited between workgroups.  A row's result does not depend on N or on its place in the
+ *   batch.  Deterministic.  N == 0: HRL_OK, no launch.  HRL_EINVAL for a NULL pack, x, policy or value, a pack that
+ *   is not 16-byte aligned, layers outside 1..16, N < 0, H or W < 1, H*W > 80. */
+int64_t hrl_geesenet_infer_bf16_pack_bytes(int64_t layers);
+int hrl_geesenet_infer_bf16_pack(const float *const *conv_w, const float *const *conv_b, const float *const *bn_w,
+                                 const float *const *bn_b, const float *const *bn_mean, const float *const *bn_var,
+                                 const double *bn_eps, int64_t layers, const float *head_p, const float *head_v,
+                                 void *pack, void *stream);
+int hrl_geesenet_infer_bf16(const void *pack, int64_t layers, const float *x, int64_t N, int64_t H, int64_t W,
+                            float *policy, float *value, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
