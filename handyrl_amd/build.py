@@ -31,7 +31,8 @@ HIPCC_FLAGS = ['--offload-arch=%s' % ARCH, '-O3', '-std=c++17', '-fPIC', '-ffp-c
 # per-source additions: hrl_geesenet_bf16.hip's fp32 epilogue is written operation by operation on float4 values;
 # its device code is compiled without the packed fp32 VALU forms (v_pk_*_f32), one scalar instruction per operation
 # (the host pass does not know the feature and ignores it)
-EXTRA_FLAGS = {'hrl_geesenet_bf16.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']}
+_NO_PACKED_FP32 = ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']
+EXTRA_FLAGS = {'hrl_geesenet_bf16.hip': _NO_PACKED_FP32, 'hrl_geister_infer.hip': _NO_PACKED_FP32}
 
 
 def hipcc():

@@ -2960,16 +2960,192 @@ class GeeseInference:
         return {'policy': policy, 'value': value}
 
 
+# ---------------------------------------------------------------- one-launch recurrent GeisterNet inference
+def _geister_infer_parts(net):
+    """The modules of a GeisterNet-shaped net (envs/geister.py) that csrc/hrl_geister_infer.hip forwards, or None:
+    bias-free stem Conv2d(25, 32, 3, padding=1) + BatchNorm2d(32); ``body.blocks`` 1..4 cells, each a 3x3 padded
+    Conv2d(64, 128) with 32 hidden channels, all biased or all bias-free; ``num_repeats`` 1..8; move head 3x3
+    Conv2d(64, p) + BatchNorm2d(p) + 1x1 Conv2d(p, 4), p in {1, 2, 4, 8}; ``head_p_set`` Linear(1, 70) with bias;
+    value / return heads 1x1 Conv2d(64, 1) + BatchNorm2d(1) + bias-free Linear(36, 1).  Checked by structure: the
+    same before and after ``accelerate``."""
+    def conv_ok(c, cin, cout, k, bias=False):
+        return (isinstance(c, nn.Conv2d) and c.in_channels == cin and c.out_channels == cout
+                and tuple(c.kernel_size) == (k, k) and tuple(c.stride) == (1, 1) and tuple(c.dilation) == (1, 1)
+                and c.groups == 1 and c.padding_mode == 'zeros' and isinstance(c.padding, tuple)
+                and tuple(c.padding) == (k // 2, k // 2) and (bias is None or (c.bias is not None) == bias))
+
+    def bn_ok(bn, C):
+        return (isinstance(bn, nn.BatchNorm2d) and bn.num_features == C and bn.affine and bn.track_running_stats
+                and bn.running_mean is not None and bn.running_var is not None)
+
+    def scalar_head_ok(m):
+        fc = getattr(m, 'fc', None)
+        return (conv_ok(getattr(m, 'conv', None), 64, 1, 1) and bn_ok(getattr(m, 'bn', None), 1)
+                and isinstance(fc, nn.Linear) and fc.in_features == 36 and fc.out_features == 1 and fc.bias is None)
+
+    cells = getattr(getattr(net, 'body', None), 'blocks', None)
+    hp, ps = getattr(net, 'head_p_move', None), getattr(net, 'head_p_set', None)
+    if not (hasattr(net, 'init_hidden') and hasattr(net, 'inference_hidden') and conv_ok(getattr(net, 'conv1', None),
+            25, 32, 3) and bn_ok(getattr(net, 'bn1', None), 32)):
+        return None
+    if not isinstance(cells, nn.ModuleList) or not 1 <= len(cells) <= 4:
+        return None
+    if not isinstance(getattr(net, 'num_repeats', None), int) or not 1 <= net.num_repeats <= 8:
+        return None
+    biased = getattr(cells[0], 'conv', None) is not None and cells[0].conv.bias is not None
+    if not all(conv_ok(getattr(c, 'conv', None), 64, 128, 3, biased) and getattr(c, 'hidden_dim', None) == 32
+               for c in cells):
+        return None
+    pf = getattr(getattr(hp, 'conv1', None), 'out_channels', None)
+    if not (pf in (1, 2, 4, 8) and conv_ok(hp.conv1, 64, pf, 3) and bn_ok(getattr(hp, 'bn', None), pf)
+            and conv_ok(getattr(hp, 'conv2', None), pf, 4, 1)):
+        return None
+    if not (isinstance(ps, nn.Linear) and ps.in_features == 1 and ps.out_features == 70 and ps.bias is not None):
+        return None
+    if not (scalar_head_ok(getattr(net, 'head_v', None)) and scalar_head_ok(getattr(net, 'head_r', None))):
+        return None
+    return list(cells), pf
+
+
+def geister_inference_ok(net):
+    """True for a net ``GeisterInference`` can forward (a GeisterNet-shaped module: 32 filters, 1..4 layers,
+    1..8 repeats, p_filters in {1, 2, 4, 8})."""
+    return _geister_infer_parts(net) is not None
+
+
+class GeisterInference(GeeseInference):
+    """GeisterNet as the generators and evaluators use one, its eval forward ONE launch (hrl_geister_infer) with the
+    recurrent state on chip; the fp32-accurate arithmetic of the module path.
+
+    The surface is ``GeeseInference``'s plus the recurrent hooks: ``init_hidden`` and ``inference_hidden`` are the
+    net's own (the same player-major stacked layout), and ``inference_session(inplace_state=False)`` packs the
+    net's current tensors (one hrl_geister_infer_pack launch) into a buffer that keeps its address.  In an
+    ``inplace_state`` session a state given in the stacked contiguous layout is advanced in place and returned as
+    views of itself (as ``DRC._inference_stacked`` does); any other state (separate leaves, ``None``) is stacked,
+    the new state written to fresh tensors and returned as channel slices.  A CPU batch runs ``net``'s own forward;
+    training mode, or the GPU outside a session, raises.
+    """
+
+    stateless_session = False   # the session decides whether the state is advanced in place
+
+    def __init__(self, net):
+        parts = _geister_infer_parts(net)
+        if parts is None:
+            raise ValueError('GeisterInference: not a GeisterNet-shaped net (geister_inference_ok)')
+        self.net = net
+        self.layers, self.p_filters = len(parts[0]), parts[1]
+        self._buf = None
+        self._live = 0
+        self._inplace = False
+
+    def init_hidden(self, batch_size=None):
+        return self.net.init_hidden(batch_size)
+
+    def inference_hidden(self, E, P, device):
+        return self.net.inference_hidden(E, P, device)
+
+    def pack(self, device=None):
+        """The pack buffer (pack_bytes uint8) on ``device``: allocated once, the same storage ever after."""
+        if self._buf is None or (device is not None and self._buf.device != torch.device(device)):
+            nbytes = _native.load().hrl_geister_infer_pack_bytes(self.layers, self.p_filters)
+            self._buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        return self._buf
+
+    def _refresh(self, dev):
+        """hrl_geister_infer_pack from the net's tensors into the pack."""
+        net = self.net
+        cells, pf = _geister_infer_parts(net)
+        bns = [net.bn1, net.head_p_move.bn, net.head_v.bn, net.head_r.bn]
+        cell_w = [c.conv.weight for c in cells]
+        cell_b = [c.conv.bias for c in cells]
+        per = [[b.weight for b in bns], [b.bias for b in bns], [b.running_mean for b in bns],
+               [b.running_var for b in bns]]
+        single = [net.conv1.weight, net.head_p_move.conv1.weight, net.head_p_move.conv2.weight,
+                  net.head_v.conv.weight, net.head_r.conv.weight, net.head_v.fc.weight, net.head_r.fc.weight,
+                  net.head_p_set.weight, net.head_p_set.bias]
+        for t in single + cell_w + [b for b in cell_b if b is not None] + [t for ts in per for t in ts]:
+            if not (t.device == dev and t.dtype == torch.float32 and t.is_contiguous()):
+                raise ValueError('GeisterInference: the net\'s tensors must be contiguous fp32 on one device')
+        stem, w1, w2, wv, wr, fcv, fcr, sw, sb = single
+        eps = (ctypes.c_double * 4)(*[float(b.eps) for b in bns])
+        _native.check(_native.load().hrl_geister_infer_pack(
+            _native.ptr(stem), _native.ptr_array(cell_w), _native.ptr_array(cell_b), self.layers,
+            *[_native.ptr_array(ts) for ts in per], eps, _native.ptr(w1), _native.ptr(w2), pf, _native.ptr(wv),
+            _native.ptr(wr), _native.ptr(fcv), _native.ptr(fcr), _native.ptr(sw), _native.ptr(sb),
+            _native.ptr(self.pack(dev)), _native.stream_of(dev)), 'hrl_geister_infer_pack')
+
+    @contextlib.contextmanager
+    def inference_session(self, inplace_state=False):
+        """Pack the net's current weights (one launch, in place).  ``inplace_state``: a state given in the stacked
+        layout (``inference_hidden``) is advanced in place and returned as views of itself -- the caller's state
+        buffers ARE the new state.  On a CPU net there is nothing to prepare."""
+        dev = next(self.net.parameters()).device
+        if dev.type == 'cuda':
+            with torch.no_grad():
+                self._refresh(dev)
+        self._live += 1
+        self._inplace = inplace_state
+        try:
+            yield self
+        finally:
+            self._live -= 1
+            self._inplace = False
+
+    def __call__(self, obs, hidden=None):
+        if self.net.training:
+            raise RuntimeError('GeisterInference is the eval forward: the net is in training mode')
+        board, scalar = obs['board'], obs['scalar']
+        if not board.is_cuda:
+            return self.net(obs, hidden)
+        if not self._live:
+            raise RuntimeError('GeisterInference on the GPU runs inside inference_session()')
+        N = board.shape[0]
+        if (board.dtype != torch.float32 or scalar.dtype != torch.float32 or tuple(board.shape) != (N, 7, 6, 6)
+                or tuple(scalar.shape) != (N, 18)):
+            raise ValueError('GeisterInference: observations are board (N, 7, 6, 6) and scalar (N, 18) fp32, not %s '
+                             '%s and %s %s' % (tuple(board.shape), board.dtype, tuple(scalar.shape), scalar.dtype))
+        from .envs.geister import _stacked
+        dev, L = board.device, self.layers
+        if hidden is None:
+            h, c = (torch.zeros(N, L * 32, 6, 6, device=dev) for _ in range(2))
+            inplace = False
+        else:
+            hs, cs = list(hidden[0]), list(hidden[1])
+            if len(hs) != L or len(cs) != L or any(tuple(t.shape) != (N, 32, 6, 6) or t.dtype != torch.float32
+                                                   for t in hs + cs):
+                raise ValueError('GeisterInference: the state is %d leaves (N, 32, 6, 6) fp32 per kind' % L)
+            h, c = _stacked(hs), _stacked(cs)
+            inplace = (self._inplace and h.is_contiguous() and c.is_contiguous()
+                       and h.data_ptr() == hs[0].data_ptr() and c.data_ptr() == cs[0].data_ptr())
+            h, c = h.contiguous(), c.contiguous()
+        h_out, c_out = (h, c) if inplace else (torch.empty_like(h), torch.empty_like(c))
+        policy = torch.empty(N, 214, device=dev)
+        value = torch.empty(N, 1, device=dev)
+        ret = torch.empty(N, 1, device=dev)
+        b = board if board.is_contiguous() else board.contiguous()
+        s = scalar if scalar.is_contiguous() else scalar.contiguous()
+        if N:
+            _native.check(_native.load().hrl_geister_infer(
+                _native.ptr(self.pack(dev)), L, self.net.num_repeats, self.p_filters, _native.ptr(b), _native.ptr(s),
+                _native.ptr(h), _native.ptr(c), N, _native.ptr(policy), _native.ptr(value), _native.ptr(ret),
+                _native.ptr(h_out), _native.ptr(c_out), _native.stream_of(dev)), 'hrl_geister_infer')
+        return {'policy': policy, 'value': value, 'return': ret,
+                'hidden': (list(h_out.split(32, 1)), list(c_out.split(32, 1)))}
+
+
 def configured_inference(mode, nets, device):
     """``train_args['inference']`` applied to the nets that play: absent / None leaves them as they are; ``fused``
     wraps each TicTacToe net in ``BoardInference`` (several: one ``board_inference_group``) and each GeeseNet in
     ``GeeseInference`` (each on its own); ``fused_bf16`` is GeeseNets only, each in
-    ``GeeseInference(net, precision='bf16')``.  Anything the fused forward cannot run, or a list mixing the two
-    kinds, raises here, at start-up, by the key's name."""
+    ``GeeseInference(net, precision='bf16')``; ``fused_geister`` is GeisterNets only, each in ``GeisterInference``
+    (a value of its own: ``fused`` keeps refusing the recurrent net, whose one-launch forward is slower today).
+    Anything the chosen forward cannot run, or a list mixing the kinds, raises here, at start-up, by the key's
+    name."""
     if mode is None:
         return nets
-    if mode not in ('fused', 'fused_bf16'):
-        raise ValueError("train_args['inference'] must be fused or fused_bf16 (or absent), not %r" % (mode,))
+    if mode not in ('fused', 'fused_bf16', 'fused_geister'):
+        raise ValueError("train_args['inference'] must be fused, fused_bf16 or fused_geister (or absent), not %r"
+                         % (mode,))
     if torch.device(device).type != 'cuda':
         raise ValueError("train_args['inference']: %r is the one-launch forward on the GPU; the device is %s"
                          % (mode, device))
@@ -2979,14 +3155,25 @@ def configured_inference(mode, nets, device):
                 raise ValueError("train_args['inference']: 'fused_bf16' forwards GeeseNet (32 filters, 1..16 blocks); "
                                  "%s is not one (geese_inference_ok)" % type(net).__name__)
         return [GeeseInference(net, precision='bf16') for net in nets]
+    if mode == 'fused_geister':
+        for net in nets:
+            if not geister_inference_ok(net):
+                raise ValueError("train_args['inference']: 'fused_geister' forwards GeisterNet (32 filters, 1..4 "
+                                 "layers, 1..8 repeats, p_filters 1, 2, 4 or 8); %s is not one (geister_inference_ok)"
+                                 % type(net).__name__)
+        return [GeisterInference(net) for net in nets]
     if nets and all(geese_inference_ok(net) for net in nets):
         return [GeeseInference(net) for net in nets]
     for net in nets:
         if geese_inference_ok(net):
             raise ValueError("train_args['inference']: 'fused' forwards nets of one kind; %s is a GeeseNet among "
                              "nets that are not" % type(net).__name__)
+        if geister_inference_ok(net):
+            raise ValueError("train_args['inference']: 'fused' forwards the TicTacToe net or GeeseNet; %s is a "
+                             "GeisterNet, whose one-launch forward is 'fused_geister'" % type(net).__name__)
         if not board_inference_ok(net):
             raise ValueError("train_args['inference']: 'fused' forwards the TicTacToe net (SimpleConv2dModel with 32 "
-                             "filters and 1..8 blocks) or GeeseNet (32 filters, 1..16 blocks); %s is not one "
-                             "(board_inference_ok, geese_inference_ok)" % type(net).__name__)
+                             "filters and 1..8 blocks) or GeeseNet (32 filters, 1..16 blocks), 'fused_geister' "
+                             "GeisterNet; %s is none of them (board_inference_ok, geese_inference_ok, "
+                             "geister_inference_ok)" % type(net).__name__)
     return board_inference_group(nets) if len(nets) > 1 else [BoardInference(nets[0])]

@@ -698,6 +698,41 @@ int hrl_geesenet_infer_bf16_pack(const float *const *conv_w, const float *const 
 int hrl_geesenet_infer_bf16(const void *pack, int64_t layers, const float *x, int64_t N, int64_t H, int64_t W,
                             float *policy, float *value, void *stream);
 
+/* GeisterNet's complete eval forward as ONE launch with the recurrent state on chip (envs/geister.py GeisterNet:
+ * stem 3x3 conv 25 -> 32 + BN + ReLU, DRC of `layers` ConvLSTM cells run num_repeats times, move / set policy, value
+ * and return heads; csrc/hrl_geister_infer.hip).  6x6 board, 32 filters; layers in 1..4, num_repeats in 1..8,
+ * p_filters in {1, 2, 4, 8} with 4 move planes, one-channel value / return heads, biased or bias-free cells.  Every
+ * entry is asynchronous, allocates nothing, never synchronises and is capturable; arguments are validated
+ * (HRL_EINVAL) before any HIP call.
+ * hrl_geister_infer_pack_bytes: the bytes of one packed net (a multiple of 16; 0 for a shape outside the above).
+ * hrl_geister_infer_pack: ONE launch that reads the net's tensors where they lie -- stem_w (32, 25, 3, 3); cell_w
+ *   (host array of `layers` device pointers, each (128, 64, 3, 3)) and cell_b (the same of (128), or NULL / all NULL
+ *   for bias-free cells); the four BatchNorms' weight, bias, running_mean, running_var (host arrays of 4 device
+ *   pointers: stem, move head, value, return) and bn_eps[4] (host doubles); move_w1 (p_filters, 64, 3, 3), move_w2
+ *   (4, p_filters); value_w / return_w (64) the 1x1 convs; value_fc / return_fc (36); set_w / set_b (70) -- and
+ *   writes the pack (16-byte aligned): the conv weights as the exact three-way bf16 split fragments the forward's
+ *   MFMAs read (the cells' output channels permuted so that a 16-column tile holds i, f, o, g of 4 hidden channels),
+ *   alpha = weight * (float)(1/sqrt((double)var + eps)), beta = bias - mean*alpha as hrl_bn_forward_eval forms
+ *   them, the cell biases (zeros when bias-free) and the remaining weights as they are.
+ * hrl_geister_infer: ONE launch, no workspace.  board (N, 7, 6, 6), scalar (N, 18), the stacked state h, c
+ *   (N, layers*32, 6, 6), all fp32 contiguous; policy (N, 214) = [144 move logits | 70 set logits], value (N, 1)
+ *   after tanh, ret (N, 1), and the advanced state in h_out, c_out, which may be h, c themselves (a workgroup
+ *   reads and writes only its own (16-row tile, layer) slice).  Arithmetic: six partial products of the exact bf16
+ *   split on v_mfma_f32_16x16x32_bf16 with fp32 accumulation (fp32-accurate), BatchNorm as y*alpha + beta, the
+ *   gates as hrl_lstm_gates_forward computes them, fp32 state.  A row's result does not depend on N or on its place
+ *   in the batch.  Deterministic.  N == 0: HRL_OK, no launch.  HRL_EINVAL for a NULL pointer, a shape outside the
+ *   above, N < 0 or N > 2^31 - 17, or a pack, board, h, c, h_out or c_out that is not 16-byte aligned. */
+int64_t hrl_geister_infer_pack_bytes(int64_t layers, int64_t p_filters);
+int hrl_geister_infer_pack(const float *stem_w, const float *const *cell_w, const float *const *cell_b,
+                           int64_t layers, const float *const *bn_w, const float *const *bn_b,
+                           const float *const *bn_mean, const float *const *bn_var, const double *bn_eps,
+                           const float *move_w1, const float *move_w2, int64_t p_filters, const float *value_w,
+                           const float *return_w, const float *value_fc, const float *return_fc, const float *set_w,
+                           const float *set_b, void *pack, void *stream);
+int hrl_geister_infer(const void *pack, int64_t layers, int64_t num_repeats, int64_t p_filters, const float *board,
+                      const float *scalar, const float *h, const float *c, int64_t N, float *policy, float *value,
+                      float *ret, float *h_out, float *c_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
