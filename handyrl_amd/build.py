@@ -32,7 +32,8 @@ HIPCC_FLAGS = ['--offload-arch=%s' % ARCH, '-O3', '-std=c++17', '-fPIC', '-ffp-c
 # its device code is compiled without the packed fp32 VALU forms (v_pk_*_f32), one scalar instruction per operation
 # (the host pass does not know the feature and ignores it)
 _NO_PACKED_FP32 = ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']
-EXTRA_FLAGS = {'hrl_geesenet_bf16.hip': _NO_PACKED_FP32, 'hrl_geister_infer.hip': _NO_PACKED_FP32}
+EXTRA_FLAGS = {'hrl_geesenet_bf16.hip': _NO_PACKED_FP32, 'hrl_geister_infer.hip': _NO_PACKED_FP32,
+               'hrl_torus_bf16.hip': _NO_PACKED_FP32}
 
 
 def hipcc():

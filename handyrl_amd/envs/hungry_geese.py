@@ -76,7 +76,7 @@ class GeeseNet(nn.Module):
         if self.training and self.conv0.use_hip and self.conv0.bn is not None and x.is_cuda:
             # accelerated training step: the unit chain is one HIP Function (nn.torus_tower)
             from ..nn import torus_tower
-            h = torus_tower(x, [self.conv0, *self.blocks])
+            h = torus_tower(x, [self.conv0, *self.blocks], getattr(self, 'tower_precision', 'fp32'))
         else:
             h = F.relu(self.conv0(x))
             for block in self.blocks:

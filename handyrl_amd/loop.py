@@ -38,7 +38,9 @@ class SelfPlayTrainer:
 
     def __init__(self, net, args, device, games_per_round=4096, capacity=65536, graph=False, seed=0,
                  env_cls=TicTacToeBatch, obs_dtype=torch.uint8, stream=False, fused_inference=False,
-                 fused_game=False):
+                 fused_game=False, precision=None):
+        if precision is not None:   # train_args' ``precision`` (nn.configured_precision), as a keyword
+            args = {**args, 'precision': precision}
         if fused_game and not fused_inference:
             raise ValueError('fused_game requires fused_inference=True (the one-launch game runs nn.BoardInference)')
         if fused_game and stream:

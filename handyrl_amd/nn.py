@@ -1345,16 +1345,140 @@ TOWER_BN_FOLD = True
 _CUT_FN = None
 
 
-def torus_tower(x, units):
+class _TorusTowerBf16(torch.autograd.Function):
+    """_TorusTower in mixed precision (csrc/hrl_torus_bf16.hip; the numeric contract is in include/hrl_nn.h): the
+    same launch sequence, one launch per role and unit, each in its bf16 form.  Conv operands and every stored
+    tower tensor (H, Y, DY, G) are bf16 channels-last (N, H*W, 32), private to this Function; BatchNorm statistics
+    and coefficients (the same hrl_bn_finalize_* launches), the master weights and the gradients it returns are
+    fp32.  x (fp32 NCHW, data: no gradient) in, the last block output fp32 NCHW out, its gradient fp32 NCHW in."""
+
+    @staticmethod
+    def forward(ctx, x, units, *params):
+        x = x.contiguous()
+        N, Cin, H, W = x.shape
+        HW = H * W
+        dev = x.device
+        lib = _native.load()
+        stream = _native.stream_of(dev)
+        P = _native.ptr
+        n = len(units)
+        weights = [params[4 * i].contiguous() for i in range(n)]
+        pack = torch.empty(lib.hrl_torus_bf16_pack_bytes(n), dtype=torch.uint8, device=dev)
+        _native.check(lib.hrl_torus_bf16_pack(_native.ptr_array(weights), n, Cin, P(pack), pack.numel(), stream),
+                      'hrl_torus_bf16_pack')
+        nparts = lib.hrl_torus_bf16_stats_blocks(N)
+        part = torch.empty(nparts * 64, dtype=torch.float64, device=dev)
+        coef = torch.empty(n, 4, 32, device=dev, dtype=x.dtype)   # per unit: save_mean, save_invstd, alpha, beta
+
+        def stored():
+            return torch.empty(N, HW, 32, device=dev, dtype=torch.bfloat16)
+        ys, hs = [], [None]   # hs[i]: unit i's input (unit 0's is x)
+        for i in range(n):
+            b, gamma, beta = params[4 * i + 1], params[4 * i + 2], params[4 * i + 3]
+            y = stored()
+            if i == 0:
+                _native.check(lib.hrl_torus_bf16_unit_forward(P(x), None, None, None, None, None, N, H, W, P(pack), 0,
+                                                              P(b), P(y), P(part), stream),
+                              'hrl_torus_bf16_unit_forward(stem)')
+            else:
+                h = stored()
+                _native.check(lib.hrl_torus_bf16_unit_forward(None, P(ys[-1]), P(hs[-1]) if i >= 2 else None,
+                                                              P(coef[i - 1, 2]), P(coef[i - 1, 3]), P(h), N, H, W,
+                                                              P(pack), i, P(b), P(y), P(part), stream),
+                              'hrl_torus_bf16_unit_forward')
+                hs.append(h)
+            rm, rv, momentum, eps = units[i]
+            _native.check(lib.hrl_bn_finalize_stats(P(part), nparts, 32, N * HW, P(gamma), P(beta), P(rm), P(rv),
+                                                    momentum, eps, P(coef[i, 0]), P(coef[i, 1]), P(coef[i, 2]),
+                                                    P(coef[i, 3]), stream), 'hrl_bn_finalize_stats')
+            ys.append(y)
+        out = torch.empty(N, 32, H, W, device=dev, dtype=x.dtype)
+        _native.check(lib.hrl_torus_bf16_output(P(ys[-1]), P(hs[-1]) if n >= 2 else None, P(coef[n - 1, 2]),
+                                                P(coef[n - 1, 3]), N, H, W, P(out), stream), 'hrl_torus_bf16_output')
+        gammas = [params[4 * i + 2] for i in range(n)]
+        ctx.save_for_backward(x, out, coef, pack, *gammas, *ys, *hs[1:])
+        ctx.n = n
+        ctx.wshapes = [tuple(w.shape) for w in weights]
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        n = ctx.n
+        saved = ctx.saved_tensors
+        x, out, coef, pack = saved[:4]
+        gammas, ys, hs = saved[4:4 + n], saved[4 + n:4 + 2 * n], (None,) + tuple(saved[4 + 2 * n:])
+        g = g.contiguous()
+        N, Cin, H, W = x.shape
+        HW = H * W
+        dev = x.device
+        lib = _native.load()
+        stream = _native.stream_of(dev)
+        P = _native.ptr
+        ws_bytes = lib.hrl_torus_bf16_workspace_bytes(N)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        nparts = lib.hrl_torus_bf16_stats_blocks(N)
+        part = torch.empty(nparts * 64, dtype=torch.float64, device=dev)
+        kg = torch.empty(2, 32, device=dev, dtype=g.dtype)   # k, mean(gm) of the unit being applied
+        grads = [None] * (4 * n)
+        for i in range(n):
+            grads[4 * i + 2] = torch.empty(32, device=dev, dtype=g.dtype)
+            grads[4 * i + 3] = torch.empty(32, device=dev, dtype=g.dtype)
+
+        def finalize(i):
+            _native.check(lib.hrl_bn_finalize_backward(P(part), nparts, 32, N * HW, P(gammas[i]), P(coef[i, 1]),
+                                                       P(grads[4 * i + 2]), P(grads[4 * i + 3]), P(kg[0]), P(kg[1]),
+                                                       stream), 'hrl_bn_finalize_backward')
+        # the last unit: the pool's fp32 NCHW gradient, masked, as fp32 channels-last, with its backward sums
+        g_cur, g_fp32 = torch.empty(N, HW, 32, device=dev, dtype=g.dtype), 1
+        _native.check(lib.hrl_torus_bf16_masked_sums(P(g), P(out), P(ys[-1]), P(coef[n - 1, 0]), N, H, W, P(g_cur),
+                                                     P(part), stream), 'hrl_torus_bf16_masked_sums')
+        finalize(n - 1)
+        dy = torch.empty(N, HW, 32, device=dev, dtype=torch.bfloat16)
+        for i in range(n - 1, -1, -1):
+            dw = torch.empty(ctx.wshapes[i], device=dev, dtype=g.dtype)
+            db = torch.empty(32, device=dev, dtype=g.dtype)
+            _native.check(lib.hrl_torus_bf16_wgrad_bn(P(x) if i == 0 else None, P(hs[i]), N, H, W, P(ys[i]), P(g_cur),
+                                                      g_fp32, P(coef[i, 2]), P(coef[i, 3]), 1 if i >= 1 else 0,
+                                                      P(gammas[i]), P(coef[i, 0]), P(coef[i, 1]), P(kg[0]), P(kg[1]),
+                                                      P(dy), P(dw), P(db), P(ws), ws_bytes, stream),
+                          'hrl_torus_bf16_wgrad_bn')
+            grads[4 * i], grads[4 * i + 1] = dw, db
+            if i == 0:
+                break
+            g_prev = torch.empty(N, HW, 32, device=dev, dtype=torch.bfloat16)
+            _native.check(lib.hrl_torus_bf16_unit_input_grad(P(dy), N, H, W, P(pack), i, P(g_cur), g_fp32,
+                                                             P(hs[i + 1]) if i + 1 < n else None, P(g_prev), P(hs[i]),
+                                                             P(ys[i - 1]), P(coef[i - 1, 0]), P(part), stream),
+                          'hrl_torus_bf16_unit_input_grad')
+            finalize(i - 1)
+            g_cur, g_fp32 = g_prev, 0
+        return (None, None, *grads)
+
+
+TOWER_PRECISIONS = ('fp32', 'bf16')
+
+
+def torus_tower(x, units, precision='fp32'):
     """The chain relu(bn(conv(x))) -> relu(h + bn(conv(h))) ... over training-mode TorusConv2d ``units``
     (GeeseNet's conv0 and blocks, hungry_geese.py:48-51) as one HIP Function (_TorusTower); each
     BatchNorm module's batch counter and running statistics advance as in its forward.
 
     ``units[0].tower_split = k`` (set by a data-parallel LearnerStep) runs it as two Functions, units [0, k) and
     [k, n) (the second with residual_in), so the backward can be cut between them and the upper part's gradient
-    all-reduce overlaps the lower part's backward; the value between them passes through _CUT_FN when set."""
+    all-reduce overlaps the lower part's backward; the value between them passes through _CUT_FN when set.
+
+    ``precision='bf16'`` (train_args' ``precision``) is the mixed-precision form, _TorusTowerBf16: bf16 conv
+    operands and stored activations / gradients, everything else fp32.  It has no split form."""
+    if precision not in TOWER_PRECISIONS:
+        raise ValueError("torus_tower: precision is 'fp32' or 'bf16', not %r" % (precision,))
     k = getattr(units[0], 'tower_split', None)
-    if k is not None and 0 < k < len(units):
+    split = k is not None and 0 < k < len(units)
+    if precision == 'bf16':
+        if split:
+            raise NotImplementedError("torus_tower: precision 'bf16' has no data-parallel split (tower_split = %r)"
+                                      % (k,))
+        return _tower_part(x, units, False, _TorusTowerBf16)
+    if split:
         h = _tower_part(x, units[:k], False)
         if _CUT_FN is not None:
             h = _CUT_FN(h)
@@ -1362,7 +1486,31 @@ def torus_tower(x, units):
     return _tower_part(x, units, False)
 
 
-def _tower_part(x, units, residual_in):
+def configured_precision(value, net, device):
+    """``train_args['precision']`` applied to the net the learner trains: ``fp32`` (or absent) leaves it as it is;
+    ``bf16`` makes a GeeseNet's training forward run its tower in mixed precision (``torus_tower(precision='bf16')``
+    through ``net.tower_precision``).  Anything else raises here, at start-up, by the key's name: another value, a
+    net that is not GeeseNet-shaped (32 filters, 1..16 blocks: ``geese_inference_ok``), a device that is not the
+    GPU, or a tower split for a data-parallel segmented backward."""
+    value = 'fp32' if value is None else value
+    if value not in TOWER_PRECISIONS:
+        raise ValueError("train_args['precision'] must be fp32 or bf16 (or absent), not %r" % (value,))
+    if value == 'bf16':
+        if not geese_inference_ok(net):
+            raise ValueError("train_args['precision']: 'bf16' trains GeeseNet's tower (32 filters, 1..16 blocks); "
+                             "%s is not one (geese_inference_ok)" % type(net).__name__)
+        if torch.device(device).type != 'cuda':
+            raise ValueError("train_args['precision']: 'bf16' is the mixed-precision tower on the GPU; the device "
+                             "is %s" % (device,))
+        if getattr(net.conv0, 'tower_split', None):
+            raise NotImplementedError("train_args['precision']: 'bf16' has no data-parallel split (tower_split); "
+                                      "train one GPU per process or keep precision fp32")
+    if value == 'bf16' or hasattr(net, 'tower_precision'):
+        net.tower_precision = value
+    return value
+
+
+def _tower_part(x, units, residual_in, function=None):
     meta, params = [], []
     for unit in units:
         bn = unit.bn
@@ -1374,6 +1522,8 @@ def _tower_part(x, units, residual_in):
         meta.append((bn.running_mean if bn.track_running_stats else None,
                      bn.running_var if bn.track_running_stats else None, momentum, bn.eps))
         params += [unit.conv.weight, unit.conv.bias, bn.weight, bn.bias]
+    if function is not None:
+        return function.apply(x, meta, *params)
     return _TorusTower.apply(x, meta, residual_in, *params)
 
 

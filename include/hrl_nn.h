@@ -389,6 +389,68 @@ int hrl_torus_conv_wgrad_bn(const float *x, int64_t N, int64_t Cin, int64_t H, i
 int hrl_torus_unit_forward(const float *y_prev, const float *res, const float *alpha, const float *beta, float *h,
                            int64_t N, int64_t H, int64_t W, const float *weight, const float *bias, float *y,
                            double *part, void *workspace, int64_t workspace_bytes, void *stream);
+/*
+ * The GeeseNet unit chain in mixed precision (csrc/hrl_torus_bf16.hip; opt-in, train_args precision: 'bf16'):
+ * bf16 conv operands and bf16 stored activations / gradients; accumulation, BatchNorm statistics and
+ * coefficients, master weights, pool, heads, loss and optimizer fp32.  Units u = 0..L, H*W <= 80, 17 -> 32 (stem)
+ * and 32 -> 32 channels.  bf(.) is fp32 -> bf16 round to nearest even; arithmetic is uncontracted and in the fp32
+ * tower's operation order wherever the same operation exists.
+ *
+ * Layout.  Every stored tower tensor (H, Y, DY, G; `void *` below) is channels-last bf16 [sample][cell][32 ch]:
+ * 64 B per cell, 64*H*W B per sample, 16-byte aligned, private to the caller's Function.  Only x in, the last
+ * block output and the gradient coming back are fp32 (N, C, H, W).
+ *
+ * Forward.   h_0 = bf(x) (x fp32 (N, 17, H, W), read once by the stem; channels 17..31 zero).
+ *            y_u = conv_torus(H_u, bf(W_u)) + b_u, fp32 accumulation; bf(W_u) comes from ONE hrl_torus_bf16_pack
+ *            launch per step over the fp32 master weights.  part[block][c] = (sum y, sum y^2) is taken from the
+ *            UNROUNDED fp32 y_u (fp32 per sample, fp64 across samples, fixed fold order: deterministic)
+ *            -> hrl_bn_finalize_stats, unchanged.  Y_u = bf(y_u) is stored.
+ *            H_{u+1} = bf(relu([float(H_u) +] float(Y_u) alpha + beta)) is formed and stored once by unit u+1's
+ *            staging; for the last unit hrl_torus_bf16_output writes the unrounded fp32 value (N, 32, H, W) for
+ *            the pool instead (its bf16 form has no reader).
+ * Backward.  gm = float(G_{u+1}) [H_{u+1} > 0]; for the last unit gm = g [bf(out) > 0] with g the pool's fp32
+ *            gradient (hrl_torus_bf16_masked_sums, which also writes gm as fp32 [sample][cell][32]).
+ *            part[block][c] = (sum gm, sum gm (float(Y_u) - mean)), fp32 per sample, fp64 across samples
+ *            -> hrl_bn_finalize_backward, unchanged.
+ *            dy = (((gm - gmean) - (float(Y_u) - mean) k) invstd) gamma; DY_u = bf(dy) stored once.
+ *            dW_u[tap] = sum DY_u (x) H_u(tap), db_u = sum DY_u: bf16 operands, fp32 accumulation, fixed folds
+ *            (deterministic); fp32 results (hrl_torus_bf16_wgrad_bn).
+ *            G_u = bf(conv_torus^T(DY_u, bf(W_u)) + gm): the residual branch is added in fp32 before the one
+ *            rounding (hrl_torus_bf16_unit_input_grad, which also sums unit u-1's two backward terms from the
+ *            stored G_u, H_u and Y_{u-1}).  The stem produces no input gradient.
+ *
+ * hrl_torus_bf16_pack: weights[u] (32, Cin_u, 3, 3) fp32 (Cin_0 = stem_cin, 17 or 32) -> pack, per unit the
+ *   forward and the adjoint operands in MFMA fragment order; hrl_torus_bf16_pack_bytes(units) bytes, units 1..17.
+ * hrl_torus_bf16_unit_forward: x != NULL is the stem (unit 0; y_prev, h_prev, alpha, beta, h NULL); otherwise unit
+ *   `unit` >= 1 whose input h is built from y_prev, h_prev (NULL for unit 1: no residual) and alpha / beta.
+ *   part: hrl_torus_bf16_stats_blocks(N) x 32 x 2 doubles (every part below has that many rows).
+ * hrl_torus_bf16_wgrad_bn: x (fp32, stem) or h (bf16), exactly one; g the gradient w.r.t. the block output, bf16
+ *   channels-last, or with g_fp32 != 0 the masked fp32 gm of hrl_torus_bf16_masked_sums; dweight (32, Cin, 3, 3),
+ *   dbias (32, may be NULL); workspace hrl_torus_bf16_workspace_bytes(N).
+ * hrl_torus_bf16_unit_input_grad: unit >= 1; h_next the block's output H_{u+1} (unused with g_fp32 != 0).
+ * Any NULL, misaligned or out-of-range argument is HRL_EINVAL before anything is launched.
+ */
+int64_t hrl_torus_bf16_pack_bytes(int64_t units);
+int64_t hrl_torus_bf16_workspace_bytes(int64_t N);
+int64_t hrl_torus_bf16_stats_blocks(int64_t N);
+int hrl_torus_bf16_pack(const float *const *weights, int64_t units, int64_t stem_cin, void *pack, int64_t pack_bytes,
+                        void *stream);
+int hrl_torus_bf16_unit_forward(const float *x, const void *y_prev, const void *h_prev, const float *alpha,
+                                const float *beta, void *h, int64_t N, int64_t H, int64_t W, const void *pack,
+                                int64_t unit, const float *bias, void *y, double *part, void *stream);
+int hrl_torus_bf16_output(const void *y, const void *h_prev, const float *alpha, const float *beta, int64_t N,
+                          int64_t H, int64_t W, float *out, void *stream);
+int hrl_torus_bf16_masked_sums(const float *g, const float *out, const void *y, const float *mean, int64_t N,
+                               int64_t H, int64_t W, float *gm, double *part, void *stream);
+int hrl_torus_bf16_wgrad_bn(const float *x, const void *h, int64_t N, int64_t H, int64_t W, const void *y,
+                            const void *g, int g_fp32, const float *alpha, const float *beta, int residual,
+                            const float *gamma, const float *save_mean, const float *save_invstd, const float *kcoef,
+                            const float *gmean, void *dy, float *dweight, float *dbias, void *workspace,
+                            int64_t workspace_bytes, void *stream);
+int hrl_torus_bf16_unit_input_grad(const void *dy, int64_t N, int64_t H, int64_t W, const void *pack, int64_t unit,
+                                   const void *g, int g_fp32, const void *h_next, void *dh, const void *h_mask,
+                                   const void *y_prev, const float *mean_prev, double *part, void *stream);
+
 /* A zero-padded 3x3 'same' nn.Conv2d, 32 input channels -> Cout (a multiple of 32) on a board of 4..80 cells,
  * on the torus kernel's MFMA path (GeisterNet's ConvLSTM h / x halves, geister.py:48-59): x (N, 32, H, W),
  * y (N, Cout, H, W); the weights are input channels [w_ci0, w_ci0 + 32) of a (Cout, w_cin_total, 3, 3)
