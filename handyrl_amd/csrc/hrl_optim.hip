@@ -397,14 +397,20 @@ int hrl_grad_fold_norm_ex(float *grads, int64_t n, const float *const *parts, co
     if (loss_part && (loss_nparts < 1 || loss_nparts > INT32_MAX || !losses ||
                       (reinterpret_cast<uintptr_t>(loss_part) & 7) != 0))
         return HRL_EINVAL;
+    if (nfolds > 0 && (!parts || !strides || !col0 || !nparts || !dst || !count || !modes)) return HRL_EINVAL;
+    if (ncounters > 0 && !counters) return HRL_EINVAL;
     const LossFold lf{loss_part, (int)loss_nparts, (float)ent_coef, losses};
     FoldTable ft{};
     for (int k = 0; k < nfolds; ++k) {
-        if (!parts[k] || nparts[k] < 1 || count[k] < 1 || dst[k] < 0 || dst[k] + count[k] > n || col0[k] < 0 ||
-            (modes[k] != 0 && modes[k] != 1) || (modes[k] == 1 && count[k] != 9216))
+        if (!parts[k] || nparts[k] < 1 || count[k] < 1 || dst[k] < 0 || dst[k] > n || count[k] > n - dst[k] ||
+            col0[k] < 0 || (modes[k] != 0 && modes[k] != 1) || (modes[k] == 1 && count[k] != 9216))
             return HRL_EINVAL;
         const int64_t span = modes[k] == 1 ? 9216 : count[k];
-        if (strides[k] < col0[k] + span) return HRL_EINVAL;
+        if (strides[k] < span || col0[k] > strides[k] - span) return HRL_EINVAL;
+        // a position belongs to one fold: the kernel's lookup keeps the last match, so of two folds on one
+        // destination the earlier one's gradient would be lost without an error
+        for (int j = 0; j < k; ++j)
+            if (dst[k] < dst[j] + count[j] && dst[j] < dst[k] + count[k]) return HRL_EINVAL;
         ft.part[k] = parts[k]; ft.stride[k] = strides[k]; ft.col0[k] = col0[k]; ft.nparts[k] = nparts[k];
         ft.dst[k] = dst[k]; ft.count[k] = count[k]; ft.mode[k] = modes[k];
     }

@@ -624,10 +624,18 @@ int hrl_stem_set_fwd_form(int form);
 /* The learner step's tail on the flat gradient buffer `grads` (n floats; parameter gradients are views of it):
  * hrl_grad_fold_norm: for each of nfolds (<= 16) deferred weight-gradient folds, grads[dst + j] (j < count) =
  *   the fixed-order fp64 sum over nparts partial rows of parts[row * stride + col0 + col(j)] (mode 0: col(j) = j;
- *   mode 1: a 32x32x3x3 conv weight from the chain blocks' [tap][ci][co] rows, count 9216); then the fp64 sum of
- *   squares of every 64-element block of grads into norm_part (hrl_grad_fold_norm_blocks(n) doubles); and,
- *   once, *step += 1 (may be NULL) and *counters[k] += increments[k] (BatchNorm num_batches_tracked,
- *   ncounters <= 8; increments NULL: all 1, e.g. T for a recurrent unroll's per-step BatchNorm).
+ *   mode 1: a 32x32x3x3 conv weight from the chain blocks' [tap][ci][co] rows, count 9216), added to what
+ *   grads[dst + j] holds; then the fp64 sum of squares of every 64-element block of grads into norm_part
+ *   (hrl_grad_fold_norm_blocks(n) doubles; every element is counted once, so the sums total the squared norm, but
+ *   inside a mode-1 fold block position dst + j counts the element its source column j lands on, not element
+ *   dst + j); and, once, *step += 1 (may be NULL) and *counters[k] += increments[k] (BatchNorm
+ *   num_batches_tracked, ncounters <= 8; increments NULL: all 1, e.g. T for a recurrent unroll's per-step
+ *   BatchNorm).  HRL_EINVAL before any launch: n < 1; with nfolds > 0 a NULL parts, strides, col0, nparts, dst,
+ *   count or modes table, a NULL parts[k], nparts[k] < 1, count[k] < 1, dst[k] < 0, dst[k] + count[k] > n,
+ *   col0[k] < 0, strides[k] < col0[k] + span (span = count[k], 9216 in mode 1), a mode other than 0 / 1, mode 1
+ *   with count != 9216, or two folds whose [dst, dst + count) ranges intersect (a position belongs to one fold:
+ *   a parameter's second use folds with its own launch); with ncounters > 0 a NULL counters table or entry or
+ *   a negative increment; norm_part NULL or shorter than the block count.
  * hrl_adam_clip: clip_grad_norm_(max_norm) from those block sums (every workgroup folds them in one fixed order;
  *   *total_norm = the norm; grads scaled in place) and torch.optim.Adam's step (fused_adam_utils.cuh adam_math,
  *   L2 weight decay, the same double / float promotions) on the tensors params[t] (elements offsets[t] ..
