@@ -33,7 +33,8 @@ class SelfPlayTrainer:
     more games are in the ring) instead of the lockstep ``DeviceGenerator``.  ``fused_inference``: self-play runs
     ``nn.BoardInference(net)`` (``play_net``, also the net to hand to ``evaluate_vs_random``); the learner trains
     ``net`` itself; ``fused_inference='fused_bf16'`` (a GeeseNet on a CUDA device) runs
-    ``nn.GeeseInference(net, precision='bf16')`` instead.  ``fused_game`` (with ``fused_inference``, without ``stream``): the lockstep generator plays a whole
+    ``nn.GeeseInference(net, precision='bf16')`` instead, ``'fused_geister_bf16'`` (a GeisterNet)
+    ``nn.GeisterInference(net, precision='bf16')``.  ``fused_game`` (with ``fused_inference``, without ``stream``): the lockstep generator plays a whole
     round in one launch (``DeviceGenerator(fused_game=True)``), the same episodes bit for bit."""
 
     def __init__(self, net, args, device, games_per_round=4096, capacity=65536, graph=False, seed=0,
@@ -52,8 +53,8 @@ class SelfPlayTrainer:
                                    maximum_episodes=args.get('maximum_episodes', capacity), obs_dtype=obs_dtype)
         self.stream = bool(stream)
         # the net as self-play runs it: itself, or its one-launch eval forward (the learner trains `net` itself)
-        if fused_inference == 'fused_bf16':   # GeeseNet's bf16 one-launch forward (nn.configured_inference's rules)
-            self.play_net = configured_inference('fused_bf16', [net], device)[0]
+        if fused_inference in ('fused_bf16', 'fused_geister_bf16'):   # the bf16 one-launch forwards of GeeseNet /
+            self.play_net = configured_inference(fused_inference, [net], device)[0]   # GeisterNet (that function's rules)
         else:
             self.play_net = BoardInference(net) if fused_inference else net
         if self.stream:

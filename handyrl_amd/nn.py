@@ -3174,14 +3174,23 @@ class GeisterInference(GeeseInference):
     views of itself (as ``DRC._inference_stacked`` does); any other state (separate leaves, ``None``) is stacked,
     the new state written to fresh tensors and returned as channel slices.  A CPU batch runs ``net``'s own forward;
     training mode, or the GPU outside a session, raises.
+
+    ``precision='bf16'`` is the actor's form (hrl_geister_infer_bf16, csrc/hrl_geister_infer_bf16.hip): the 3x3 conv
+    weights and the activations the convs and heads read are bf16, accumulation, gates and the state ``h``, ``c``
+    fp32 (include/hrl_nn.h has the contract).  Its own pack; sessions, the state's handling and the CPU path are the
+    same.
     """
 
     stateless_session = False   # the session decides whether the state is advanced in place
 
-    def __init__(self, net):
+    def __init__(self, net, precision='fp32'):
         parts = _geister_infer_parts(net)
         if parts is None:
             raise ValueError('GeisterInference: not a GeisterNet-shaped net (geister_inference_ok)')
+        if precision not in ('fp32', 'bf16'):
+            raise ValueError("GeisterInference: precision is 'fp32' or 'bf16', not %r" % (precision,))
+        self.precision = precision
+        self._entry = 'hrl_geister_infer' if precision == 'fp32' else 'hrl_geister_infer_bf16'
         self.net = net
         self.layers, self.p_filters = len(parts[0]), parts[1]
         self._buf = None
@@ -3197,12 +3206,12 @@ class GeisterInference(GeeseInference):
     def pack(self, device=None):
         """The pack buffer (pack_bytes uint8) on ``device``: allocated once, the same storage ever after."""
         if self._buf is None or (device is not None and self._buf.device != torch.device(device)):
-            nbytes = _native.load().hrl_geister_infer_pack_bytes(self.layers, self.p_filters)
+            nbytes = getattr(_native.load(), self._entry + '_pack_bytes')(self.layers, self.p_filters)
             self._buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
         return self._buf
 
     def _refresh(self, dev):
-        """hrl_geister_infer_pack from the net's tensors into the pack."""
+        """hrl_geister_infer_pack (or the bf16 form's) from the net's tensors into the pack."""
         net = self.net
         cells, pf = _geister_infer_parts(net)
         bns = [net.bn1, net.head_p_move.bn, net.head_v.bn, net.head_r.bn]
@@ -3218,11 +3227,11 @@ class GeisterInference(GeeseInference):
                 raise ValueError('GeisterInference: the net\'s tensors must be contiguous fp32 on one device')
         stem, w1, w2, wv, wr, fcv, fcr, sw, sb = single
         eps = (ctypes.c_double * 4)(*[float(b.eps) for b in bns])
-        _native.check(_native.load().hrl_geister_infer_pack(
+        _native.check(getattr(_native.load(), self._entry + '_pack')(
             _native.ptr(stem), _native.ptr_array(cell_w), _native.ptr_array(cell_b), self.layers,
             *[_native.ptr_array(ts) for ts in per], eps, _native.ptr(w1), _native.ptr(w2), pf, _native.ptr(wv),
             _native.ptr(wr), _native.ptr(fcv), _native.ptr(fcr), _native.ptr(sw), _native.ptr(sb),
-            _native.ptr(self.pack(dev)), _native.stream_of(dev)), 'hrl_geister_infer_pack')
+            _native.ptr(self.pack(dev)), _native.stream_of(dev)), self._entry + '_pack')
 
     @contextlib.contextmanager
     def inference_session(self, inplace_state=False):
@@ -3275,10 +3284,10 @@ class GeisterInference(GeeseInference):
         b = board if board.is_contiguous() else board.contiguous()
         s = scalar if scalar.is_contiguous() else scalar.contiguous()
         if N:
-            _native.check(_native.load().hrl_geister_infer(
+            _native.check(getattr(_native.load(), self._entry)(
                 _native.ptr(self.pack(dev)), L, self.net.num_repeats, self.p_filters, _native.ptr(b), _native.ptr(s),
                 _native.ptr(h), _native.ptr(c), N, _native.ptr(policy), _native.ptr(value), _native.ptr(ret),
-                _native.ptr(h_out), _native.ptr(c_out), _native.stream_of(dev)), 'hrl_geister_infer')
+                _native.ptr(h_out), _native.ptr(c_out), _native.stream_of(dev)), self._entry)
         return {'policy': policy, 'value': value, 'return': ret,
                 'hidden': (list(h_out.split(32, 1)), list(c_out.split(32, 1)))}
 
@@ -3288,14 +3297,15 @@ def configured_inference(mode, nets, device):
     wraps each TicTacToe net in ``BoardInference`` (several: one ``board_inference_group``) and each GeeseNet in
     ``GeeseInference`` (each on its own); ``fused_bf16`` is GeeseNets only, each in
     ``GeeseInference(net, precision='bf16')``; ``fused_geister`` is GeisterNets only, each in ``GeisterInference``
-    (a value of its own: ``fused`` keeps refusing the recurrent net, whose one-launch forward is slower today).
+    (a value of its own: ``fused`` keeps refusing the recurrent net, whose exact one-launch forward is slower than
+    the module path); ``fused_geister_bf16`` is GeisterNets only, each in ``GeisterInference(net, precision='bf16')``.
     Anything the chosen forward cannot run, or a list mixing the kinds, raises here, at start-up, by the key's
     name."""
     if mode is None:
         return nets
-    if mode not in ('fused', 'fused_bf16', 'fused_geister'):
-        raise ValueError("train_args['inference'] must be fused, fused_bf16 or fused_geister (or absent), not %r"
-                         % (mode,))
+    if mode not in ('fused', 'fused_bf16', 'fused_geister', 'fused_geister_bf16'):
+        raise ValueError("train_args['inference'] must be fused, fused_bf16, fused_geister or fused_geister_bf16 "
+                         "(or absent), not %r" % (mode,))
     if torch.device(device).type != 'cuda':
         raise ValueError("train_args['inference']: %r is the one-launch forward on the GPU; the device is %s"
                          % (mode, device))
@@ -3305,13 +3315,13 @@ def configured_inference(mode, nets, device):
                 raise ValueError("train_args['inference']: 'fused_bf16' forwards GeeseNet (32 filters, 1..16 blocks); "
                                  "%s is not one (geese_inference_ok)" % type(net).__name__)
         return [GeeseInference(net, precision='bf16') for net in nets]
-    if mode == 'fused_geister':
+    if mode in ('fused_geister', 'fused_geister_bf16'):
         for net in nets:
             if not geister_inference_ok(net):
-                raise ValueError("train_args['inference']: 'fused_geister' forwards GeisterNet (32 filters, 1..4 "
+                raise ValueError("train_args['inference']: %r forwards GeisterNet (32 filters, 1..4 "
                                  "layers, 1..8 repeats, p_filters 1, 2, 4 or 8); %s is not one (geister_inference_ok)"
-                                 % type(net).__name__)
-        return [GeisterInference(net) for net in nets]
+                                 % (mode, type(net).__name__))
+        return [GeisterInference(net, precision='fp32' if mode == 'fused_geister' else 'bf16') for net in nets]
     if nets and all(geese_inference_ok(net) for net in nets):
         return [GeeseInference(net) for net in nets]
     for net in nets:

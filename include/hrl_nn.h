@@ -803,6 +803,43 @@ int hrl_geister_infer(const void *pack, int64_t layers, int64_t num_repeats, int
                       const float *scalar, const float *h, const float *c, int64_t N, float *policy, float *value,
                       float *ret, float *h_out, float *c_out, void *stream);
 
+/* GeisterNet's eval forward with bf16 conv operands and an fp32 recurrent state, ONE launch per forward
+ * (csrc/hrl_geister_infer_bf16.hip): the actor's form of the entries above.  Same nets, same arguments, same calling
+ * rules (asynchronous, no allocation, no workspace, capturable, arguments validated before any HIP call).
+ * Numerics:
+ *   - the 3x3 conv weights (stem, the cells' x and h halves, the move head's first conv) are rounded fp32 -> bf16
+ *     once, at pack time, round to nearest even;
+ *   - an activation is rounded to bf16 (nearest even) at the moment it is stored as a conv or head operand: the 25
+ *     stem input planes, h_e after BatchNorm + ReLU, each layer's h_l as loaded and each layer's h_l after every
+ *     repeat.  Every reader of h_e and h_l inside the launch -- the cells, the move head, the value and return 1x1
+ *     convs -- reads that rounded copy;
+ *   - everything else is fp32, in hrl_geister_infer's operation order: the MFMA's accumulation (x half, then h half,
+ *     input cells in order), the cell biases, the gates with hrl_lstm_gates_forward's sigm / tanhf, c, BatchNorm as
+ *     y*alpha + beta with alpha = weight * (float)(1/sqrt((double)var + eps)), beta = bias - mean*alpha as
+ *     hrl_bn_forward_eval forms them, the 1x1, fc and head_p_set weights, tanh of the value;
+ *   - c is never rounded, and the h_out written to memory is the unrounded fp32 o * tanh(c') of the last repeat: from
+ *     ply to ply the state is fp32, bf16 exists only inside a launch.
+ *   A row's result does not depend on N or on its place in the batch.  Deterministic.
+ * hrl_geister_infer_bf16_pack_bytes: the bytes of one packed net (a multiple of 16; 0 for a shape hrl_geister_infer
+ *   does not take): 4 + 16*layers fragment sets of 9,216 B, then 496 + 128*layers floats.
+ * hrl_geister_infer_bf16_pack: hrl_geister_infer_pack's arguments and HRL_EINVAL rules; ONE launch that writes what
+ *   the forward reads in the order it reads it: the bf16 MFMA column operands [set][tap 9][lane 64][8 bf16] of the
+ *   stem (2 sets), each layer's x half and h half (8 column tiles each, output channels permuted so that a tile holds
+ *   i, f, o, g of 4 hidden channels) and the move head (2), then the BatchNorm coefficients, the fp32 head weights
+ *   and the cell biases (zeros when bias-free).
+ * hrl_geister_infer_bf16: hrl_geister_infer's arguments and HRL_EINVAL rules; h_out, c_out may be h, c.  N == 0:
+ *   HRL_OK, no launch. */
+int64_t hrl_geister_infer_bf16_pack_bytes(int64_t layers, int64_t p_filters);
+int hrl_geister_infer_bf16_pack(const float *stem_w, const float *const *cell_w, const float *const *cell_b,
+                                int64_t layers, const float *const *bn_w, const float *const *bn_b,
+                                const float *const *bn_mean, const float *const *bn_var, const double *bn_eps,
+                                const float *move_w1, const float *move_w2, int64_t p_filters, const float *value_w,
+                                const float *return_w, const float *value_fc, const float *return_fc,
+                                const float *set_w, const float *set_b, void *pack, void *stream);
+int hrl_geister_infer_bf16(const void *pack, int64_t layers, int64_t num_repeats, int64_t p_filters,
+                           const float *board, const float *scalar, const float *h, const float *c, int64_t N,
+                           float *policy, float *value, float *ret, float *h_out, float *c_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
