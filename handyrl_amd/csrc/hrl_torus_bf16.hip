@@ -26,6 +26,9 @@
 // torus_bf16_pack_kernel: bf(W) of every unit in forward and adjoint operand order, one launch per step.
 // bn_bf16_output_kernel / bn_bf16_masked_sums_kernel: the two layout crossings, the last unit's output as fp32
 //   NCHW for the pool and the pool's fp32 NCHW gradient as masked fp32 channels-last with its backward sums.
+// torus_bf16_heads_fwd_kernel / _bwd_kernel (precision 'bf16_heads'): the tail without either crossing, the last
+//   unit's output rebuilt from Y, H and the coefficients in registers, pooled and put through both heads; the
+//   backward writes the masked fp32 gradient, its sums and the head weight gradients (described at the kernels).
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -765,6 +768,233 @@ __global__ __launch_bounds__(256) void bn_bf16_masked_sums_kernel(const float *_
     }
 }
 
+// ------------------------------------------------------------------ the fused tail: last unit's output, pool, heads
+// A wave owns a sample, 8 waves a workgroup.  Lane l reads chunks j = 64 k + l of Y (and H): always channel group
+// g = l & 3 (channels 8 g .. 8 g + 7), cells 16 k + (l >> 2).  out = relu([float(H) +] float(Y) alpha + beta) is
+// rebuilt chunk-wise in bn_bf16_output_kernel's operation order and never stored; a channel's sum over the cells
+// is the lane's fp32 partial (at most 5 cells) folded over the 16 lanes l ^ (4, 8, 16, 32), after which every lane
+// of a group holds its 8 channels of h_head and h_avg.  The head products are 8-channel partials per lane folded
+// over l ^ (1, 2).  Head weights, alpha, beta (and mean) sit in LDS; nothing else does.
+constexpr int kActions = 4;
+constexpr int kHeadW = (kActions + 2) * kCo;   // head_p (4, 32) | head_v (1, 64); also a workgroup's dW partial
+
+template <int M>
+__device__ __forceinline__ float swz_xor(float v) {   // lane l gets lane l ^ M's value (M < 32)
+    return __uint_as_float(__builtin_amdgcn_ds_swizzle(__float_as_uint(v), (M << 10) | 0x1f));
+}
+__device__ __forceinline__ float fold_cells(float v) {
+    v += swz_xor<4>(v);
+    v += swz_xor<8>(v);
+    v += swz_xor<16>(v);
+    return v + __shfl_xor(v, 32, 64);
+}
+__device__ __forceinline__ void coef8(const float *p, float (&f)[8]) {
+    const float4 a = reinterpret_cast<const float4 *>(p)[0], b = reinterpret_cast<const float4 *>(p)[1];
+    f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
+}
+
+struct TailArgs {
+    int64_t N, x_stride;
+    int HW;
+    const uint4 *y, *hprev;                    // the last unit's Y and its input H (residual; NULL: one unit)
+    const float *alpha, *beta, *x, *head_p, *head_v;
+    float *policy, *value, *pooled;            // forward: outputs; backward: value and pooled are read
+    const float *dpolicy, *dvalue, *mean;      // backward
+    float4 *gm;
+    double *part, *wpart;                      // [gridDim.x][32][2], [gridDim.x][kHeadW]
+};
+
+// one sample's staged operands: Y, H and x[:, 0] at the lane's cells (clamped loads issue back to back)
+template <bool RES>
+struct TailSample {
+    uint4 y[kNCh], h[RES ? kNCh : 1];
+    float x0[kNCh];
+    __device__ __forceinline__ void load(const TailArgs &a, int64_t n, int lane, int nch) {
+#pragma unroll
+        for (int k = 0; k < kNCh; ++k) {
+            const int j = min(k * 64 + lane, nch - 1);
+            y[k] = a.y[n * nch + j];
+            if constexpr (RES) h[k] = a.hprev[n * nch + j];
+            x0[k] = a.x[n * a.x_stride + (j >> 2)];
+        }
+    }
+    // relu([float(H) +] float(Y) alpha + beta) of chunk k, and float(Y)
+    __device__ __forceinline__ void out(int k, const float *coef_s, int g, float (&o)[8], float (&yv)[8]) const {
+        float hv[8], al[8], be[8];
+        unpack8(y[k], yv);
+        if constexpr (RES) unpack8(h[k], hv);
+        coef8(coef_s + 8 * g, al);
+        coef8(coef_s + kCo + 8 * g, be);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            float t = yv[e] * al[e] + be[e];
+            if constexpr (RES) t = hv[e] + t;
+            o[e] = relu(t);
+        }
+    }
+};
+
+__device__ __forceinline__ void tail_constants(const TailArgs &a, float *coef_s, float *head_s, bool with_mean) {
+    if (threadIdx.x < 2 * kCo) coef_s[threadIdx.x] = threadIdx.x < kCo ? a.alpha[threadIdx.x] : a.beta[threadIdx.x - kCo];
+    else if (with_mean && threadIdx.x < 3 * kCo) coef_s[threadIdx.x] = a.mean[threadIdx.x - 2 * kCo];
+    for (int i = threadIdx.x; i < kHeadW; i += kThreads)
+        head_s[i] = i < kActions * kCo ? a.head_p[i] : a.head_v[i - kActions * kCo];
+    __syncthreads();
+}
+
+template <bool RES>
+__global__ __launch_bounds__(kThreads) void torus_bf16_heads_fwd_kernel(TailArgs a) {
+    __shared__ __attribute__((aligned(16))) float coef_s[2 * kCo];
+    __shared__ __attribute__((aligned(16))) float head_s[kHeadW];
+    const int HW = a.HW, nch = 4 * HW;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane & 3;
+    const float fhw = (float)HW;
+    tail_constants(a, coef_s, head_s, false);
+    TailSample<RES> s;
+    for (int64_t n = (int64_t)blockIdx.x * kNW + wave; n < a.N; n += (int64_t)gridDim.x * kNW) {
+        s.load(a, n, lane, nch);
+        float hh[8], ha[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) hh[e] = ha[e] = 0.f;
+#pragma unroll
+        for (int k = 0; k < kNCh; ++k) {
+            if (opaque(k * 64 + lane) < nch) {
+                float o[8], yv[8];
+                s.out(k, coef_s, opaque(g), o, yv);   // the coefficients are read per chunk, not held
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    hh[e] += o[e] * s.x0[k];
+                    ha[e] += o[e];
+                }
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            hh[e] = fold_cells(hh[e]);
+            ha[e] = fold_cells(ha[e]) / fhw;   // sum, then divide: hrl_torus_head_pool's mean
+        }
+        if (lane < 4) {
+            float4 *ph = reinterpret_cast<float4 *>(a.pooled + n * (2 * kCo) + 8 * g);
+            ph[0] = make_float4(hh[0], hh[1], hh[2], hh[3]);
+            ph[1] = make_float4(hh[4], hh[5], hh[6], hh[7]);
+            ph[kCo / 4] = make_float4(ha[0], ha[1], ha[2], ha[3]);
+            ph[kCo / 4 + 1] = make_float4(ha[4], ha[5], ha[6], ha[7]);
+        }
+        // the head products in fp64 (exact products, 32 / 64 terms), rounded once
+        double r[kActions + 1];
+#pragma unroll
+        for (int k = 0; k <= kActions; ++k) r[k] = 0.0;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int c = 8 * g + e;
+#pragma unroll
+            for (int k = 0; k <= kActions; ++k) r[k] += (double)head_s[k * kCo + c] * (double)hh[e];
+            r[kActions] += (double)head_s[(kActions + 1) * kCo + c] * (double)ha[e];
+        }
+#pragma unroll
+        for (int k = 0; k <= kActions; ++k) {
+            r[k] += __shfl_xor(r[k], 1, 64);
+            r[k] += __shfl_xor(r[k], 2, 64);
+        }
+        if (lane < kActions)
+            a.policy[n * kActions + lane] = (float)(lane == 0 ? r[0] : lane == 1 ? r[1] : lane == 2 ? r[2] : r[3]);
+        if (lane == kActions) a.value[n] = tanhf((float)r[kActions]);
+    }
+}
+
+template <bool RES>
+__global__ __launch_bounds__(kThreads) void torus_bf16_heads_bwd_kernel(TailArgs a) {
+    __shared__ __attribute__((aligned(16))) float coef_s[3 * kCo];   // alpha | beta | mean
+    __shared__ __attribute__((aligned(16))) float head_s[kHeadW];
+    __shared__ double red[kNW * kCo * 2];
+    __shared__ double wred[kNW * kHeadW];
+    const int HW = a.HW, nch = 4 * HW;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane & 3;
+    const float fhw = (float)HW;
+    tail_constants(a, coef_s, head_s, true);
+    // the lane's backward sum across samples: channel 8 g + (i & 7), term i >> 3, i = lane >> 2
+    double sum = 0.0, wp0 = 0.0, wp1 = 0.0, wv = 0.0;
+    TailSample<RES> s;
+    for (int64_t n = (int64_t)blockIdx.x * kNW + wave; n < a.N; n += (int64_t)gridDim.x * kNW) {
+        s.load(a, n, lane, nch);
+        float dp[kActions];
+#pragma unroll
+        for (int k = 0; k < kActions; ++k) dp[k] = a.dpolicy ? a.dpolicy[n * kActions + k] : 0.f;
+        const float val = a.value[n];
+        const float dv = (a.dvalue ? a.dvalue[n] : 0.f) * (1.f - val * val);
+        // dW_p[k][c] (lanes 0-31: k = 0, 1; lanes 32-63: k = 2, 3; c = lane & 31) and dW_v[lane]
+        const float ph = a.pooled[n * (2 * kCo) + (lane & 31)], pl = a.pooled[n * (2 * kCo) + lane];
+        wp0 += (double)(lane < 32 ? dp[0] : dp[2]) * (double)ph;
+        wp1 += (double)(lane < 32 ? dp[1] : dp[3]) * (double)ph;
+        wv += (double)dv * (double)pl;
+        // the pool's adjoint for the lane's channels: g[q][c] = dhead[c] x0[q] + davg[c] / HW
+        float dh[8], da[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int c = 8 * g + e;
+            double t = (double)dv * (double)head_s[kActions * kCo + c];   // five exact products, one rounding
+#pragma unroll
+            for (int k = 0; k < kActions; ++k) t += (double)head_s[k * kCo + c] * (double)dp[k];
+            dh[e] = (float)t;
+            da[e] = (dv * head_s[(kActions + 1) * kCo + c]) / fhw;   // hrl_torus_head_unpool's davg / HW
+        }
+        float t1[8], t2[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) t1[i] = t2[i] = 0.f;
+#pragma unroll
+        for (int k = 0; k < kNCh; ++k) {
+            const int j = opaque(k * 64 + lane);
+            if (j < nch) {
+                float o[8], yv[8], v[8], mu[8];
+                s.out(k, coef_s, j & 3, o, yv);   // j & 3 = g: the coefficients are read per chunk, not held
+                coef8(coef_s + 2 * kCo + 8 * (j & 3), mu);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    v[e] = bf_round(o[e]) > 0.f ? dh[e] * s.x0[k] + da[e] : 0.f;   // masked_sums' mask
+                    t1[e] += v[e];
+                    t2[e] += v[e] * (yv[e] - mu[e]);
+                }
+                a.gm[(n * nch + j) * 2] = make_float4(v[0], v[1], v[2], v[3]);
+                a.gm[(n * nch + j) * 2 + 1] = make_float4(v[4], v[5], v[6], v[7]);
+            }
+        }
+        // the lane's fp32 sums over its cells go to fp64 as masked_sums' do, then fold over the 16 lanes of the
+        // channel group; each lane keeps one of the 16 sums
+        double pick = 0.0;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const double f1 = fold16<4>((double)t1[e]), f2 = fold16<4>((double)t2[e]);
+            pick = (lane >> 2) == e ? f1 : ((lane >> 2) == 8 + e ? f2 : pick);
+        }
+        sum += pick;
+    }
+    red[(wave * kCo + 8 * g + ((lane >> 2) & 7)) * 2 + (lane >> 5)] = sum;
+    wred[wave * kHeadW + 2 * (lane >> 5) * kCo + (lane & 31)] = wp0;
+    wred[wave * kHeadW + (2 * (lane >> 5) + 1) * kCo + (lane & 31)] = wp1;
+    wred[wave * kHeadW + kActions * kCo + lane] = wv;
+    __syncthreads();
+    if (threadIdx.x < 2 * kCo) {
+        double t = 0.0;
+        for (int w = 0; w < kNW; ++w) t += red[w * kCo * 2 + threadIdx.x];
+        a.part[(int64_t)blockIdx.x * kCo * 2 + threadIdx.x] = t;
+    }
+    if (threadIdx.x < kHeadW) {
+        double t = 0.0;
+        for (int w = 0; w < kNW; ++w) t += wred[w * kHeadW + threadIdx.x];
+        a.wpart[(int64_t)blockIdx.x * kHeadW + threadIdx.x] = t;
+    }
+}
+
+// fold the workgroups' head-weight partials in a fixed order: dW_p (4, 32) then dW_v (1, 64)
+__global__ __launch_bounds__(kHeadW) void torus_bf16_heads_fold_kernel(const double *__restrict__ wpart, int nparts,
+                                                                       float *__restrict__ dwp, float *__restrict__ dwv) {
+    const int i = threadIdx.x;
+    double t = 0.0;
+    for (int w = 0; w < nparts; ++w) t += wpart[(int64_t)w * kHeadW + i];
+    if (i < kActions * kCo) dwp[i] = (float)t;
+    else dwv[i - kActions * kCo] = (float)t;
+}
+
 int status() {
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? HRL_OK : HRL_ELAUNCH_BASE - (int)e;
@@ -772,6 +1002,10 @@ int status() {
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 bool shape_ok(int64_t N, int64_t H, int64_t W) {
     return N >= 1 && N < ((int64_t)1 << 31) && H >= 1 && W >= 1 && H * W <= kMaxCells;
+}
+// the fused tail's entries take N = 0 (no launch)
+bool tail_shape_ok(int64_t N, int64_t H, int64_t W) {
+    return N >= 0 && N < ((int64_t)1 << 31) && H >= 1 && W >= 1 && H * W <= kMaxCells;
 }
 // every conv-role launch (and the sums kernel) writes this many partial rows: one grid for all of them
 int conv_grid(int64_t N) {
@@ -907,6 +1141,57 @@ int hrl_torus_bf16_unit_input_grad(const void *dy, int64_t N, int64_t H, int64_t
     const dim3 grid(conv_grid(N)), block(kThreads);
     if (g_fp32) hipLaunchKernelGGL((torus_bf16_conv_kernel<ADJ, true>), grid, block, 0, s, a);
     else hipLaunchKernelGGL((torus_bf16_conv_kernel<ADJ, false>), grid, block, 0, s, a);
+    return status();
+}
+
+int64_t hrl_torus_bf16_heads_workspace_bytes(int64_t N) {
+    return N < 0 ? -1 : (N == 0 ? 0 : (int64_t)conv_grid(N) * kHeadW * 8);
+}
+
+int hrl_torus_bf16_heads_forward(const void *y, const void *h_prev, const float *alpha, const float *beta,
+                                 const float *x, int64_t x_stride, const float *head_p, const float *head_v, int64_t N,
+                                 int64_t H, int64_t W, float *policy, float *value, float *pooled, void *stream) {
+    if (!tail_shape_ok(N, H, W) || !y || !alpha || !beta || !x || x_stride < H * W || !head_p || !head_v || !policy ||
+        !value || !pooled || !aligned16(y) || !aligned16(h_prev) || !aligned16(pooled))
+        return HRL_EINVAL;
+    if (N == 0) return HRL_OK;
+    TailArgs a{};
+    a.N = N; a.x_stride = x_stride; a.HW = (int)(H * W); a.y = static_cast<const uint4 *>(y);
+    a.hprev = static_cast<const uint4 *>(h_prev); a.alpha = alpha; a.beta = beta; a.x = x; a.head_p = head_p;
+    a.head_v = head_v; a.policy = policy; a.value = value; a.pooled = pooled;
+    const dim3 grid(conv_grid(N)), block(kThreads);   // two resident workgroups per CU, as the conv launches
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (h_prev) hipLaunchKernelGGL(torus_bf16_heads_fwd_kernel<true>, grid, block, 0, s, a);
+    else hipLaunchKernelGGL(torus_bf16_heads_fwd_kernel<false>, grid, block, 0, s, a);
+    return status();
+}
+
+int hrl_torus_bf16_heads_backward(const float *dpolicy, const float *dvalue, const float *value, const float *pooled,
+                                  const float *head_p, const float *head_v, const float *x, int64_t x_stride,
+                                  const void *y, const void *h_prev, const float *alpha, const float *beta,
+                                  const float *save_mean, int64_t N, int64_t H, int64_t W, float *gm, double *part,
+                                  float *dhead_p, float *dhead_v, void *workspace, int64_t workspace_bytes,
+                                  void *stream) {
+    if (!tail_shape_ok(N, H, W) || !value || !pooled || !head_p || !head_v || !x || x_stride < H * W || !y || !alpha ||
+        !beta || !save_mean || !gm || !part || !dhead_p || !dhead_v || !workspace ||
+        workspace_bytes < hrl_torus_bf16_heads_workspace_bytes(N) || !aligned16(y) || !aligned16(h_prev) ||
+        !aligned16(gm) || !aligned16(workspace))
+        return HRL_EINVAL;
+    if (N == 0) return HRL_OK;
+    TailArgs a{};
+    a.N = N; a.x_stride = x_stride; a.HW = (int)(H * W); a.y = static_cast<const uint4 *>(y);
+    a.hprev = static_cast<const uint4 *>(h_prev); a.alpha = alpha; a.beta = beta; a.x = x; a.head_p = head_p;
+    a.head_v = head_v; a.value = const_cast<float *>(value); a.pooled = const_cast<float *>(pooled);
+    a.dpolicy = dpolicy; a.dvalue = dvalue; a.mean = save_mean; a.gm = reinterpret_cast<float4 *>(gm); a.part = part;
+    a.wpart = static_cast<double *>(workspace);
+    // conv_grid(N) rows of part, as every other producer of it
+    const dim3 grid(conv_grid(N)), block(kThreads);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (h_prev) hipLaunchKernelGGL(torus_bf16_heads_bwd_kernel<true>, grid, block, 0, s, a);
+    else hipLaunchKernelGGL(torus_bf16_heads_bwd_kernel<false>, grid, block, 0, s, a);
+    const int rc = status();
+    if (rc) return rc;
+    hipLaunchKernelGGL(torus_bf16_heads_fold_kernel, dim3(1), dim3(kHeadW), 0, s, a.wpart, (int)grid.x, dhead_p, dhead_v);
     return status();
 }
 

@@ -75,8 +75,12 @@ class GeeseNet(nn.Module):
     def forward(self, x, _=None):
         if self.training and self.conv0.use_hip and self.conv0.bn is not None and x.is_cuda:
             # accelerated training step: the unit chain is one HIP Function (nn.torus_tower)
-            from ..nn import torus_tower
-            h = torus_tower(x, [self.conv0, *self.blocks], getattr(self, 'tower_precision', 'fp32'))
+            from ..nn import torus_tower, torus_tower_heads
+            precision = getattr(self, 'tower_precision', 'fp32')
+            if precision == 'bf16_heads':   # the tower with the pool and both heads fused into its tail
+                p, v = torus_tower_heads(x, [self.conv0, *self.blocks], self.head_p, self.head_v)
+                return {'policy': p, 'value': v}
+            h = torus_tower(x, [self.conv0, *self.blocks], precision)
         else:
             h = F.relu(self.conv0(x))
             for block in self.blocks:

@@ -1345,6 +1345,98 @@ TOWER_BN_FOLD = True
 _CUT_FN = None
 
 
+def _bf16_units_forward(x, units, params):
+    """The mixed-precision tower's unit loop (one hrl_torus_bf16_pack launch, then per unit its conv launch and
+    hrl_bn_finalize_stats): (weights, pack, coef, ys, hs) with hs[i] unit i's stored input (hs[0] None: x)."""
+    N, Cin, H, W = x.shape
+    HW = H * W
+    dev = x.device
+    lib = _native.load()
+    stream = _native.stream_of(dev)
+    P = _native.ptr
+    n = len(units)
+    weights = [params[4 * i].contiguous() for i in range(n)]
+    pack = torch.empty(lib.hrl_torus_bf16_pack_bytes(n), dtype=torch.uint8, device=dev)
+    _native.check(lib.hrl_torus_bf16_pack(_native.ptr_array(weights), n, Cin, P(pack), pack.numel(), stream),
+                  'hrl_torus_bf16_pack')
+    nparts = lib.hrl_torus_bf16_stats_blocks(N)
+    part = torch.empty(nparts * 64, dtype=torch.float64, device=dev)
+    coef = torch.empty(n, 4, 32, device=dev, dtype=x.dtype)   # per unit: save_mean, save_invstd, alpha, beta
+
+    def stored():
+        return torch.empty(N, HW, 32, device=dev, dtype=torch.bfloat16)
+    ys, hs = [], [None]   # hs[i]: unit i's input (unit 0's is x)
+    for i in range(n):
+        b, gamma, beta = params[4 * i + 1], params[4 * i + 2], params[4 * i + 3]
+        y = stored()
+        if i == 0:
+            _native.check(lib.hrl_torus_bf16_unit_forward(P(x), None, None, None, None, None, N, H, W, P(pack), 0,
+                                                          P(b), P(y), P(part), stream),
+                          'hrl_torus_bf16_unit_forward(stem)')
+        else:
+            h = stored()
+            _native.check(lib.hrl_torus_bf16_unit_forward(None, P(ys[-1]), P(hs[-1]) if i >= 2 else None,
+                                                          P(coef[i - 1, 2]), P(coef[i - 1, 3]), P(h), N, H, W,
+                                                          P(pack), i, P(b), P(y), P(part), stream),
+                          'hrl_torus_bf16_unit_forward')
+            hs.append(h)
+        rm, rv, momentum, eps = units[i]
+        _native.check(lib.hrl_bn_finalize_stats(P(part), nparts, 32, N * HW, P(gamma), P(beta), P(rm), P(rv),
+                                                momentum, eps, P(coef[i, 0]), P(coef[i, 1]), P(coef[i, 2]),
+                                                P(coef[i, 3]), stream), 'hrl_bn_finalize_stats')
+        ys.append(y)
+    return weights, pack, coef, ys, hs
+
+
+def _bf16_units_backward(x, coef, pack, gammas, ys, hs, wshapes, last_unit):
+    """The mixed-precision tower's backward loop.  ``last_unit(gm, part)`` launches what writes the last unit's
+    masked fp32 gradient (N, H*W, 32) and its two backward sums; returns the units' parameter gradients."""
+    n = len(ys)
+    N, Cin, H, W = x.shape
+    HW = H * W
+    dev, dtype = x.device, x.dtype
+    lib = _native.load()
+    stream = _native.stream_of(dev)
+    P = _native.ptr
+    ws_bytes = lib.hrl_torus_bf16_workspace_bytes(N)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    nparts = lib.hrl_torus_bf16_stats_blocks(N)
+    part = torch.empty(nparts * 64, dtype=torch.float64, device=dev)
+    kg = torch.empty(2, 32, device=dev, dtype=dtype)   # k, mean(gm) of the unit being applied
+    grads = [None] * (4 * n)
+    for i in range(n):
+        grads[4 * i + 2] = torch.empty(32, device=dev, dtype=dtype)
+        grads[4 * i + 3] = torch.empty(32, device=dev, dtype=dtype)
+
+    def finalize(i):
+        _native.check(lib.hrl_bn_finalize_backward(P(part), nparts, 32, N * HW, P(gammas[i]), P(coef[i, 1]),
+                                                   P(grads[4 * i + 2]), P(grads[4 * i + 3]), P(kg[0]), P(kg[1]),
+                                                   stream), 'hrl_bn_finalize_backward')
+    g_cur, g_fp32 = torch.empty(N, HW, 32, device=dev, dtype=dtype), 1
+    last_unit(g_cur, part)
+    finalize(n - 1)
+    dy = torch.empty(N, HW, 32, device=dev, dtype=torch.bfloat16)
+    for i in range(n - 1, -1, -1):
+        dw = torch.empty(wshapes[i], device=dev, dtype=dtype)
+        db = torch.empty(32, device=dev, dtype=dtype)
+        _native.check(lib.hrl_torus_bf16_wgrad_bn(P(x) if i == 0 else None, P(hs[i]), N, H, W, P(ys[i]), P(g_cur),
+                                                  g_fp32, P(coef[i, 2]), P(coef[i, 3]), 1 if i >= 1 else 0,
+                                                  P(gammas[i]), P(coef[i, 0]), P(coef[i, 1]), P(kg[0]), P(kg[1]),
+                                                  P(dy), P(dw), P(db), P(ws), ws_bytes, stream),
+                      'hrl_torus_bf16_wgrad_bn')
+        grads[4 * i], grads[4 * i + 1] = dw, db
+        if i == 0:
+            break
+        g_prev = torch.empty(N, HW, 32, device=dev, dtype=torch.bfloat16)
+        _native.check(lib.hrl_torus_bf16_unit_input_grad(P(dy), N, H, W, P(pack), i, P(g_cur), g_fp32,
+                                                         P(hs[i + 1]) if i + 1 < n else None, P(g_prev), P(hs[i]),
+                                                         P(ys[i - 1]), P(coef[i - 1, 0]), P(part), stream),
+                      'hrl_torus_bf16_unit_input_grad')
+        finalize(i - 1)
+        g_cur, g_fp32 = g_prev, 0
+    return grads
+
+
 class _TorusTowerBf16(torch.autograd.Function):
     """_TorusTower in mixed precision (csrc/hrl_torus_bf16.hip; the numeric contract is in include/hrl_nn.h): the
     same launch sequence, one launch per role and unit, each in its bf16 form.  Conv operands and every stored
@@ -1355,46 +1447,14 @@ class _TorusTowerBf16(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, units, *params):
         x = x.contiguous()
-        N, Cin, H, W = x.shape
-        HW = H * W
-        dev = x.device
-        lib = _native.load()
-        stream = _native.stream_of(dev)
-        P = _native.ptr
+        N, _, H, W = x.shape
         n = len(units)
-        weights = [params[4 * i].contiguous() for i in range(n)]
-        pack = torch.empty(lib.hrl_torus_bf16_pack_bytes(n), dtype=torch.uint8, device=dev)
-        _native.check(lib.hrl_torus_bf16_pack(_native.ptr_array(weights), n, Cin, P(pack), pack.numel(), stream),
-                      'hrl_torus_bf16_pack')
-        nparts = lib.hrl_torus_bf16_stats_blocks(N)
-        part = torch.empty(nparts * 64, dtype=torch.float64, device=dev)
-        coef = torch.empty(n, 4, 32, device=dev, dtype=x.dtype)   # per unit: save_mean, save_invstd, alpha, beta
-
-        def stored():
-            return torch.empty(N, HW, 32, device=dev, dtype=torch.bfloat16)
-        ys, hs = [], [None]   # hs[i]: unit i's input (unit 0's is x)
-        for i in range(n):
-            b, gamma, beta = params[4 * i + 1], params[4 * i + 2], params[4 * i + 3]
-            y = stored()
-            if i == 0:
-                _native.check(lib.hrl_torus_bf16_unit_forward(P(x), None, None, None, None, None, N, H, W, P(pack), 0,
-                                                              P(b), P(y), P(part), stream),
-                              'hrl_torus_bf16_unit_forward(stem)')
-            else:
-                h = stored()
-                _native.check(lib.hrl_torus_bf16_unit_forward(None, P(ys[-1]), P(hs[-1]) if i >= 2 else None,
-                                                              P(coef[i - 1, 2]), P(coef[i - 1, 3]), P(h), N, H, W,
-                                                              P(pack), i, P(b), P(y), P(part), stream),
-                              'hrl_torus_bf16_unit_forward')
-                hs.append(h)
-            rm, rv, momentum, eps = units[i]
-            _native.check(lib.hrl_bn_finalize_stats(P(part), nparts, 32, N * HW, P(gamma), P(beta), P(rm), P(rv),
-                                                    momentum, eps, P(coef[i, 0]), P(coef[i, 1]), P(coef[i, 2]),
-                                                    P(coef[i, 3]), stream), 'hrl_bn_finalize_stats')
-            ys.append(y)
-        out = torch.empty(N, 32, H, W, device=dev, dtype=x.dtype)
+        lib, P = _native.load(), _native.ptr
+        weights, pack, coef, ys, hs = _bf16_units_forward(x, units, params)
+        out = torch.empty(N, 32, H, W, device=x.device, dtype=x.dtype)
         _native.check(lib.hrl_torus_bf16_output(P(ys[-1]), P(hs[-1]) if n >= 2 else None, P(coef[n - 1, 2]),
-                                                P(coef[n - 1, 3]), N, H, W, P(out), stream), 'hrl_torus_bf16_output')
+                                                P(coef[n - 1, 3]), N, H, W, P(out), _native.stream_of(x.device)),
+                      'hrl_torus_bf16_output')
         gammas = [params[4 * i + 2] for i in range(n)]
         ctx.save_for_backward(x, out, coef, pack, *gammas, *ys, *hs[1:])
         ctx.n = n
@@ -1408,54 +1468,69 @@ class _TorusTowerBf16(torch.autograd.Function):
         x, out, coef, pack = saved[:4]
         gammas, ys, hs = saved[4:4 + n], saved[4 + n:4 + 2 * n], (None,) + tuple(saved[4 + 2 * n:])
         g = g.contiguous()
-        N, Cin, H, W = x.shape
-        HW = H * W
-        dev = x.device
-        lib = _native.load()
-        stream = _native.stream_of(dev)
-        P = _native.ptr
-        ws_bytes = lib.hrl_torus_bf16_workspace_bytes(N)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        nparts = lib.hrl_torus_bf16_stats_blocks(N)
-        part = torch.empty(nparts * 64, dtype=torch.float64, device=dev)
-        kg = torch.empty(2, 32, device=dev, dtype=g.dtype)   # k, mean(gm) of the unit being applied
-        grads = [None] * (4 * n)
-        for i in range(n):
-            grads[4 * i + 2] = torch.empty(32, device=dev, dtype=g.dtype)
-            grads[4 * i + 3] = torch.empty(32, device=dev, dtype=g.dtype)
+        N, _, H, W = x.shape
+        lib, P = _native.load(), _native.ptr
 
-        def finalize(i):
-            _native.check(lib.hrl_bn_finalize_backward(P(part), nparts, 32, N * HW, P(gammas[i]), P(coef[i, 1]),
-                                                       P(grads[4 * i + 2]), P(grads[4 * i + 3]), P(kg[0]), P(kg[1]),
-                                                       stream), 'hrl_bn_finalize_backward')
-        # the last unit: the pool's fp32 NCHW gradient, masked, as fp32 channels-last, with its backward sums
-        g_cur, g_fp32 = torch.empty(N, HW, 32, device=dev, dtype=g.dtype), 1
-        _native.check(lib.hrl_torus_bf16_masked_sums(P(g), P(out), P(ys[-1]), P(coef[n - 1, 0]), N, H, W, P(g_cur),
-                                                     P(part), stream), 'hrl_torus_bf16_masked_sums')
-        finalize(n - 1)
-        dy = torch.empty(N, HW, 32, device=dev, dtype=torch.bfloat16)
-        for i in range(n - 1, -1, -1):
-            dw = torch.empty(ctx.wshapes[i], device=dev, dtype=g.dtype)
-            db = torch.empty(32, device=dev, dtype=g.dtype)
-            _native.check(lib.hrl_torus_bf16_wgrad_bn(P(x) if i == 0 else None, P(hs[i]), N, H, W, P(ys[i]), P(g_cur),
-                                                      g_fp32, P(coef[i, 2]), P(coef[i, 3]), 1 if i >= 1 else 0,
-                                                      P(gammas[i]), P(coef[i, 0]), P(coef[i, 1]), P(kg[0]), P(kg[1]),
-                                                      P(dy), P(dw), P(db), P(ws), ws_bytes, stream),
-                          'hrl_torus_bf16_wgrad_bn')
-            grads[4 * i], grads[4 * i + 1] = dw, db
-            if i == 0:
-                break
-            g_prev = torch.empty(N, HW, 32, device=dev, dtype=torch.bfloat16)
-            _native.check(lib.hrl_torus_bf16_unit_input_grad(P(dy), N, H, W, P(pack), i, P(g_cur), g_fp32,
-                                                             P(hs[i + 1]) if i + 1 < n else None, P(g_prev), P(hs[i]),
-                                                             P(ys[i - 1]), P(coef[i - 1, 0]), P(part), stream),
-                          'hrl_torus_bf16_unit_input_grad')
-            finalize(i - 1)
-            g_cur, g_fp32 = g_prev, 0
-        return (None, None, *grads)
+        def last_unit(gm, part):
+            # the pool's fp32 NCHW gradient, masked, as fp32 channels-last, with its backward sums
+            _native.check(lib.hrl_torus_bf16_masked_sums(P(g), P(out), P(ys[-1]), P(coef[n - 1, 0]), N, H, W, P(gm),
+                                                         P(part), _native.stream_of(x.device)),
+                          'hrl_torus_bf16_masked_sums')
+        return (None, None, *_bf16_units_backward(x, coef, pack, gammas, ys, hs, ctx.wshapes, last_unit))
+
+
+class _TorusTowerHeadsBf16(torch.autograd.Function):
+    """_TorusTowerBf16 with GeeseNet's tail fused (train_args precision: 'bf16_heads'): the same unit loops, but the
+    last unit's output, the pool and both heads are one launch each way (hrl_torus_bf16_heads_forward / _backward,
+    contract in include/hrl_nn.h) and no fp32 board tensor exists in the forward.  x (fp32 NCHW, data) and the two
+    bias-free head weights in, (policy (N, 4), value (N, 1)) out; saved beside the tower's tensors: value, pooled."""
+
+    @staticmethod
+    def forward(ctx, x, units, head_p, head_v, *params):
+        x = x.contiguous()
+        head_p, head_v = head_p.contiguous(), head_v.contiguous()
+        N, Cin, H, W = x.shape
+        n = len(units)
+        lib, P = _native.load(), _native.ptr
+        weights, pack, coef, ys, hs = _bf16_units_forward(x, units, params)
+        policy = torch.empty(N, 4, device=x.device, dtype=x.dtype)
+        value = torch.empty(N, 1, device=x.device, dtype=x.dtype)
+        pooled = torch.empty(N, 64, device=x.device, dtype=x.dtype)
+        _native.check(lib.hrl_torus_bf16_heads_forward(P(ys[-1]), P(hs[-1]) if n >= 2 else None, P(coef[n - 1, 2]),
+                                                       P(coef[n - 1, 3]), P(x), Cin * H * W, P(head_p), P(head_v), N,
+                                                       H, W, P(policy), P(value), P(pooled),
+                                                       _native.stream_of(x.device)), 'hrl_torus_bf16_heads_forward')
+        gammas = [params[4 * i + 2] for i in range(n)]
+        ctx.save_for_backward(x, coef, pack, head_p, head_v, value, pooled, *gammas, *ys, *hs[1:])
+        ctx.n = n
+        ctx.wshapes = [tuple(w.shape) for w in weights]
+        return policy, value
+
+    @staticmethod
+    def backward(ctx, dpolicy, dvalue):
+        n = ctx.n
+        saved = ctx.saved_tensors
+        x, coef, pack, head_p, head_v, value, pooled = saved[:7]
+        gammas, ys, hs = saved[7:7 + n], saved[7 + n:7 + 2 * n], (None,) + tuple(saved[7 + 2 * n:])
+        dpolicy = None if dpolicy is None else dpolicy.contiguous()
+        dvalue = None if dvalue is None else dvalue.contiguous()
+        N, Cin, H, W = x.shape
+        lib, P = _native.load(), _native.ptr
+        dhead_p, dhead_v = torch.empty_like(head_p), torch.empty_like(head_v)
+        ws = torch.empty(lib.hrl_torus_bf16_heads_workspace_bytes(N), dtype=torch.uint8, device=x.device)
+
+        def last_unit(gm, part):
+            _native.check(lib.hrl_torus_bf16_heads_backward(
+                P(dpolicy), P(dvalue), P(value), P(pooled), P(head_p), P(head_v), P(x), Cin * H * W, P(ys[-1]),
+                P(hs[-1]) if n >= 2 else None, P(coef[n - 1, 2]), P(coef[n - 1, 3]), P(coef[n - 1, 0]), N, H, W,
+                P(gm), P(part), P(dhead_p), P(dhead_v), P(ws), ws.numel(), _native.stream_of(x.device)),
+                'hrl_torus_bf16_heads_backward')
+        grads = _bf16_units_backward(x, coef, pack, gammas, ys, hs, ctx.wshapes, last_unit)
+        return (None, None, dhead_p, dhead_v, *grads)
 
 
 TOWER_PRECISIONS = ('fp32', 'bf16')
+LEARNER_PRECISIONS = TOWER_PRECISIONS + ('bf16_heads',)   # train_args' ``precision``
 
 
 def torus_tower(x, units, precision='fp32'):
@@ -1469,6 +1544,9 @@ def torus_tower(x, units, precision='fp32'):
 
     ``precision='bf16'`` (train_args' ``precision``) is the mixed-precision form, _TorusTowerBf16: bf16 conv
     operands and stored activations / gradients, everything else fp32.  It has no split form."""
+    if precision == 'bf16_heads':
+        raise ValueError("torus_tower: precision 'bf16_heads' has no block output to return (the tower ends in the "
+                         "heads): call torus_tower_heads(x, units, head_p, head_v)")
     if precision not in TOWER_PRECISIONS:
         raise ValueError("torus_tower: precision is 'fp32' or 'bf16', not %r" % (precision,))
     k = getattr(units[0], 'tower_split', None)
@@ -1486,31 +1564,53 @@ def torus_tower(x, units, precision='fp32'):
     return _tower_part(x, units, False)
 
 
+def _stock_geese_heads(head_p, head_v):
+    """True for GeeseNet's two heads as the fused tail takes them: bias-free Linear 32 -> 4 and 64 -> 1."""
+    return (isinstance(head_p, nn.Linear) and isinstance(head_v, nn.Linear) and head_p.bias is None
+            and head_v.bias is None and tuple(head_p.weight.shape) == (4, 32) and tuple(head_v.weight.shape) == (1, 64))
+
+
+def torus_tower_heads(x, units, head_p, head_v):
+    """GeeseNet's whole training forward as one HIP Function (_TorusTowerHeadsBf16, train_args' ``precision:
+    bf16_heads``): the mixed-precision tower of ``torus_tower(precision='bf16')`` over ``units``, then the pool and
+    the bias-free Linear modules ``head_p`` (32 -> 4) and ``head_v`` (64 -> 1) in one launch each way.  Returns
+    (policy (N, 4), value (N, 1)); the gradients reach every unit's parameters and both head weights."""
+    if not _stock_geese_heads(head_p, head_v):
+        raise ValueError('torus_tower_heads: the heads are bias-free Linear modules 32 -> 4 and 64 -> 1')
+    k = getattr(units[0], 'tower_split', None)
+    if k is not None and 0 < k < len(units):
+        raise NotImplementedError("torus_tower_heads: the mixed-precision tower has no data-parallel split "
+                                  "(tower_split = %r)" % (k,))
+    return _tower_part(x, units, False, _TorusTowerHeadsBf16, (head_p.weight, head_v.weight))
+
+
 def configured_precision(value, net, device):
     """``train_args['precision']`` applied to the net the learner trains: ``fp32`` (or absent) leaves it as it is;
     ``bf16`` makes a GeeseNet's training forward run its tower in mixed precision (``torus_tower(precision='bf16')``
-    through ``net.tower_precision``).  Anything else raises here, at start-up, by the key's name: another value, a
-    net that is not GeeseNet-shaped (32 filters, 1..16 blocks: ``geese_inference_ok``), a device that is not the
-    GPU, or a tower split for a data-parallel segmented backward."""
+    through ``net.tower_precision``); ``bf16_heads`` runs that tower with the pool and heads fused into its last
+    launch each way (``torus_tower_heads``), under the same rules (the shape check covers the bias-free heads).
+    Anything else raises here, at start-up, by the key's name: another value, a net that is not GeeseNet-shaped
+    (32 filters, 1..16 blocks: ``geese_inference_ok``), a device that is not the GPU, or a tower split for a
+    data-parallel segmented backward."""
     value = 'fp32' if value is None else value
-    if value not in TOWER_PRECISIONS:
-        raise ValueError("train_args['precision'] must be fp32 or bf16 (or absent), not %r" % (value,))
-    if value == 'bf16':
+    if value not in LEARNER_PRECISIONS:
+        raise ValueError("train_args['precision'] must be fp32, bf16 or bf16_heads (or absent), not %r" % (value,))
+    if value != 'fp32':
         if not geese_inference_ok(net):
-            raise ValueError("train_args['precision']: 'bf16' trains GeeseNet's tower (32 filters, 1..16 blocks); "
-                             "%s is not one (geese_inference_ok)" % type(net).__name__)
+            raise ValueError("train_args['precision']: %r trains GeeseNet's tower (32 filters, 1..16 blocks); "
+                             "%s is not one (geese_inference_ok)" % (value, type(net).__name__))
         if torch.device(device).type != 'cuda':
-            raise ValueError("train_args['precision']: 'bf16' is the mixed-precision tower on the GPU; the device "
-                             "is %s" % (device,))
+            raise ValueError("train_args['precision']: %r is the mixed-precision tower on the GPU; the device "
+                             "is %s" % (value, device))
         if getattr(net.conv0, 'tower_split', None):
-            raise NotImplementedError("train_args['precision']: 'bf16' has no data-parallel split (tower_split); "
-                                      "train one GPU per process or keep precision fp32")
-    if value == 'bf16' or hasattr(net, 'tower_precision'):
+            raise NotImplementedError("train_args['precision']: %r has no data-parallel split (tower_split); "
+                                      "train one GPU per process or keep precision fp32" % (value,))
+    if value != 'fp32' or hasattr(net, 'tower_precision'):
         net.tower_precision = value
     return value
 
 
-def _tower_part(x, units, residual_in, function=None):
+def _tower_part(x, units, residual_in, function=None, leading=()):
     meta, params = [], []
     for unit in units:
         bn = unit.bn
@@ -1523,7 +1623,7 @@ def _tower_part(x, units, residual_in, function=None):
                      bn.running_var if bn.track_running_stats else None, momentum, bn.eps))
         params += [unit.conv.weight, unit.conv.bias, bn.weight, bn.bias]
     if function is not None:
-        return function.apply(x, meta, *params)
+        return function.apply(x, meta, *leading, *params)
     return _TorusTower.apply(x, meta, residual_in, *params)
 
 

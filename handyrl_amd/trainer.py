@@ -169,7 +169,8 @@ class LearnerStep:
             self.reducer = hdist.GradAllReduce(self.grads, group=reduce_group, bucket_bytes=bucket_bytes)
             if self.graph and segment_backward:
                 split_torus_tower(self.net)   # only a segmented capture uses the cut (eager: one Function)
-        # train_args['precision']: bf16 runs a GeeseNet's tower in mixed precision (nn.configured_precision's rules)
+        # train_args['precision']: bf16 runs a GeeseNet's tower in mixed precision, bf16_heads with its tail fused
+        # (nn.configured_precision's rules)
         self.precision = hnn.configured_precision(args.get('precision'), self.net, device)
         if lr is None:
             # train.py:318-321: lr = 3e-8 * batch_size * forward_steps for the batch ONE update sees.

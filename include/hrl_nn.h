@@ -450,6 +450,44 @@ int hrl_torus_bf16_wgrad_bn(const float *x, const void *h, int64_t N, int64_t H,
 int hrl_torus_bf16_unit_input_grad(const void *dy, int64_t N, int64_t H, int64_t W, const void *pack, int64_t unit,
                                    const void *g, int g_fp32, const void *h_next, void *dh, const void *h_mask,
                                    const void *y_prev, const float *mean_prev, double *part, void *stream);
+/*
+ * The mixed-precision tower's fused tail (train_args precision: 'bf16_heads'): the last unit's output, GeeseNet's
+ * pool and both bias-free heads in one launch each way, with no fp32 board tensor in the forward.  L = the last
+ * unit, y = Y_L, h_prev = H_L (NULL for a one-unit tower: no residual), alpha / beta unit L's coefficients,
+ * x the net's input with sample stride x_stride >= H*W floats (only plane 0, x[n * x_stride + q], is read),
+ * head_p (4, 32), head_v (1, 64) fp32.
+ *
+ * hrl_torus_bf16_heads_forward:
+ *   out[q][c] = relu([float(H) +] float(Y) alpha + beta), fp32, unrounded, hrl_torus_bf16_output's operations;
+ *   h_head[c] = sum_q out x0[q], h_avg[c] = (sum_q out) / (H*W) (hrl_torus_head_pool's definitions; a sum is a
+ *   lane's cells in order, then a fixed butterfly over 16 lanes); pooled (N, 64) = [h_head | h_avg];
+ *   policy (N, 4) = head_p . h_head; value (N, 1) = tanhf(head_v . [h_head, h_avg]); both products are summed
+ *   in fp64 and rounded once.
+ * hrl_torus_bf16_heads_backward: dpolicy (N, 4), dvalue (N, 1), either may be NULL (zero); value and pooled as the
+ *   forward wrote them; save_mean unit L's.
+ *   dv = dvalue (1 - value^2); dhead = head_p^T dpolicy + dv head_v[:32] (fp64 sum, one rounding);
+ *   davg = dv head_v[32:];
+ *   gm[n][q][c] = (dhead[c] x0[q] + davg[c] / (H*W)) [bf(out) > 0], fp32 [sample][cell][32]: what
+ *   hrl_torus_bf16_masked_sums writes (the same mask bits), read by hrl_torus_bf16_wgrad_bn / _unit_input_grad
+ *   with g_fp32 != 0; part[block][c] = (sum gm, sum gm (float(Y) - mean)), hrl_torus_bf16_stats_blocks(N) rows,
+ *   fp32 per sample, fp64 across samples -> hrl_bn_finalize_backward.
+ *   dhead_p[a][c] = sum_n dpolicy[n][a] h_head[n][c], dhead_v[j] = sum_n dv[n] pooled[n][j]: fp64 products and sums
+ *   across samples, per-workgroup partials in workspace (hrl_torus_bf16_heads_workspace_bytes(N) bytes) folded in
+ *   a fixed order by a second small launch; no atomics, the same bits on every call.
+ * y, h_prev, pooled (forward), gm and workspace are 16-byte aligned.  Any NULL (but h_prev, dpolicy, dvalue),
+ * misaligned or out-of-range argument (H*W > 80, x_stride < H*W, N < 0, a short workspace) is HRL_EINVAL before
+ * anything is launched; N == 0 is HRL_OK with no launch.
+ */
+int64_t hrl_torus_bf16_heads_workspace_bytes(int64_t N);
+int hrl_torus_bf16_heads_forward(const void *y, const void *h_prev, const float *alpha, const float *beta,
+                                 const float *x, int64_t x_stride, const float *head_p, const float *head_v, int64_t N,
+                                 int64_t H, int64_t W, float *policy, float *value, float *pooled, void *stream);
+int hrl_torus_bf16_heads_backward(const float *dpolicy, const float *dvalue, const float *value, const float *pooled,
+                                  const float *head_p, const float *head_v, const float *x, int64_t x_stride,
+                                  const void *y, const void *h_prev, const float *alpha, const float *beta,
+                                  const float *save_mean, int64_t N, int64_t H, int64_t W, float *gm, double *part,
+                                  float *dhead_p, float *dhead_v, void *workspace, int64_t workspace_bytes,
+                                  void *stream);
 
 /* A zero-padded 3x3 'same' nn.Conv2d, 32 input channels -> Cout (a multiple of 32) on a board of 4..80 cells,
  * on the torus kernel's MFMA path (GeisterNet's ConvLSTM h / x halves, geister.py:48-59): x (N, 32, H, W),
