@@ -695,12 +695,22 @@ class _DRCStep(torch.autograd.Function):
     the K-split adjoint conv (gboard_adjoint_split's grouped launch, summed in the gate kernel) and accumulates the
     x half's gradient over the repeats; each repeat records its (h, dz) for the deferred weight gradient.
 
-    apply(meta, *zx, *h, *c) -> (*h', *c'); meta = (ws, h slice of the weights, pad, packed, DeferredGrads, R)."""
+    apply(meta, *zx, *h, *c) -> (*h', *c'); meta = (ws, h slice of the weights, pad, packed, DeferredGrads, R) and,
+    for the bf16 forward, two more entries: the precision 'bf16_drc' and the cells' h halves packed by drc_bf16_pack.
+
+    precision 'bf16_drc': each repeat's forward is ONE launch, hrl_drc_bf16_repeat_forward (include/hrl_nn.h has the
+    numeric contract: bf16 h and h-half weights on one MFMA per product, the accumulator started from zx, fp32 gates
+    and state, no zh tensor).  It saves the tensors the fp32 forward saves -- the unrounded h_r, c_r, c_out and the
+    activated gates -- and the backward above runs on them unchanged: the fp32 step's gradient evaluated at the saved
+    activations, with the fp32 master weights in the exact-split adjoint and weight-gradient kernels, i.e.
+    straight-through across the roundings of h and W_h."""
 
     @staticmethod
     def forward(ctx, meta, *args):
         ctx.set_materialize_grads(False)
-        ws, sl, pad, packed, rec, R = meta
+        ws, sl, pad, packed, rec, R = meta[:6]
+        pack16 = meta[7] if len(meta) > 6 and meta[6] == 'bf16_drc' else None
+        meta = meta[:6]
         L = len(ws)
         zx, hs, cs = args[:L], list(args[L:2 * L]), list(args[2 * L:])
         N, H = hs[0].shape[0], hs[0].shape[1]
@@ -713,8 +723,23 @@ class _DRCStep(torch.autograd.Function):
         zx_ptrs = _native.ptr_array(zx)
         zx_strides = _native.i64_array([z.stride(0) for z in zx])
         saved = []
-        _check_gboard_packed(packed, L * 4 * H, H)
+        if pack16 is None:
+            _check_gboard_packed(packed, L * 4 * H, H)
         for _ in range(R):
+            if pack16 is not None:
+                h_out = [torch.empty_like(c) for c in cs]
+                c_out = [torch.empty_like(c) for c in cs]
+                gates = [torch.empty(N, 4 * H, 6, 6, device=cs[0].device) if lv else None for lv in live]
+                _native.check(lib.hrl_drc_bf16_repeat_forward(
+                    P(pack16), pack16.numel(), L, H, zx_ptrs, zx_strides, _native.ptr_array(hs),
+                    _native.i64_array([h.stride(0) for h in hs]), _native.ptr_array(cs),
+                    _native.i64_array([c.stride(0) for c in cs]), N, _native.ptr_array(h_out),
+                    _native.ptr_array(c_out), _native.ptr_array(gates), stream), 'hrl_drc_bf16_repeat_forward')
+                for i in range(L):
+                    if live[i]:
+                        saved += [hs[i], cs[i], c_out[i], gates[i]]
+                hs, cs = h_out, c_out
+                continue
             zh = torch.empty(N, L * 4 * H, 6, 6, device=hs[0].device)
             _native.check(lib.hrl_gboard_forward_groups(
                 _native.ptr_array(hs), _native.i64_array([h.stride(0) for h in hs]), N, H, L, P(packed),
@@ -806,10 +831,33 @@ def drc_step_ok(zx, hs, cs, ws, pad):
             and all(t.shape[0] == hs[0].shape[0] for t in (*zx, *hs, *cs)))
 
 
-def drc_step(zx, hs, cs, ws, sl, pad, packed, repeats):
-    """The repeats of the DRC cells at one time step of a deferred unroll (_DRCStep); returns (hs', cs')."""
+def drc_bf16_pack(ws, ci0):
+    """The h halves (input channels [ci0, ci0 + 32)) of the cells' (128, Cin, 3, 3) weights ws as the bf16 column
+    operands of hrl_drc_bf16_repeat_forward, one launch (rounded to nearest even here, once per unroll)."""
+    lib = _native.load()
+    ws = [w.detach().contiguous() for w in ws]
+    nbytes = lib.hrl_drc_bf16_pack_bytes(len(ws))
+    if nbytes <= 0 or any(tuple(w.shape) != (128, ws[0].shape[1], 3, 3) or w.dtype != torch.float32 for w in ws):
+        raise ValueError('hrl_drc_bf16_pack: 1..4 fp32 cell weights (128, Cin, 3, 3), not %s'
+                         % ([tuple(w.shape) for w in ws],))
+    pack = torch.empty(nbytes, dtype=torch.uint8, device=ws[0].device)
+    _native.check(lib.hrl_drc_bf16_pack(_native.ptr_array(ws), len(ws), ws[0].shape[1], ci0, _native.ptr(pack), nbytes,
+                                        _native.stream_of(pack.device)), 'hrl_drc_bf16_pack')
+    return pack
+
+
+def drc_step(zx, hs, cs, ws, sl, pad, packed, repeats, precision='fp32'):
+    """The repeats of the DRC cells at one time step of a deferred unroll (_DRCStep); returns (hs', cs').
+    precision 'bf16_drc': ``packed`` is drc_bf16_pack's buffer (or None: packed here) and every repeat's forward is
+    one hrl_drc_bf16_repeat_forward launch; the gradient is the fp32 step's at the saved activations."""
     L = len(ws)
-    out = _DRCStep.apply((ws, sl, tuple(pad), packed, _DEFER, repeats), *zx, *hs, *cs)
+    if precision not in ('fp32', 'bf16_drc'):
+        raise ValueError("drc_step: precision is 'fp32' or 'bf16_drc', not %r" % (precision,))
+    meta = (ws, sl, tuple(pad), packed, _DEFER, repeats)
+    if precision == 'bf16_drc':
+        meta = (ws, sl, tuple(pad), None, _DEFER, repeats, precision,
+                drc_bf16_pack(ws, sl[0]) if packed is None else packed)
+    out = _DRCStep.apply(meta, *zx, *hs, *cs)
     return list(out[:L]), list(out[L:])
 
 
@@ -1530,7 +1578,7 @@ class _TorusTowerHeadsBf16(torch.autograd.Function):
 
 
 TOWER_PRECISIONS = ('fp32', 'bf16')
-LEARNER_PRECISIONS = TOWER_PRECISIONS + ('bf16_heads',)   # train_args' ``precision``
+LEARNER_PRECISIONS = TOWER_PRECISIONS + ('bf16_heads', 'bf16_drc')   # train_args' ``precision``
 
 
 def torus_tower(x, units, precision='fp32'):
@@ -1588,13 +1636,29 @@ def configured_precision(value, net, device):
     """``train_args['precision']`` applied to the net the learner trains: ``fp32`` (or absent) leaves it as it is;
     ``bf16`` makes a GeeseNet's training forward run its tower in mixed precision (``torus_tower(precision='bf16')``
     through ``net.tower_precision``); ``bf16_heads`` runs that tower with the pool and heads fused into its last
-    launch each way (``torus_tower_heads``), under the same rules (the shape check covers the bias-free heads).
+    launch each way (``torus_tower_heads``), under the same rules (the shape check covers the bias-free heads);
+    ``bf16_drc`` makes a GeisterNet's learner unroll run each repeat of its DRC cells as one bf16 launch
+    (``drc_step(precision='bf16_drc')`` through ``net.body.step_precision``) and needs a DRC body inside
+    ``drc_step_ok``'s shape rules (1..4 cells, 3x3 'same', 32 hidden channels, 6x6 board) on the GPU.
     Anything else raises here, at start-up, by the key's name: another value, a net that is not GeeseNet-shaped
     (32 filters, 1..16 blocks: ``geese_inference_ok``), a device that is not the GPU, or a tower split for a
     data-parallel segmented backward."""
     value = 'fp32' if value is None else value
     if value not in LEARNER_PRECISIONS:
-        raise ValueError("train_args['precision'] must be fp32, bf16 or bf16_heads (or absent), not %r" % (value,))
+        raise ValueError("train_args['precision'] must be fp32, bf16, bf16_heads or bf16_drc (or absent), not %r"
+                         % (value,))
+    if value == 'bf16_drc':
+        if not drc_body_ok(net):
+            raise ValueError("train_args['precision']: 'bf16_drc' trains GeisterNet's DRC body (1..4 ConvLSTM cells, "
+                             "3x3 'same', 32 hidden channels, 6x6 board); %s has none (drc_body_ok)"
+                             % type(net).__name__)
+        if torch.device(device).type != 'cuda':
+            raise ValueError("train_args['precision']: 'bf16_drc' is the one-launch bf16 repeat on the GPU; the "
+                             "device is %s" % (device,))
+        net.body.step_precision = value
+        return value
+    if getattr(getattr(net, 'body', None), 'step_precision', 'fp32') != 'fp32':
+        net.body.step_precision = 'fp32'   # a net configured for bf16_drc before
     if value != 'fp32':
         if not geese_inference_ok(net):
             raise ValueError("train_args['precision']: %r trains GeeseNet's tower (32 filters, 1..16 blocks); "
@@ -1608,6 +1672,20 @@ def configured_precision(value, net, device):
     if value != 'fp32' or hasattr(net, 'tower_precision'):
         net.tower_precision = value
     return value
+
+
+def drc_body_ok(net):
+    """True for a net whose recurrent body the bf16 DRC step takes (drc_step_ok's shape rules, read off the modules):
+    ``net.body.blocks`` are 1..4 ConvLSTM cells with 32 hidden channels and 3x3 'same' convs over 32 + 32 input
+    channels, on GeisterNet's 6x6 board."""
+    body = getattr(net, 'body', None)
+    blocks = getattr(body, 'blocks', None)
+    if blocks is None or not 1 <= len(blocks) <= 4 or not hasattr(body, 'step_hip'):
+        return False
+    return all(getattr(b, 'hidden_dim', None) == 32 and isinstance(getattr(b, 'conv', None), nn.Conv2d)
+               and tuple(b.conv.weight.shape) == (128, 64, 3, 3) and tuple(b.conv.padding) == (1, 1)
+               and tuple(b.conv.stride) == (1, 1) and tuple(b.conv.dilation) == (1, 1) and b.conv.groups == 1
+               for b in blocks)
 
 
 def _tower_part(x, units, residual_in, function=None, leading=()):

@@ -878,6 +878,45 @@ int hrl_geister_infer_bf16(const void *pack, int64_t layers, int64_t num_repeats
                            const float *board, const float *scalar, const float *h, const float *c, int64_t N,
                            float *policy, float *value, float *ret, float *h_out, float *c_out, void *stream);
 
+/* One repeat of a DRC's L ConvLSTM cells at one time step of the learner's unroll as ONE launch with bf16 h-half
+ * operands (csrc/hrl_drc_bf16.hip; train_args precision: bf16_drc): the forward of hrl_gboard_forward_groups +
+ * hrl_lstm_gates_forward_grouped without the zh tensor between them.  6x6 board, H = 32 hidden channels, 3x3 'same'
+ * cells, L in 1..4.  Asynchronous, no allocation, no workspace, capturable; every argument is validated (HRL_EINVAL)
+ * before any HIP call.
+ * Numerics:
+ *   - the h-half weights are rounded fp32 -> bf16 once, at pack time, round to nearest even;
+ *   - h_in is rounded to bf16 (nearest even) as it is staged as the conv operand;
+ *   - everything else is fp32: the MFMA accumulator is initialised from zx (the x half, which already carries the
+ *     cell bias) and then takes the h half's products, input cells in order, one v_mfma_f32_16x16x32_bf16 per
+ *     on-board tap (K = 32 is all h channels); the gates use hrl_lstm_gates_forward's sigm / tanhf on the chunks
+ *     i, f, o, g (ConvLSTMCell.forward's order); c' = f*c + i*g and h' = o*tanh(c') are written unrounded;
+ *   - c never passes through bf16.
+ *   A row's result depends on nothing but the row (not on N or its place in the batch).  Deterministic.
+ *   Gradient (nn._DRCStep.backward, unchanged): the fp32 step's backward evaluated at the saved activations -- the
+ *   gate backward on the stored gates, the exact-split adjoint and weight-gradient kernels on the fp32 master
+ *   weights and the unrounded h_in: straight-through across the two roundings.
+ * hrl_drc_bf16_pack_bytes: 73,728 * L (0 for L outside 1..4).
+ * hrl_drc_bf16_pack: ONE launch; weights: host array of L device pointers, each a cell's (128, w_cin_total, 3, 3)
+ *   fp32 weight read in place, its h half being input channels [w_ci0, w_ci0 + 32).  Writes the MFMA column operands
+ *   [layer][tile 8][tap 9][lane 64][8 bf16]; column j of tile T is gate j >> 2 of hidden channel 4T + (j & 3).
+ *   HRL_EINVAL: L outside 1..4, a NULL pointer, a pack that is not 16-byte aligned, w_ci0 < 0 or
+ *   w_ci0 + 32 > w_cin_total, pack_bytes below hrl_drc_bf16_pack_bytes(L).
+ * hrl_drc_bf16_repeat_forward: ONE launch of ceil(N/16) * L * 8 workgroups.  zx, h_in, c_in: host arrays of L device
+ *   pointers with a row stride (floats) each: zx[l] (N, 128, 6, 6), possibly a channel slice of a wider tensor,
+ *   h_in[l] and c_in[l] (N, 32, 6, 6).  h_out[l], c_out[l] (N, 32, 6, 6) contiguous; gates (NULL, or a host array
+ *   whose NULL entries mean "not stored") receives the activated i, f, o, g as (N, 128, 6, 6) contiguous, the layout
+ *   hrl_lstm_gates_backward_ex reads.  No output may overlap an input (eight workgroups read each h_in tile).
+ *   HRL_EINVAL: H != 32, L outside 1..4, a NULL or not 16-byte-aligned pointer, a stride that is no multiple of 4
+ *   floats or below the tensor's row, pack_bytes below hrl_drc_bf16_pack_bytes(L), N < 0 or N > 2^24.  N == 0:
+ *   HRL_OK, no launch. */
+int64_t hrl_drc_bf16_pack_bytes(int64_t L);
+int hrl_drc_bf16_pack(const float *const *weights, int64_t L, int64_t w_cin_total, int64_t w_ci0, void *pack,
+                      int64_t pack_bytes, void *stream);
+int hrl_drc_bf16_repeat_forward(const void *pack, int64_t pack_bytes, int64_t L, int64_t H, const float *const *zx,
+                                const int64_t *zx_strides, const float *const *h_in, const int64_t *h_strides,
+                                const float *const *c_in, const int64_t *c_strides, int64_t N, float *const *h_out,
+                                float *const *c_out, float *const *gates, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
