@@ -125,8 +125,8 @@ class DRC(nn.Module):
     # (nn.drc_step) instead of a conv and a gate launch per layer
     group_repeat = os.environ.get('HRL_DRC_GROUPED', '1') == '1'
     _inplace = False  # the session advances a stacked state in place (DeviceGenerator)
-    # train_args' ``precision``: 'bf16_drc' runs each repeat of the learner's grouped step as one bf16 launch
-    # (nn.configured_precision sets it; nn.drc_step)
+    # train_args' ``precision``: 'bf16_drc' runs each repeat of the learner's grouped step as one bf16 launch,
+    # 'bf16_drc_bwd' the step's backward as one launch as well (nn.configured_precision sets it; nn.drc_step)
     step_precision = 'fp32'
 
     def _stacked_weights(self, out=None):
@@ -259,13 +259,15 @@ class DRC(nn.Module):
         cin = c_all - self.blocks[0].hidden_dim
         deferred = hnn._DEFER is not None
         w_h = None if deferred else [w[:, cin:].contiguous() for w in ws]
-        if self.step_precision == 'bf16_drc':
+        if self.step_precision in ('bf16_drc', 'bf16_drc_bwd'):
             # no quiet return to the fp32 kernels: the option is the one-launch bf16 repeat or an error
             if not (deferred and torch.is_grad_enabled() and hnn.drc_step_ok(zx, hs, cs, ws, pad)):
-                raise RuntimeError("precision 'bf16_drc' covers the learner's deferred-gradient unroll of 1..4 3x3 "
-                                   "cells with 32 hidden channels on the 6x6 board (nn.drc_step_ok)")
-            pack16 = packed_h.get('bf16_drc') if isinstance(packed_h, dict) else None
-            hs, cs = hnn.drc_step(zx, hs, cs, ws, (cin, c_all), pad, pack16, num_repeats, precision='bf16_drc')
+                raise RuntimeError("precision %r covers the learner's deferred-gradient unroll of 1..4 3x3 "
+                                   "cells with 32 hidden channels on the 6x6 board (nn.drc_step_ok)"
+                                   % self.step_precision)
+            pack16 = packed_h.get(self.step_precision) if isinstance(packed_h, dict) else None
+            hs, cs = hnn.drc_step(zx, hs, cs, ws, (cin, c_all), pad, pack16, num_repeats,
+                                  precision=self.step_precision)
             return hs[-1], (hs, cs)
         if (deferred and isinstance(packed_h, dict) and self.group_repeat
                 and hnn.drc_step_ok(zx, hs, cs, ws, pad)):
@@ -535,6 +537,10 @@ class GeisterNet(nn.Module):
         if hnn._DEFER is not None and self.body.step_precision == 'bf16_drc':
             # the h halves as bf16 MFMA operands, one launch per unroll (the backward packs its own exact split)
             packed_h = {'bf16_drc': hnn.drc_bf16_pack([c.weight for c in cells], cin)}
+        elif hnn._DEFER is not None and self.body.step_precision == 'bf16_drc_bwd':
+            # both ways in bf16: the forward's operands and the one-launch backward's adjoint operands
+            packed_h = {'bf16_drc_bwd': (hnn.drc_bf16_pack([c.weight for c in cells], cin),
+                                         hnn.drc_bf16_adjoint_pack([c.weight for c in cells], cin))}
         elif hnn._DEFER is not None and hnn.gboard_conv_ok(h_e[:1, :hd], cells[0].weight, hd, cells[0].padding):
             w_h = torch.cat([c.weight.detach()[:, cin:] for c in cells])
             packed_h = {'layers': [hnn.gboard_pack(c.weight.detach(), hd, cin) for c in cells],

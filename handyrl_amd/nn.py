@@ -703,13 +703,19 @@ class _DRCStep(torch.autograd.Function):
     and state, no zh tensor).  It saves the tensors the fp32 forward saves -- the unrounded h_r, c_r, c_out and the
     activated gates -- and the backward above runs on them unchanged: the fp32 step's gradient evaluated at the saved
     activations, with the fp32 master weights in the exact-split adjoint and weight-gradient kernels, i.e.
-    straight-through across the roundings of h and W_h."""
+    straight-through across the roundings of h and W_h.
+
+    precision 'bf16_drc_bwd' (a ninth entry: drc_bf16_adjoint_pack's buffer): that forward, and the whole backward
+    as ONE launch for all live layers and repeats, hrl_drc_bf16_step_backward -- the gate backward's float
+    operations, the adjoint on bf16(dz) and bf16(W_h) with dh and dc kept on chip between the repeats, no partial
+    input gradients and no sums; the R (h_r, dz_r) pairs are recorded as the loop records them."""
 
     @staticmethod
     def forward(ctx, meta, *args):
         ctx.set_materialize_grads(False)
         ws, sl, pad, packed, rec, R = meta[:6]
-        pack16 = meta[7] if len(meta) > 6 and meta[6] == 'bf16_drc' else None
+        pack16 = meta[7] if len(meta) > 6 and meta[6] in ('bf16_drc', 'bf16_drc_bwd') else None
+        ctx.adjoint_pack = meta[8] if len(meta) > 8 and meta[6] == 'bf16_drc_bwd' else None
         meta = meta[:6]
         L = len(ws)
         zx, hs, cs = args[:L], list(args[L:2 * L]), list(args[2 * L:])
@@ -770,6 +776,8 @@ class _DRCStep(torch.autograd.Function):
         saved = ctx.saved_tensors
         dzx, dh, dc = [None] * L, [None] * L, [None] * L
         lib = _native.load()
+        if ctx.adjoint_pack is not None:
+            return (None, *_drc_bf16_step_backward(ctx, grads))
         k = -1
         for i in range(L):
             if not live[i]:
@@ -818,6 +826,56 @@ class _DRCStep(torch.autograd.Function):
         return (None, *dzx, *dh, *dc)
 
 
+def _drc_bf16_step_backward(ctx, grads):
+    """_DRCStep.backward under precision 'bf16_drc_bwd': one hrl_drc_bf16_step_backward launch for every live layer
+    that a gradient reached; returns (*dzx, *dh, *dc)."""
+    ws, sl, pad, packed, rec, R = ctx.meta
+    L, live, saved = len(ws), ctx.live, ctx.saved_tensors
+    nl = sum(live)
+    dzx, dh, dc = [None] * L, [None] * L, [None] * L
+    todo, k = [], -1
+    for i in range(L):
+        if not live[i]:
+            if grads[i] is not None or grads[L + i] is not None:
+                raise RuntimeError('DRC step: a gradient reached layer %d, whose x half was computed without '
+                                   'autograd (DRC.x_halves)' % i)
+            continue
+        k += 1
+        if grads[i] is not None or grads[L + i] is not None:
+            todo.append((i, k))
+    if not todo:
+        return (*dzx, *dh, *dc)
+    N, H = saved[0].shape[0], saved[0].shape[1]
+    dev = saved[0].device
+    new = lambda ch: torch.empty(N, ch, 6, 6, device=dev)
+    gates, c_in, c_out, dz, gh, gc = [], [], [], [], [], []
+    for i, k in todo:
+        for r in range(R):
+            h_r, c_r, co_r, g_r = saved[4 * (r * nl + k):4 * (r * nl + k) + 4]
+            gates.append(g_r)
+            c_in.append(c_r)
+            c_out.append(co_r)
+            dz.append(new(4 * H))
+        for src, dst in ((grads[i], gh), (grads[L + i], gc)):
+            dst.append(src if src is None or (src.stride(0) % 4 == 0 and src[0].is_contiguous())
+                       else src.contiguous())
+        dzx[i] = new(4 * H) if ctx.needs_input_grad[1 + i] else None
+        dh[i] = new(H) if ctx.needs_input_grad[1 + L + i] else None
+        dc[i] = new(H) if ctx.needs_input_grad[1 + 2 * L + i] else None
+    pack = ctx.adjoint_pack
+    A = _native.ptr_array
+    strides = lambda ts: _native.i64_array([0 if t is None else t.stride(0) for t in ts])
+    _native.check(_native.load().hrl_drc_bf16_step_backward(
+        _native.ptr(pack), pack.numel(), _native.i64_array([i for i, _ in todo]), len(todo), R, H, A(gates), A(c_in),
+        A(c_out), A(gh), strides(gh), A(gc), strides(gc), N, A(dz), A([dzx[i] for i, _ in todo]),
+        A([dh[i] for i, _ in todo]), A([dc[i] for i, _ in todo]), _native.stream_of(dev)),
+        'hrl_drc_bf16_step_backward')
+    for j, (i, k) in enumerate(todo):
+        for r in range(R - 1, -1, -1):   # the order the per-repeat loop records them in
+            rec.add_conv((ws[i], None, sl, tuple(pad)), saved[4 * (r * nl + k)], dz[j * R + r], late=True)
+    return (*dzx, *dh, *dc)
+
+
 def drc_step_ok(zx, hs, cs, ws, pad):
     """_DRCStep covers: 1..4 layers of 3x3 'same' cells on the 6x6 board, H = 32 hidden channels, fp32 CUDA
     float4-aligned games (zx may be channel slices of a wider tensor)."""
@@ -846,17 +904,37 @@ def drc_bf16_pack(ws, ci0):
     return pack
 
 
+def drc_bf16_adjoint_pack(ws, ci0):
+    """The h halves of the cells' weights ws (as drc_bf16_pack takes them) as the bf16 column operands of
+    hrl_drc_bf16_step_backward's adjoint, one launch (rounded to nearest even here, once per unroll)."""
+    lib = _native.load()
+    ws = [w.detach().contiguous() for w in ws]
+    nbytes = lib.hrl_drc_bf16_adjoint_pack_bytes(len(ws))
+    if nbytes <= 0 or any(tuple(w.shape) != (128, ws[0].shape[1], 3, 3) or w.dtype != torch.float32 for w in ws):
+        raise ValueError('hrl_drc_bf16_adjoint_pack: 1..4 fp32 cell weights (128, Cin, 3, 3), not %s'
+                         % ([tuple(w.shape) for w in ws],))
+    pack = torch.empty(nbytes, dtype=torch.uint8, device=ws[0].device)
+    _native.check(lib.hrl_drc_bf16_adjoint_pack(_native.ptr_array(ws), len(ws), ws[0].shape[1], ci0, _native.ptr(pack),
+                                                nbytes, _native.stream_of(pack.device)), 'hrl_drc_bf16_adjoint_pack')
+    return pack
+
+
 def drc_step(zx, hs, cs, ws, sl, pad, packed, repeats, precision='fp32'):
     """The repeats of the DRC cells at one time step of a deferred unroll (_DRCStep); returns (hs', cs').
     precision 'bf16_drc': ``packed`` is drc_bf16_pack's buffer (or None: packed here) and every repeat's forward is
-    one hrl_drc_bf16_repeat_forward launch; the gradient is the fp32 step's at the saved activations."""
+    one hrl_drc_bf16_repeat_forward launch; the gradient is the fp32 step's at the saved activations.
+    precision 'bf16_drc_bwd': that forward, and the step's whole backward as one hrl_drc_bf16_step_backward launch;
+    ``packed`` is the pair (drc_bf16_pack's, drc_bf16_adjoint_pack's) or None."""
     L = len(ws)
-    if precision not in ('fp32', 'bf16_drc'):
-        raise ValueError("drc_step: precision is 'fp32' or 'bf16_drc', not %r" % (precision,))
+    if precision not in ('fp32', 'bf16_drc', 'bf16_drc_bwd'):
+        raise ValueError("drc_step: precision is 'fp32', 'bf16_drc' or 'bf16_drc_bwd', not %r" % (precision,))
     meta = (ws, sl, tuple(pad), packed, _DEFER, repeats)
     if precision == 'bf16_drc':
         meta = (ws, sl, tuple(pad), None, _DEFER, repeats, precision,
                 drc_bf16_pack(ws, sl[0]) if packed is None else packed)
+    elif precision == 'bf16_drc_bwd':
+        fwd, adj = (drc_bf16_pack(ws, sl[0]), drc_bf16_adjoint_pack(ws, sl[0])) if packed is None else packed
+        meta = (ws, sl, tuple(pad), None, _DEFER, repeats, precision, fwd, adj)
     out = _DRCStep.apply(meta, *zx, *hs, *cs)
     return list(out[:L]), list(out[L:])
 
@@ -1578,7 +1656,7 @@ class _TorusTowerHeadsBf16(torch.autograd.Function):
 
 
 TOWER_PRECISIONS = ('fp32', 'bf16')
-LEARNER_PRECISIONS = TOWER_PRECISIONS + ('bf16_heads', 'bf16_drc')   # train_args' ``precision``
+LEARNER_PRECISIONS = TOWER_PRECISIONS + ('bf16_heads', 'bf16_drc', 'bf16_drc_bwd')   # train_args' ``precision``
 
 
 def torus_tower(x, units, precision='fp32'):
@@ -1639,22 +1717,23 @@ def configured_precision(value, net, device):
     launch each way (``torus_tower_heads``), under the same rules (the shape check covers the bias-free heads);
     ``bf16_drc`` makes a GeisterNet's learner unroll run each repeat of its DRC cells as one bf16 launch
     (``drc_step(precision='bf16_drc')`` through ``net.body.step_precision``) and needs a DRC body inside
-    ``drc_step_ok``'s shape rules (1..4 cells, 3x3 'same', 32 hidden channels, 6x6 board) on the GPU.
+    ``drc_step_ok``'s shape rules (1..4 cells, 3x3 'same', 32 hidden channels, 6x6 board) on the GPU;
+    ``bf16_drc_bwd`` is ``bf16_drc`` with the step's backward as one launch as well, under the same rules.
     Anything else raises here, at start-up, by the key's name: another value, a net that is not GeeseNet-shaped
     (32 filters, 1..16 blocks: ``geese_inference_ok``), a device that is not the GPU, or a tower split for a
     data-parallel segmented backward."""
     value = 'fp32' if value is None else value
     if value not in LEARNER_PRECISIONS:
-        raise ValueError("train_args['precision'] must be fp32, bf16, bf16_heads or bf16_drc (or absent), not %r"
+        raise ValueError("train_args['precision'] must be fp32, bf16, bf16_heads, bf16_drc or bf16_drc_bwd (or absent), not %r"
                          % (value,))
-    if value == 'bf16_drc':
+    if value in ('bf16_drc', 'bf16_drc_bwd'):
         if not drc_body_ok(net):
-            raise ValueError("train_args['precision']: 'bf16_drc' trains GeisterNet's DRC body (1..4 ConvLSTM cells, "
+            raise ValueError("train_args['precision']: %r trains GeisterNet's DRC body (1..4 ConvLSTM cells, "
                              "3x3 'same', 32 hidden channels, 6x6 board); %s has none (drc_body_ok)"
-                             % type(net).__name__)
+                             % (value, type(net).__name__))
         if torch.device(device).type != 'cuda':
-            raise ValueError("train_args['precision']: 'bf16_drc' is the one-launch bf16 repeat on the GPU; the "
-                             "device is %s" % (device,))
+            raise ValueError("train_args['precision']: %r is the one-launch bf16 repeat on the GPU; the "
+                             "device is %s" % (value, device))
         net.body.step_precision = value
         return value
     if getattr(getattr(net, 'body', None), 'step_precision', 'fp32') != 'fp32':

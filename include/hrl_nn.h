@@ -917,6 +917,48 @@ int hrl_drc_bf16_repeat_forward(const void *pack, int64_t pack_bytes, int64_t L,
                                 const float *const *c_in, const int64_t *c_strides, int64_t N, float *const *h_out,
                                 float *const *c_out, float *const *gates, void *stream);
 
+/* The whole backward of a DRC time step (nn._DRCStep: R repeats of the ConvLSTM cells) as ONE launch for all live
+ * layers (csrc/hrl_drc_bf16_bwd.hip; train_args precision: bf16_drc_bwd).  It replaces, per live layer and repeat,
+ * hrl_lstm_gates_backward_ex and the K-split exact adjoint conv with its S partial input gradients, and the sum that
+ * follows them.  6x6 board, H = 32 hidden channels, 3x3 'same' cells, L_live in 1..4, R in 1..8.  Asynchronous, no
+ * allocation, no workspace, capturable, no atomics; every argument is validated (HRL_EINVAL) before any HIP call.
+ * Per (live layer l, game), for r = R-1 .. 0:
+ *   - gate backward: hrl_lstm_gates_backward_ex's float operations on the saved activated gates[l*R + r] (i, f, o, g
+ *     as (N, 128, 6, 6)), c[l*R + r] and c_out[l*R + r] ((N, 32, 6, 6)), all contiguous.  At r = R-1 dh is gh[l] and
+ *     dc_out is gc[l] (row strides gh_strides[l], gc_strides[l]; a NULL entry means zero); below that dh is the
+ *     adjoint's result of repeat r+1 and dc_out the dc of repeat r+1's gate backward, neither of which leaves the chip;
+ *   - dz[l*R + r] (N, 128, 6, 6) contiguous receives dz_r as fp32, unrounded (the deferred weight gradient reads it);
+ *   - dzx[l] (NULL: not wanted) = dz_{R-1} + dz_{R-2} + ... + dz_0, added in fp32 in that order, written once;
+ *   - adjoint, unless r == 0 and dh_in[l] is NULL:
+ *       dh[n, ci, q] = sum over taps, over k of bf16(dz_r[n, k, q - tap]) * bf16(W[k, ci0 + ci, tap]),
+ *     K = 128 gate columns x the on-board taps, on v_mfma_f32_16x16x32_bf16 with fp32 accumulation from zero, the
+ *     taps 0..8 in order and within a tap the chunks i, f, o, g (an off-board tap adds exact zeros).  dz_r is rounded
+ *     to nearest-even bf16 as it is staged as the operand; the copy in HBM is not rounded; W is rounded at pack time.
+ *   After r = 0: dh_in[l] and dc_in[l] ((N, 32, 6, 6) contiguous; NULL: not wanted).
+ * Numerics: the gradient is the fp32 step's backward with one more straight-through rounding pair, of dz and W_h, in
+ *   the h-half adjoint only; dc never passes through bf16; a row's result depends on nothing but the row (not on N or
+ *   its place in the batch); deterministic.
+ * hrl_drc_bf16_adjoint_pack_bytes: 73,728 * L (0 for L outside 1..4).
+ * hrl_drc_bf16_adjoint_pack: ONE launch; arguments as hrl_drc_bf16_pack's.  Writes the adjoint's MFMA column operands
+ *   [layer][tap 9][k-step 4][column tile 2][lane 64][8 bf16]: lane l holds
+ *   bf16(W[32 ks + 8 (l >> 4) + e][w_ci0 + 16 ct + (l & 15)][tap]), e = 0..7; the tap is the forward's, the kernel
+ *   reads dz at the mirrored cell.  HRL_EINVAL as hrl_drc_bf16_pack.
+ * hrl_drc_bf16_step_backward: ONE launch of ceil(N/4) * L_live workgroups.  pack_layer[l]: the pack's layer of live
+ *   layer l.  gates, c, c_out, dz: host arrays of L_live * R device pointers; gh, gc, dzx, dh_in, dc_in: host arrays of
+ *   L_live device pointers whose entries may be NULL as said above.  No output may overlap an input or another output.
+ *   HRL_EINVAL: H != 32, L_live outside 1..4, R outside 1..8, a NULL array, a required pointer that is NULL, any
+ *   pointer that is not 16-byte aligned, a gh / gc stride that is no multiple of 4 floats or below 1152, pack_layer[l]
+ *   outside 0..3 or pack_bytes below hrl_drc_bf16_adjoint_pack_bytes(pack_layer[l] + 1), N < 0 or N > 2^24.
+ *   N == 0: HRL_OK, no launch. */
+int64_t hrl_drc_bf16_adjoint_pack_bytes(int64_t L);
+int hrl_drc_bf16_adjoint_pack(const float *const *weights, int64_t L, int64_t w_cin_total, int64_t w_ci0, void *pack,
+                              int64_t pack_bytes, void *stream);
+int hrl_drc_bf16_step_backward(const void *pack, int64_t pack_bytes, const int64_t *pack_layer, int64_t L_live,
+                               int64_t R, int64_t H, const float *const *gates, const float *const *c,
+                               const float *const *c_out, const float *const *gh, const int64_t *gh_strides,
+                               const float *const *gc, const int64_t *gc_strides, int64_t N, float *const *dz,
+                               float *const *dzx, float *const *dh_in, float *const *dc_in, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

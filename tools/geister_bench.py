@@ -1,7 +1,7 @@
 """Time the recurrent (GeisterNet, config C3) learner step on the GPU.
 
     python tools/geister_bench.py --B 256 1024 --T 16 --graph 0 1
-    python tools/geister_bench.py --B 256 --graph 1 --precision fp32 bf16_drc --rounds 9
+    python tools/geister_bench.py --B 256 --graph 1 --precision fp32 bf16_drc bf16_drc_bwd --rounds 9
 
 With more than one ``--precision`` (train_args' key) the forms run in ONE process, one learner each, alternating
 round by round; every form reports the median and min-max of its rounds' mean step time.
